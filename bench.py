@@ -3,7 +3,7 @@
 bench.py -- benchmark of the nd_amd hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload omnibus|c3|pipeline]
-                    [--scaling weak|strong] [--no-extra]
+                    [--scaling weak|strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -22,11 +22,17 @@ Workloads (--workload), all row-sharded over the ranks (nd_amd/tiles.py):
 Scaling (--scaling): weak (default) = every rank owns a raster of the stated size, the job's raster
 is N times as tall; strong = the stated raster is split over the ranks by tiles.row_partition.
 
-At N = 1 with the default workload the line also carries `cpu_baseline` (the C oracle on the host's
-cores).  `--extras` (its own invocation) adds the other kernels of the path (dense-threshold omnibus,
-multilooking, pixel-major, C3, boxcar, non-local means in both patch modes, Gaussian, the pipeline),
-each with ms, Mpx/s, roofline and a sampled oracle check: they are written to bench_extras.json, the
-long form of the headline (notes, per-step durations, N > 1 per-rank records) to bench_detail.json.
+A plain run sets up, warms up, times the K steps and prints the line: nothing else runs on the GPU or
+the host.  `--full` adds what the headline does not need: the other kernels' durations from a second
+loop of the step, at N = 1 `cpu_baseline` (the C oracle on the host's cores, default workload) or the
+sampled oracle check (the others), with the default workload and arguments the `secondary` block, at
+N > 1 the exchange timing and the boundary check, and the long form of the headline (notes, per-step
+durations, N > 1 per-rank records) in bench_detail.json.  `--extras` (its own invocation, implies
+`--full`) adds the other kernels of the path (dense-threshold omnibus, multilooking, pixel-major, C3,
+boxcar, non-local means in both patch modes, Gaussian, the pipeline), each with ms, Mpx/s, roofline and
+a sampled oracle check: they are written to bench_extras.json.  `--dump-outputs DIR` writes the change
+map of the last timed step (a fixed seeded sample of pixels and the per-row counts, dump_outputs()) as
+.npy files; the synthetic inputs are seeded, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no launcher around it starts the N ranks itself (the launch line above, as a
 child process) and relays rank 0's line; a WORLD_SIZE that differs from --gpus is an error.
@@ -108,17 +114,24 @@ def parse():
                     help='omnibus / c3: 0.99 (SURVEY 8d); pipeline: the tutorial\'s 1e-4')
     ap.add_argument('--change-frac', type=float, default=0.01)
     ap.add_argument('--patch-mode', type=int, default=0, help='pipeline: 0 reference, 1 signed')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline does not need: the other kernels\' durations '
+                         '(a second loop), the CPU baseline, the oracle checks, the `secondary` block, N > 1 '
+                         'exchange timing and boundary check, bench_detail.json')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last step computed to DIR/<name>.npy '
+                         '(float32 / float64, a fixed seeded sample of the change map and its per-row counts)')
     ap.add_argument('--cpu-rows', type=int, default=4096,
-                    help='rows of the stack the all-core CPU baseline is timed on (0 = skip)')
+                    help='--full: rows of the stack the all-core CPU baseline is timed on (0 = skip)')
     ap.add_argument('--extras', action='store_true',
                     help='N = 1, default workload: also run the secondary workloads (dense thresholds, '
                          'multilooking, pixel-major, C3, boxcar, Gaussian, non-local means, the pipeline), '
                          'device clocks and transfer rates; they go to bench_extras.json / '
-                         'bench_detail.json, never into the line')
+                         'bench_detail.json, never into the line (implies --full)')
     ap.add_argument('--no-extra', action='store_true', help='(accepted, ignored: extras are opt-in now)')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='N = 1, default workload: skip the `secondary` block of the line (BASELINE configs 3 - 5 '
-                         'at one GPU\'s share: a few steps and a sampled oracle check each, ~30 s of wall)')
+                    help='--full, N = 1, default workload: skip the `secondary` block of the line (BASELINE configs '
+                         '3 - 5 at one GPU\'s share: a few steps and a sampled oracle check each, ~30 s of wall)')
     ap.add_argument('--traffic-bytes', type=float, default=None,
                     help='HBM bytes per launch of the dominant kernel from a separate '
                          'rocprofv3 --pmc pass, copied into roofline.traffic')
@@ -126,6 +139,11 @@ def parse():
                     help='run only workload KEY (headline or one of the extras) for a few steps, '
                          'no timing events, no checks: the command rocprofv3 --pmc is pointed at')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    if a.warmup < 0:
+        ap.error('--warmup must not be negative')
+    a.full = a.full or a.extras
     dk, dy, dx = DEFAULTS[a.workload]
     a.k, a.ny, a.nx = a.k or dk, a.ny or dy, a.nx or dx
     if a.alpha is None:
@@ -1089,6 +1107,38 @@ def _write_sidecar(name, obj):
     return wrote
 
 
+DUMP_BYTES = 32 << 20      # --dump-outputs: all ranks' files together, well under 64 MB
+
+
+def dump_outputs(out, dirpath, rank, world):
+    """--dump-outputs: the change map of the last timed step (what the caller of the timed path receives,
+    uint8 (rows, nx, dates) on the device) as .npy files under `dirpath` -- its per-row change counts
+    whole, float64 (rows, dates), and a fixed seeded sample of pixels, float32 (pixels, dates), with
+    their flat indices y * nx + x, float64.  The same arguments give the same inputs, so two builds
+    can be compared file for file.  With N > 1 every rank writes its own rows' files (_rank<r>)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    rows, nx, k = out.shape
+    npix = rows * nx
+    counts = out.sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64)
+    per_px = 4 * k + 8
+    budget = DUMP_BYTES // world - counts.nbytes
+    if budget < per_px:
+        raise RuntimeError('--dump-outputs: %d rows x %d dates leave no room for a sample under %d bytes'
+                           % (rows, k, DUMP_BYTES))
+    rng = np.random.default_rng(7)
+    idx = np.unique(rng.integers(0, npix, min(npix, budget // per_px)))
+    flat = out.reshape(npix, k)
+    sample = flat[torch.from_numpy(idx).to(out.device)].cpu().numpy().astype(np.float32)
+    sfx = '_rank%d' % rank if world > 1 else ''
+    files = {'change_count_per_row': counts, 'change_sample': sample,
+             'change_sample_pixels': idx.astype(np.float64)}
+    for name, arr in files.items():
+        np.save(os.path.join(dirpath, name + sfx + '.npy'), arr)
+    return sorted(name + sfx for name in files)
+
+
 def launch_ranks(args, argv):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks the way the
     driver does (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -1231,7 +1281,13 @@ def main():
     state_before = device_state(local_rank) if args.extras else None
     dt, avg, out = timed(w.step, args.steps, args.warmup, barrier, only=[w.dom], per_step=per_step, settle=False)
     state_after = device_state(local_rank) if args.extras else None
-    _, avg_all, _ = timed(w.step, max(3, min(args.steps, 10)), 1, barrier, settle=False)
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, rank, world)
+    # the other kernels' durations: a second loop of the same step (--full, or when the dominant kernel did
+    # not run at all, so that the roofline has a kernel to be quoted on)
+    avg_all = {}
+    if args.full or w.dom not in avg:
+        _, avg_all, _ = timed(w.step, max(3, min(args.steps, 10)), 1, barrier, settle=False)
     avg_timed = dict(avg)                      # measured inside the timed region
     for name, ms in avg_all.items():
         avg.setdefault(name, ms)
@@ -1255,14 +1311,14 @@ def main():
         mine = {'rank': rank, 'device': torch.cuda.get_device_name(local_rank), 'device_index': local_rank,
                 'rows': [w.r0, w.r1], 'step_ms': local_dt / args.steps * 1e3,
                 'step_ms_median': sorted(per_step)[len(per_step) // 2] if per_step else None}
-        if hasattr(w, 'comm'):
+        if hasattr(w, 'comm') and args.full:
             mine.update(w.comm())
-            if hasattr(w, 'status_any'):
-                from nd_amd import kernels
-                kernels.raise_if_no_solution(w.status_any)
+        if hasattr(w, 'status_any'):
+            from nd_amd import kernels
+            kernels.raise_if_no_solution(w.status_any)
         ranks = [None] * world
         dist.all_gather_object(ranks, mine)
-        bcheck = boundary_check(w, out, dist, rank, world, rdev)
+        bcheck = boundary_check(w, out, dist, rank, world, rdev) if args.full else None
         comm_detail = {'backend': dist.get_backend(), 'world_size': dist.get_world_size(),
                        'data_path_collective': 'none (per-pixel path: every rank runs its own rows)'
                        if w.name != 'pipeline' else
@@ -1276,9 +1332,10 @@ def main():
                     'rank_cols': ['rank', 'device_index', 'row0', 'row1', 'step_ms'],
                     'ranks': [[r_['rank'], r_['device_index'], r_['rows'][0], r_['rows'][1], r_['step_ms']]
                               for r_ in ranks],
-                    'device': ranks[0]['device'],
-                    'boundary_check': {k_: bcheck[k_] for k_ in ('boundaries', 'map_bytes_compared',
-                                                                 'map_bytes_differing', 'filtered_values_differing')}}
+                    'device': ranks[0]['device']}
+            if bcheck is not None:
+                comm['boundary_check'] = {k_: bcheck[k_] for k_ in ('boundaries', 'map_bytes_compared',
+                                                                    'map_bytes_differing', 'filtered_values_differing')}
             if 'halo_bytes_sent_per_step' in ranks[0]:
                 comm['halo_bytes_sent_per_step'] = [r_['halo_bytes_sent_per_step'] for r_ in ranks]
                 comm['exchange_ms_alone'] = [r_['exchange_ms_alone'] for r_ in ranks]
@@ -1340,7 +1397,11 @@ def main():
                                'same step run again behind it; kernels_ms (the line): both together',
             'step_ms_all': per_step,
         }
-        if world == 1 and w.name == 'omnibus':
+        if not args.full:
+            if world == 1 and hasattr(w, 'status_any'):
+                from nd_amd import kernels
+                kernels.raise_if_no_solution(w.status_any)
+        elif world == 1 and w.name == 'omnibus':
             if args.cpu_rows > 0:
                 cb = cpu_baseline_omnibus(w, out)
                 detail['cpu_baseline'] = cb
@@ -1352,7 +1413,7 @@ def main():
             chk = w.check(out)
             detail['check'] = chk
             m['matches_oracle_on_sample'] = bool(chk.get('bad', 1) == 0 and chk.get('change_bad', 0) == 0)
-        if world == 1 and is_default and not args.no_secondary and not args.extras:
+        if args.full and world == 1 and is_default and not args.no_secondary and not args.extras:
             # configs 3 - 5 in the driver-run line (behind every timed region of the headline)
             m['secondary'], detail['secondary'] = secondary(w, barrier, dev)
         if args.extras and world == 1 and w.name == 'omnibus':
@@ -1361,8 +1422,9 @@ def main():
             detail['transfer'] = transfer_rates(dev)
             ex = extras(w, barrier, dev)
             m['extras_file'] = _write_sidecar('bench_extras.json', {'headline': headline(m), 'extra': ex})
-        detail['line'] = headline(m)
-        m['detail_file'] = _write_sidecar('bench_detail.json', detail)
+        if args.full:
+            detail['line'] = headline(m)
+            m['detail_file'] = _write_sidecar('bench_detail.json', detail)
         print(emit(headline(m)))
         sys.stdout.flush()
     if dist is not None:

@@ -15,6 +15,9 @@ What each file holds and where the expected outputs come from:
                     `pm1_*` pins the signed-patch semantics (patch_mode 1) through the
                     reference itself: with f = 0 and one channel per patch offset the
                     reference's variable loop IS the patch loop (interior pixels only).
+  nlmeans_live_ref.npz  inputs + outputs of the same kernel on small random float32 and float64
+                    arrays, and its find_weight(10, 5, 3): what the oracle is pinned to
+                    without a build of the reference at hand.
   convolve_scipy.npz inputs + outputs of scipy.ndimage.convolve (scipy is the reference's
                     arithmetic for ConvolutionFilter/BoxcarFilter, nd/filters.py:256-267;
                     cases from nd/tests/test_convolution_filter.py and SURVEY 8c F6).
@@ -93,6 +96,27 @@ def make_nlmeans():
     d['pm1_out_interior'] = ref[ry + fy:-(ry + fy), rx + fx:-(rx + fx), 0, centre]
     np.savez_compressed(os.path.join(HERE, 'nlmeans_ref.npz'), **d)
     print('nlmeans_ref.npz:', len(cases) + 1, 'cases')
+
+
+def make_nlmeans_live():
+    """nlmeans_live_ref.npz: the cases of tests/test_oracle_filters.py::test_nlmeans_live_reference
+    (float32 and float64, two-variable (y, x, time, var) arrays) through the real reference, and its
+    find_weight(10, 5, 3)."""
+    from nd import _filters as RF
+    d = {}
+    rng = np.random.default_rng(31)
+    params = [((2, 1, 1), (1, 1, 1), 0.5, 0.7, -1), ((2, 2, 1), (0, 0, 0), 0.5, 0.7, -1),
+              ((1, 2, 0), (0, 0, 0), 1.0, 2.0, 3.0)]
+    for dt in (np.float32, np.float64):
+        a = rng.normal(0, 1, (9, 11, 4, 2)).astype(dt)
+        for i, (r, f, s, h, ne) in enumerate(params):
+            name = '%s_%d' % (np.dtype(dt).name, i)
+            d[name + '__in'] = a
+            d[name + '__par'] = np.array(list(r) + list(f) + [s, h, ne], np.float64)
+            d[name + '__out'] = ref_nlmeans(a, r, f, s, h, ne)
+    d['find_weight_10_5_3'] = np.float64(RF.find_weight(10, 5, 3))
+    np.savez_compressed(os.path.join(HERE, 'nlmeans_live_ref.npz'), **d)
+    print('nlmeans_live_ref.npz:', 2 * len(params), 'cases')
 
 
 def make_convolve():
@@ -177,5 +201,6 @@ def make_omnibus():
 
 if __name__ == '__main__':
     make_nlmeans()
+    make_nlmeans_live()
     make_convolve()
     make_omnibus()

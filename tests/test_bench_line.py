@@ -1,7 +1,7 @@
 """bench.py's host logic, no GPU: the ONE line (headline object only, strict JSON, under 4 KB -- a
 longer line is cut by the driver's stdout tail and leaves the round unmeasured), the
---gpus / WORLD_SIZE agreement, and the self-launch of the N ranks (a child process, relayed exit
-code)."""
+--gpus / WORLD_SIZE agreement, the self-launch of the N ranks (a child process, relayed exit
+code), --full and --dump-outputs; one test marked gpu runs the plain benchmark on the device."""
 import json
 import os
 import subprocess
@@ -136,3 +136,89 @@ def test_gpus_n_starts_n_ranks_or_fails():
     assert p.returncode != 0
     assert p.stdout.strip() == ''                       # no result line of a job that did not run
     assert 'needs a ROCm GPU' in p.stderr
+
+
+def test_full_is_off_by_default_and_extras_imply_it(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', 'out'])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == 'out'
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--extras'])
+    assert bench.parse().full is True
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '0'])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def _read_dump(d):
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_dump_outputs_fixed_sample_of_the_change_map(tmp_path, monkeypatch):
+    """--dump-outputs on a host tensor: per-row counts whole, a seeded pixel sample, float32 / float64,
+    the same files from call to call, and within the size budget (shrunk here to force a sample)."""
+    import numpy as np
+    import torch
+    import bench
+    rows, nx, k = 40, 96, 8
+    out = torch.from_numpy((np.random.default_rng(3).random((rows, nx, k)) < 0.2).astype(np.uint8))
+    monkeypatch.setattr(bench, 'DUMP_BYTES', rows * k * 8 + 1000 * (4 * k + 8))
+    bench.dump_outputs(out, str(tmp_path / 'a'), 0, 1)
+    bench.dump_outputs(out, str(tmp_path / 'b'), 0, 1)
+    a, b = _read_dump(tmp_path / 'a'), _read_dump(tmp_path / 'b')
+    assert set(a) == {'change_count_per_row', 'change_sample', 'change_sample_pixels'}
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a[name], b[name])
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BYTES
+    host = out.numpy()
+    np.testing.assert_array_equal(a['change_count_per_row'], host.sum(axis=1))
+    px = a['change_sample_pixels'].astype(np.int64)
+    assert 500 < len(px) <= 1000 and np.all(np.diff(px) > 0) and px[-1] < rows * nx
+    np.testing.assert_array_equal(a['change_sample'], host.reshape(-1, k)[px])
+    bench.dump_outputs(out, str(tmp_path / 'r'), 1, 2)
+    assert sorted(os.listdir(tmp_path / 'r')) == ['change_count_per_row_rank1.npy', 'change_sample_pixels_rank1.npy',
+                                                  'change_sample_rank1.npy']
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path, oracle):
+    """A plain run: the headline fields, `steps` timed steps, nothing of --full in the line; two runs with
+    the same arguments dump the same outputs, and those are the oracle's change map of the seeded inputs.
+    --full adds the CPU baseline to the line."""
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip('no GPU')
+    from nd_amd import synth
+    k, ny, nx = 8, 96, 512
+    args = ['--gpus', '1', '--steps', '3', '--warmup', '1', '--k', str(k), '--ny', str(ny), '--nx', str(nx)]
+    lines = []
+    for d in ('a', 'b'):
+        p = _run(args + ['--dump-outputs', str(tmp_path / d)], timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    for line in lines:
+        assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0
+        assert line['unit'] == 'Mpixels/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+        want = ny * nx / (line['ms_per_step'] * 1e-3) / 1e6
+        assert abs(line['value'] - want) <= 1e-4 * want
+        for key in ('cpu_baseline', 'secondary', 'detail_file', 'matches_oracle_on_sample'):
+            assert key not in line, key
+    a, b = _read_dump(tmp_path / 'a'), _read_dump(tmp_path / 'b')
+    assert set(a) == {'change_count_per_row', 'change_sample', 'change_sample_pixels'}
+    for name in a:
+        np.testing.assert_array_equal(a[name], b[name])
+    st = synth.wishart_c2_stack(k, ny, nx, looks=9, seed=1234, device='cuda', change_frac=0.01).cpu().numpy()
+    want = oracle.change_detection_planes([np.moveaxis(st[v], 0, -1) for v in range(4)], 0.99, 9).astype(np.float64)
+    np.testing.assert_array_equal(a['change_count_per_row'], want.sum(axis=1))
+    px = a['change_sample_pixels'].astype(np.int64)
+    np.testing.assert_array_equal(a['change_sample'], want.reshape(-1, k)[px])
+    p = _run(args + ['--full'], timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    full = json.loads(p.stdout.strip().splitlines()[-1])
+    assert full['steps'] == 3 and full['cpu_baseline']['gpu_matches_cpu_on_sample'] is True

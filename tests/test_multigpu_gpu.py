@@ -239,7 +239,7 @@ def test_bench_launch_line_with_two_ranks(workload, extra, tmp_path):
     import json
     ny, nx, k = (96, 512, 8) if workload != 'pipeline' else (64, 512, 6)
     rc, lines, stderr = _bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', workload,
-                                '--ny', str(ny), '--nx', str(nx), '--k', str(k)] + extra, {}, tmp_path)
+                                '--ny', str(ny), '--nx', str(nx), '--k', str(k), '--full'] + extra, {}, tmp_path)
     assert rc == 0, stderr[-3000:]
     assert len(lines) == 1, lines                       # the contract: one JSON line, rank 0 only
     assert len(lines[0].encode()) < 4096
@@ -307,7 +307,7 @@ def test_bench_falls_back_to_the_sequential_halo_form(tmp_path):
     both ranks time the sequential form, the line says so, and the boundary check is still green."""
     import json
     rc, lines, stderr = _bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--workload', 'pipeline',
-                                '--ny', '64', '--nx', '512', '--k', '6'],
+                                '--ny', '64', '--nx', '512', '--k', '6', '--full'],
                                {'ND_AMD_BENCH_FORCE_OVERLAP_DIFF': '1'}, tmp_path)
     assert rc == 0, stderr[-3000:]
     comm = json.loads(lines[-1])['comm']

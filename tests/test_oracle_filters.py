@@ -1,14 +1,12 @@
 """Pins of the nlmeans and convolution oracles (CPU): the real reference (golden vectors from
-oracle/_ref, and oracle/_ref itself when it is present) and scipy.ndimage.convolve."""
-import glob
+oracle/_ref) and scipy.ndimage.convolve."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GN = os.path.join(os.path.dirname(__file__), 'golden', 'nlmeans_ref.npz')
+GL = os.path.join(os.path.dirname(__file__), 'golden', 'nlmeans_live_ref.npz')
 GC = os.path.join(os.path.dirname(__file__), 'golden', 'convolve_scipy.npz')
 
 
@@ -42,22 +40,20 @@ def test_nlmeans_patch_mode_1_pinned_through_reference(oracle):
     assert not np.array_equal(out0, out)
 
 
-@pytest.mark.skipif(not glob.glob(os.path.join(ROOT, 'oracle', '_ref', 'nd', '_filters*.so')),
-                    reason='oracle/_ref not built (needs /root/reference)')
 def test_nlmeans_live_reference(oracle):
-    sys.path.insert(0, os.path.join(ROOT, 'oracle', '_ref'))
-    from nd import _filters as RF
-    rng = np.random.default_rng(31)
-    for dt in (np.float32, np.float64):
-        a = rng.normal(0, 1, (9, 11, 4, 2)).astype(dt)
-        for r, f, s, h, ne in [((2, 1, 1), (1, 1, 1), 0.5, 0.7, -1), ((2, 2, 1), (0, 0, 0), 0.5, 0.7, -1),
-                               ((1, 2, 0), (0, 0, 0), 1.0, 2.0, 3.0)]:
-            want = np.empty_like(a)
-            RF._pixelwise_nlmeans_3d(a, want, np.array(r, np.uint32), np.array(f, np.uint32), s, h, ne)
-            got = np.empty_like(a)
-            oracle.pixelwise_nlmeans_3d(a, got, r, f, s, h, ne)
-            np.testing.assert_array_equal(got, want)
-    assert RF.find_weight(10, 5, 3) == oracle.find_weight(10, 5, 3)
+    """The reference kernel's outputs on random float32 / float64 arrays (tests/golden/make_golden.py
+    ran them through the build in oracle/_ref): the oracle must reproduce them bit for bit."""
+    g = np.load(GL)
+    names = sorted({n.split('__')[0] for n in g.files if '__' in n})
+    assert len(names) == 6
+    for name in names:
+        a, par, want = g[name + '__in'], g[name + '__par'], g[name + '__out']
+        assert a.dtype == want.dtype and a.dtype in (np.float32, np.float64)
+        got = np.empty_like(a)
+        oracle.pixelwise_nlmeans_3d(a, got, tuple(par[:3].astype(int)), tuple(par[3:6].astype(int)),
+                                    par[6], par[7], par[8])
+        np.testing.assert_array_equal(got, want, err_msg=name)
+    assert float(g['find_weight_10_5_3']) == oracle.find_weight(10, 5, 3)
     with pytest.raises(ValueError):
         oracle.find_weight(1.0, 1.0, 30.0)
 

@@ -22,7 +22,7 @@ cp $OUT/traffic/traffic.json $OUT/traffic.json
 mkdir -p $R/profiles && cp $OUT/traffic.json $R/profiles/r05_traffic.json     # bench.py reads it from there
 echo "traffic collected"
 cd $R
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err; cp bench_detail.json $OUT/bench_detail.json
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_line.json 2> $OUT/bench_line.err; cp bench_detail.json $OUT/bench_detail.json
 python3 bench.py --gpus 1 --steps 20 --warmup 5 --extras > $OUT/bench_line_extras_run.json 2> $OUT/bench_extras.err; cp bench_extras.json $OUT/bench_extras.json
 ls $OUT
 cat $OUT/omnibus_rocprof.txt | head -40

@@ -9,11 +9,11 @@
 #    bench_extras.json
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/$1; COMMIT=${2:-unknown}; mkdir -p $OUT
-CMD="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5"
+CMD="python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full"
 timeout -k 5 400 rocprofv3 --kernel-trace --stats -d $OUT/stats -o p --output-format csv -- $CMD > $OUT/stats.log 2>&1
 timeout -k 5 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o p --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --cpu-rows 0 --no-secondary > $OUT/fetch.log 2>&1
 timeout -k 5 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o p --output-format csv -- python3 $R/bench.py --steps 5 --warmup 1 --cpu-rows 0 --no-secondary > $OUT/write.log 2>&1
-python3 $R/tools/summarize_prof.py $OUT/stats $OUT/fetch $OUT/write $OUT/omnibus_rocprof.txt "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5   (the driver's command, secondary block included; PMC passes: --pmc FETCH_SIZE / --pmc WRITE_SIZE with --kernel-trace, --steps 5 --warmup 1); commit $COMMIT" > /dev/null
+python3 $R/tools/summarize_prof.py $OUT/stats $OUT/fetch $OUT/write $OUT/omnibus_rocprof.txt "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full   (the driver's command, secondary block included; PMC passes: --pmc FETCH_SIZE / --pmc WRITE_SIZE with --kernel-trace, --steps 5 --warmup 1); commit $COMMIT" > /dev/null
 cp $(find $OUT/stats -name 'p_kernel_stats.csv' | head -1) $OUT/bench_kernel_stats.csv 2>/dev/null
 rm -rf $OUT/stats $OUT/fetch $OUT/write
 echo "headline profiled"

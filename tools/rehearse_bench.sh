@@ -9,7 +9,7 @@ for v in "omnibus" "omnibus --scaling strong" "pipeline" "c3"; do
   if [ "$wl" = pipeline ]; then sz="--ny 64 --nx 512 --k 6"; else sz="--ny 96 --nx 512 --k 8"; fi
   t0=$(date +%s.%N)
   timeout -k 10 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-      --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --workload $wl $sz "$@" \
+      --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --workload $wl $sz --full "$@" \
       > gpurun_out/rehearse_$wl$#.out 2> gpurun_out/rehearse_$wl$#.err
   rc=$?
   t1=$(date +%s.%N)
