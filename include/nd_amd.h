@@ -96,7 +96,11 @@ const char *nd_amd_last_error(void);
  *              *min_bytes, the smallest size the call accepts; anything in
  *              between trades speed on change-rich rasters for memory.
  * njobs has no equivalent: the whole raster is one launch.
- * Series length: any k >= 1; parity-tested up to k = 193.  The first call
+ * Series length: any k >= 1; parity-tested up to k = 5200 (tests/
+ * test_long_series_gpu.py; fuzzed over 193 .. 4096).  Beyond 192 dates pass B
+ * sweeps each listed pixel from memory; its per-j screen constants, 32 (k + 1)
+ * bytes, sit in LDS up to the device's limit per block (160 KB on gfx950,
+ * k <= 5119) and are read from global memory beyond it.  The first call
  * with a new (k, n_looks, alpha, dtype) tabulates one pair of decision bounds
  * per sub-series length on the host (O(k^2) work, cached); their safety
  * margin grows with k (see omni_bounds) so that very long series stay exact.

@@ -2531,14 +2531,17 @@ struct OmniSearchArgs {
 // ones on top (the sweep of a long series is bound by them: 96 dates x 164 000 pixels 0.41 -> 0.2 ms).
 // Whatever it cannot decide (band, non-positive or non-finite determinants, a product outside the normal
 // doubles) takes the exact evaluation, as before.  The table covers tests over up to 192 dates.
+// GSCR: the double screen's constants read from s.tab in global memory instead of LDS -- MODE 1 only, for series
+// whose 32 (k + 1) bytes of constants exceed what the device grants a block (k > 5119 on 160 KB).
 constexpr int kScreenLong = 192;
 struct DenseScreenLong {
     DenseScreenEntry e[kScreenLong + 1];
 };
 
-template <typename T, int MODE, int PXW = 64, bool FS = false>
+template <typename T, int MODE, int PXW = 64, bool FS = false, bool GSCR = false>
 __global__ void __launch_bounds__(64) omnibus_c2_search_kernel(const OmniSearchArgs<T> s, const DenseScreenLong fscr)
 {
+    static_assert(!GSCR || (MODE == 1 && !FS), "the global-memory screen serves the double screen of MODE 1");
     constexpr bool USE_LDS = (MODE == 0);
     extern __shared__ __align__(16) unsigned char nd_smem[];
     T *lds = reinterpret_cast<T *>(nd_smem);
@@ -2555,7 +2558,7 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_kernel(const OmniSearchA
     if (FS) {
         for (int j = lane; j <= k; j += 64) scr_f[j] = fscr.e[j];
         __syncthreads();
-    } else {
+    } else if (!GSCR) {
         for (int j = lane; j <= k; j += 64) {
             const OmniTabEntry e = s.tab[j];
             scr[j] = e.m2rho;
@@ -2565,7 +2568,10 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_kernel(const OmniSearchA
         }
         __syncthreads();
     }
-    auto screen = [&](int f, int j) -> double { return scr[f * kp + j]; };
+    auto screen = [&](int f, int j) -> double {
+        if (GSCR) return f == 0 ? tabp[j].m2rho : (f == 1 ? tabp[j].pklogk : (f == 2 ? tabp[j].zlo_a : tabp[j].zhi_a));
+        return scr[f * kp + j];
+    };
     // blocks shard, shard + kShards, ... work through the list of one shard
     const unsigned shard = blockIdx.x % kShards;
     const unsigned lblock = blockIdx.x / kShards;
@@ -3796,10 +3802,29 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             return ND_AMD_OK;
         }
         const dim3 gx((unsigned)xblocks);
-        if (mode == 0 && use_lds)
+        if (mode == 0 && use_lds) {
             ND_LAUNCH_SWEEP(0, 64, gx, lds_bytes);
-        else
+            return ND_AMD_OK;
+        }
+        // MODE 1 stages only the screen constants, 32 (k + 1) bytes: up to 64 KB (k <= 2046) as they are, up to
+        // the device's limit per block (k <= 5119 on 160 KB) with the launch attribute raised; beyond that the
+        // sweep reads them from the table in global memory.  (fs implies k <= 192: a few KB.)
+        bool scr_lds = scr_bytes <= 64 * 1024;
+        if (!scr_lds) {
+            int dev = 0, lds_max = 0;
+            hipError_t e = hipGetDevice(&dev);
+            if (e == hipSuccess) e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+            if (e == hipSuccess && scr_bytes <= (size_t)lds_max) {
+                e = hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c2_search_kernel<T, 1, 64, false>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)scr_bytes);
+                scr_lds = (e == hipSuccess);
+            }
+            if (e != hipSuccess) (void)hipGetLastError();   // a refused attribute is no failure: the global form serves
+        }
+        if (scr_lds)
             ND_LAUNCH_SWEEP(1, 64, gx, scr_bytes);
+        else
+            hipLaunchKernelGGL((omnibus_c2_search_kernel<T, 1, 64, false, true>), gx, dim3(64), 0, sq, s, fscr);
 #undef ND_LAUNCH_SWEEP
         return ND_AMD_OK;
     };

@@ -15,7 +15,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 20261004
 # (sized for ~40 s in all: the suite runs under a 900 s limit.  The long campaign is tools/fuzz_parity.py,
 #  its result per round under profiles/ -- r06: 5 248 omnibus / c3 cases in 240 s, no difference)
-CASES_PER_FAMILY = {'omnibus': 250, 'omnibus_ml': 300, 'c3': 400, 'nlmeans': 2500, 'correlate': 5000, 'gaussian': 6000}
+# (omnibus_long: 193 - 4096 dates on rasters of at most 128 pixels, about 20 s)
+CASES_PER_FAMILY = {'omnibus': 250, 'omnibus_long': 80, 'omnibus_ml': 300, 'c3': 400, 'nlmeans': 2500, 'correlate': 5000,
+                    'gaussian': 6000}
 
 
 @pytest.fixture(scope='module')

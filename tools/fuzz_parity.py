@@ -2,7 +2,7 @@
 shapes, strides, parameters and corner values.  Not part of the pytest suite (run time is open
 ended); what it finds is either fixed with a regression case in tests/ or recorded in DESIGN.md 9.
 
-    python tools/fuzz_parity.py --seconds 120 --seed 1 [--what omnibus,nlmeans,correlate,gaussian,c3]
+    python tools/fuzz_parity.py --seconds 120 --seed 1 [--what omnibus,omnibus_long,nlmeans,correlate,gaussian,c3]
 
 Prints one line per failure (with the parameters needed to replay it) and a summary; exit code 1
 if anything differed."""
@@ -52,8 +52,16 @@ def case_omnibus(rng):
         bad = rng.random((k, ny, nx)) < 0.01
         val = rng.choice([0.0, np.nan, np.inf, -1.0])
         planes[int(rng.integers(0, 4))][bad] = val
+    desc = dict(k=k, ny=ny, nx=nx, looks=looks, dtype=np.dtype(dtype).name, alpha=alpha, n=n)
+    return omnibus_parity(rng, planes, alpha, n, desc)
+
+
+def omnibus_parity(rng, planes, alpha, n, desc):
+    """The planar (time, y, x) stack `planes` through the HIP path in a random layout (also the pixel-major
+    kernel), workspace and with or without the rasters, against the oracle."""
+    k, ny, nx = planes[0].shape
     layout = rng.choice(['tyx', 'yxt', 'pad', 'pm', 'pmc'])
-    desc = dict(k=k, ny=ny, nx=nx, looks=looks, dtype=np.dtype(dtype).name, alpha=alpha, n=n, layout=str(layout))
+    desc.update(layout=str(layout))
     with np.errstate(all='ignore'):
         want, zw, pw = O.change_detection_planes([np.moveaxis(p, 0, -1) for p in planes], alpha, n, njobs=8, stats=True)
     if layout in ('tyx', 'pm', 'pmc'):
@@ -92,6 +100,32 @@ def case_omnibus(rng):
             ok = (np.allclose(z, zw, rtol=1e-5, atol=0, equal_nan=True) and
                   np.allclose(P, pw, rtol=1e-5, atol=1e-7, equal_nan=True))
     return ok, desc
+
+
+def case_omnibus_long(rng):
+    """193 - 4096 dates (the per-pixel sweep of pass B, the per-j table in device memory, MODE 1's screen
+    constants past 64 KB of LDS) on small rasters of tests.synth.long_series_stack: running products of the
+    determinants kept in range, random step dates, planted subnormal / underflowing / overflowing pixels."""
+    from tests import synth
+    k = int(np.exp(rng.uniform(np.log(193), np.log(4097))))
+    ny, nx = int(rng.integers(1, 5)), int(rng.integers(1, 33))
+    if k > 2048:
+        nx = min(nx, 16)
+    dtype = rng.choice([np.float32, np.float64])
+    alpha = float(rng.choice([1e-4, 0.01, 0.2, 0.5, 0.9, 0.99, 0.9999]))
+    plant = bool(nx >= 2 * len(synth.PLANT) and rng.random() < 0.5)
+    planes, _ = synth.long_series_stack(int(rng.integers(1 << 30)), k, ny, nx, dtype=dtype,
+                                        change_frac=float(rng.uniform(0.2, 0.8)), plant=plant)
+    # whole-stack scales: mild ones, and ones that move every determinant far enough for the products to leave
+    # the double range within a few hundred dates
+    scale = float(rng.choice([1.0, 1.0, 1.0, 0.9, 1.1, 1e-3, 1e3]))
+    if scale != 1.0:
+        planes = [(p * scale).astype(dtype) for p in planes]
+    if rng.random() < 0.3:
+        bad = rng.random((k, ny, nx)) < 0.002
+        planes[int(rng.integers(0, 4))][bad] = rng.choice([0.0, np.nan, np.inf, -1.0])
+    desc = dict(k=k, ny=ny, nx=nx, dtype=np.dtype(dtype).name, alpha=alpha, n=9, plant=plant, scale=scale)
+    return omnibus_parity(rng, planes, alpha, 9, desc)
 
 
 def case_omnibus_ml(rng):
@@ -335,7 +369,7 @@ def case_gaussian(rng):
     return np.array_equal(got, want, equal_nan=True), desc
 
 
-CASES = {'omnibus': case_omnibus, 'omnibus_ml': case_omnibus_ml, 'c3': case_c3, 'nlmeans': case_nlmeans, 'correlate': case_correlate,
+CASES = {'omnibus': case_omnibus, 'omnibus_long': case_omnibus_long, 'omnibus_ml': case_omnibus_ml, 'c3': case_c3, 'nlmeans': case_nlmeans, 'correlate': case_correlate,
          'gaussian': case_gaussian}
 
 
