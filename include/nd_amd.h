@@ -66,6 +66,15 @@ extern "C" {
 #define ND_AMD_KERNEL_OMNIBUS_FUSED  10   /* pass A with the change-point search fused in */
 #define ND_AMD_KERNEL_OMNIBUS_SAMPLE 11   /* density sample that gates the fused form */
 #define ND_AMD_KERNEL_OMNIBUS_EXACT  12   /* pass B, exact form behind the register form (marked pixels only) */
+#define ND_AMD_KERNEL_COREG_SHIFTS   13   /* nd_amd_coregister_shifts, the whole call (FFTs included) */
+#define ND_AMD_KERNEL_COREG_WARP     14   /* nd_amd_warp_translate, the whole call */
+
+/* layouts of nd_amd_warp_translate */
+#define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
+#define ND_AMD_LAYOUT_PIXEL_MAJOR  1   /* (row, col, time), time fastest: the reference's (y, x, time) */
+
+#define ND_AMD_COREG_MAX_UPSAMPLING 128
+#define ND_AMD_COREG_MAX_VARS       16
 
 int nd_amd_abi_version(void);
 const char *nd_amd_last_error(void);
@@ -387,6 +396,66 @@ int nd_amd_split_complex(const void *in, void *out_re, void *out_im, int dtype, 
  * elements -> n interleaved complex values.  16-byte aligned pointers. */
 int nd_amd_merge_complex(const void *in_re, const void *in_im, void *out, int dtype, int64_t n,
                          void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Coregistration, step 1: the shift of every date against a reference date.
+ * Replaces  skimage.registration.phase_cross_correlation(C11[t], C11[reference],
+ *           upsample_factor=upsampling)[0]   (scikit-image 0.18; nd/warp.py:1150-1151)
+ * for every date t of one stack at once.
+ *
+ * c11 holds element (t, y, x) at c11[t * stride_t + y * stride_y + x * stride_x]
+ * (element strides; planar and (y, x, time) inputs are copied with the copy
+ * engine / nd_amd_relayout_planar, anything else gathered).  Output, device
+ * memory: shifts[2 t], shifts[2 t + 1] = (row, col) shift of date t, 0 for the
+ * reference date; status[t] = 1 where skimage raises ValueError("NaN values
+ * found ...") -- a NaN reached the correlation (a NaN in C11 of date t or of the
+ * reference) -- else 0.  Nothing is synchronised.
+ * Arithmetic: hipFFT in the input precision (R2C / C2R, plans cached per device,
+ * shape, batch and dtype; the first call of a shape builds them), whole-pixel
+ * peak = first maximum of |cc| in C order, then for upsampling > 1 the upsampled
+ * DFT of R = ceil(1.5 u) x R points around it in complex128.  Sums are ordered
+ * differently from numpy's, so a near-tie of two peak values may pick the other:
+ * one 1 / u step on such a date.
+ * Limits: 1 <= upsampling <= ND_AMD_COREG_MAX_UPSAMPLING, ny * nx < 2^31,
+ * k <= 65535.  workspace: >= nd_amd_coregister_shifts_workspace_bytes() bytes,
+ * 256-byte aligned (about 3 x the C11 stack plus 96 R (ny + nx) bytes per date);
+ * the query returns 0 for arguments the call refuses.
+ * ---------------------------------------------------------------------- */
+size_t nd_amd_coregister_shifts_workspace_bytes(int dtype, int64_t k, int64_t ny, int64_t nx,
+                                                int upsampling);
+
+int nd_amd_coregister_shifts(const void *c11, int dtype, int64_t k, int64_t ny, int64_t nx,
+                             int64_t stride_t, int64_t stride_y, int64_t stride_x,
+                             int64_t reference, int upsampling,
+                             double *shifts, int32_t *status,
+                             void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Coregistration, step 2: translate every plane of `nvars` variables by its
+ * date's shift.  Replaces, for every date t != reference and variable v,
+ *   skimage.transform.warp(v[t], AffineTransform(translation=(shifts[2 t + 1],
+ *                          shifts[2 t])), order=3)            (nd/warp.py:1152-1159)
+ * out[r, c] = the Catmull-Rom bicubic of the plane at (r + s_row, c + s_col),
+ * taps outside the plane 0 (mode 'constant', cval 0), the sample coordinates
+ * formed in the data type (as skimage forms them), then clipped to the plane's
+ * own [min, max]; when 0 lies outside that range, outputs exactly 0 stay 0.  A
+ * NaN in a plane makes its min / max NaN and so every output of that plane NaN
+ * except those exact zeros (reference behaviour).  The reference date (-1:
+ * none) is copied unchanged.  in[v], out[v]: device pointers, each variable
+ * contiguous in `layout` (ND_AMD_LAYOUT_PLANAR: (k, nr, nc); _PIXEL_MAJOR:
+ * (nr, nc, k)), all of dtype `dtype`; outputs are new memory (the call refuses
+ * out[v] == in[v] and never writes an input).  shifts: device, k x 2 doubles
+ * (nd_amd_coregister_shifts' output).  nvars <= ND_AMD_COREG_MAX_VARS,
+ * nvars * k <= 65535.  workspace: >= nd_amd_warp_translate_workspace_bytes(),
+ * 256-byte aligned (per-date coordinate tables and per-plane min / max).
+ * ---------------------------------------------------------------------- */
+size_t nd_amd_warp_translate_workspace_bytes(int dtype, int nvars, int64_t k, int64_t nr, int64_t nc,
+                                             int layout);
+
+int nd_amd_warp_translate(const void *const *in, void *const *out, int nvars, int dtype,
+                          int64_t k, int64_t nr, int64_t nc, int layout,
+                          const double *shifts, int64_t reference,
+                          void *workspace, size_t workspace_bytes, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,9 @@ MODES = {'reflect': 0, 'constant': 1, 'nearest': 2, 'mirror': 3, 'wrap': 4,
          'grid-constant': 1, 'grid-mirror': 0, 'grid-wrap': 4}
 KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 4: 'nlmeans', 5: 'boxcar_tiled', 6: 'nlmeans_tiled', 7: 'correlate1d',
-                8: 'relayout', 9: 'omnibus_c2_dense', 10: 'omnibus_c2_fused', 11: 'omnibus_c2_sample', 12: 'omnibus_c2_exact'}
+                8: 'relayout', 9: 'omnibus_c2_dense', 10: 'omnibus_c2_fused', 11: 'omnibus_c2_sample', 12: 'omnibus_c2_exact',
+                13: 'coregister_shifts', 14: 'warp_translate'}
+LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 
 # every symbol include/nd_amd.h declares
 SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
@@ -29,7 +31,9 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_relayout_planar', 'nd_amd_relayout_planar_complex',
            'nd_amd_relayout_pixel_major', 'nd_amd_split_complex', 'nd_amd_merge_complex',
            'nd_amd_timing_enable', 'nd_amd_timing_collect', 'nd_amd_timing_dropped',
-           'nd_amd_timing_select')
+           'nd_amd_timing_select',
+           'nd_amd_coregister_shifts_workspace_bytes', 'nd_amd_coregister_shifts',
+           'nd_amd_warp_translate_workspace_bytes', 'nd_amd_warp_translate')
 
 _lib = None
 
@@ -112,6 +116,15 @@ def lib():
     L.nd_amd_timing_dropped.argtypes = []
     L.nd_amd_timing_select.restype = i32
     L.nd_amd_timing_select.argtypes = [C.c_uint64]
+    L.nd_amd_coregister_shifts_workspace_bytes.restype = C.c_size_t
+    L.nd_amd_coregister_shifts_workspace_bytes.argtypes = [i32, i64, i64, i64, i32]
+    L.nd_amd_coregister_shifts.restype = i32
+    L.nd_amd_coregister_shifts.argtypes = [vp, i32] + [i64] * 7 + [i32, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_warp_translate_workspace_bytes.restype = C.c_size_t
+    L.nd_amd_warp_translate_workspace_bytes.argtypes = [i32, i32, i64, i64, i64, i32]
+    L.nd_amd_warp_translate.restype = i32
+    L.nd_amd_warp_translate.argtypes = ([C.POINTER(vp), C.POINTER(vp), i32, i32] + [i64] * 3
+                                        + [i32, vp, i64, vp, C.c_size_t, vp])
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

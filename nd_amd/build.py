@@ -164,7 +164,9 @@ def _build(force, verbose, extra_flags, LIB, OBJ):
             check_no_scratch(objp + '.remarks', sym, objp)
     linked = False
     if rebuilt or not os.path.exists(LIB):
-        cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB] + objs
+        # hipFFT: the FFTs of Coregistration (coregister.hip) run inside the library, so the C ABI
+        # needs no torch
+        cmd = [HIPCC, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB] + objs + ['-lhipfft']
         if verbose:
             print(' '.join(cmd))
         subprocess.check_call(cmd)

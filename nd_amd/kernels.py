@@ -720,3 +720,93 @@ def pixelwise_nlmeans_3d(arr, output, r, f, sigma, h, n_eff=-1, patch_mode=0,
         if not deferred:
             raise_if_no_solution(status)
     return output
+
+
+# ---------------------------------------------------------------------------
+# Coregistration (nd/warp.py:1104-1163)
+# ---------------------------------------------------------------------------
+def coregister_shifts(c11, reference=0, upsampling=10, dims=('time', 'y', 'x')):
+    """Shift of every date of the C11 stack against date `reference`, as
+    skimage.registration.phase_cross_correlation(C11[t], C11[reference], upsample_factor=upsampling)
+    (scikit-image 0.18) computes it: (row, col) in the order the two spatial axes of `dims` are stored.
+    Returns device tensors (shifts float64 (k, 2), status int32 (k,)); status[t] = 1 where skimage
+    raises ValueError (a NaN reached the correlation).  Nothing is synchronised."""
+    _require_cuda(c11, 'c11')
+    dims = tuple(dims)
+    if c11.dim() != 3 or sorted(dims) != ['time', 'x', 'y']:
+        raise ValueError("c11 must be 3-D with dims a permutation of ('time', 'y', 'x')")
+    at = dims.index('time')
+    ar, ac = [i for i in range(3) if i != at]
+    k, nr, nc = c11.shape[at], c11.shape[ar], c11.shape[ac]
+    ref = int(reference)
+    if not 0 <= ref < k:
+        raise IndexError('reference %d is out of bounds for %d dates' % (ref, k))
+    dev = c11.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        shifts = torch.zeros((k, 2), dtype=torch.float64, device=dev)
+        status = torch.zeros(k, dtype=torch.int32, device=dev)
+        if k * nr * nc == 0:
+            return shifts, status
+        nbytes = L.nd_amd_coregister_shifts_workspace_bytes(_DT[c11.dtype], k, nr, nc, int(upsampling))
+        if nbytes == 0:
+            raise ValueError('coregister_shifts: unsupported shape %s or upsampling %r (1 .. 128)'
+                             % (tuple(c11.shape), upsampling))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.nd_amd_coregister_shifts(
+            _ptr(c11), _DT[c11.dtype], k, nr, nc, c11.stride(at), c11.stride(ar), c11.stride(ac), ref,
+            int(upsampling), _ptr(shifts), _ptr(status), _ptr(ws), nbytes, _stream_ptr(dev)))
+        ws.record_stream(torch.cuda.current_stream(dev))
+    return shifts, status
+
+
+def warp_translate(planes, shifts, reference=-1, layout='planar'):
+    """Translate every date of each variable by its row of `shifts` (device float64 (k, 2)), as
+    skimage.transform.warp(v[t], AffineTransform(translation=(s[t, 1], s[t, 0])), order=3) does
+    (constant 0 outside, clipped to the plane's input range).  planes: device tensors of one dtype
+    and shape, (k, rows, cols) for layout 'planar', (rows, cols, k) for 'pixel_major'; the date
+    `reference` (-1: none) is copied.  Returns new tensors; the inputs are never written."""
+    planes = list(planes)
+    if not planes:
+        return []
+    p0 = planes[0]
+    for i, t in enumerate(planes):
+        _require_cuda(t, 'planes[%d]' % i)
+        if t.shape != p0.shape or t.dtype != p0.dtype or t.device != p0.device or t.dim() != 3:
+            raise ValueError('the planes must be 3-D and share shape, dtype and device')
+    if layout == 'planar':
+        k, nr, nc = p0.shape
+        lay = _lib.LAYOUT_PLANAR
+    elif layout == 'pixel_major':
+        nr, nc, k = p0.shape
+        lay = _lib.LAYOUT_PIXEL_MAJOR
+    else:
+        raise ValueError("layout must be 'planar' or 'pixel_major'")
+    if not (torch.is_tensor(shifts) and shifts.is_cuda and shifts.dtype == torch.float64
+            and tuple(shifts.shape) == (k, 2)):
+        raise ValueError('shifts must be a float64 device tensor of shape (%d, 2)' % k)
+    dev = p0.device
+    L = _lib.lib()
+    outs = []
+    with torch.cuda.device(dev):
+        shifts = shifts.to(dev).contiguous()
+        ins = [t.contiguous() for t in planes]
+        outs = [torch.empty_like(t) for t in ins]
+        if k * nr * nc == 0:
+            return outs
+        maxv = 16
+        for g in range(0, len(ins), maxv):
+            gi, go = ins[g:g + maxv], outs[g:g + maxv]
+            nbytes = L.nd_amd_warp_translate_workspace_bytes(_DT[p0.dtype], len(gi), k, nr, nc, lay)
+            if nbytes == 0:
+                raise ValueError('warp_translate: unsupported shape %s' % (tuple(p0.shape),))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            pin = (C.c_void_p * len(gi))(*[t.data_ptr() for t in gi])
+            pout = (C.c_void_p * len(go))(*[t.data_ptr() for t in go])
+            _lib.check(L.nd_amd_warp_translate(pin, pout, len(gi), _DT[p0.dtype], k, nr, nc, lay,
+                                               _ptr(shifts), int(reference), _ptr(ws), nbytes,
+                                               _stream_ptr(dev)))
+            ws.record_stream(torch.cuda.current_stream(dev))
+        for t in ins:
+            t.record_stream(torch.cuda.current_stream(dev))
+    return outs
