@@ -68,6 +68,8 @@ extern "C" {
 #define ND_AMD_KERNEL_OMNIBUS_EXACT  12   /* pass B, exact form behind the register form (marked pixels only) */
 #define ND_AMD_KERNEL_COREG_SHIFTS   13   /* nd_amd_coregister_shifts, the whole call (FFTs included) */
 #define ND_AMD_KERNEL_COREG_WARP     14   /* nd_amd_warp_translate, the whole call */
+#define ND_AMD_KERNEL_RGB_LIMITS     15   /* nd_amd_rgb_limits, the whole call (every selection pass) */
+#define ND_AMD_KERNEL_RGB_COMPOSE    16   /* nd_amd_rgb_compose */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -456,6 +458,67 @@ int nd_amd_warp_translate(const void *const *in, void *const *out, int nvars, in
                           int64_t k, int64_t nr, int64_t nc, int layout,
                           const double *shifts, int64_t reference,
                           void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * RGB composites, step 1: the stretch limits of every channel plane.
+ * Replaces  np.nanpercentile(channel, pmin), np.nanpercentile(channel, pmax)
+ * (nd/visualize.py:184, 188) for nframes x nchan planes at once, as numpy 2.2.6
+ * computes them for data of type T = dtype.
+ *
+ * A batch is nframes frames of nchan (1 or 3) channels.  num[c] / den[c]: host
+ * arrays of nchan device pointers; channel c of frame f holds element (y, x) at
+ *   num[c][f * stride_frame + y * stride_y + x * stride_x]
+ * divided (IEEE division in T, never stored) by the same element of den[c] where
+ * den is not NULL and den[c] is not NULL.  The strides are in elements, shared by
+ * every plane and not negative: (time, y, x) variables have stride_x = 1,
+ * (y, x, time) variables stride_frame = 1.  Contiguous planes whose pointers and
+ * frame stride are multiples of 16 bytes are read with 16-byte loads.
+ *
+ * Output, device memory: limits[2 p], limits[2 p + 1] (type T) for plane
+ * p = f * nchan + c, counts[p] = its number of non-NaN values n.  Definition:
+ * NaNs are dropped and n == 0 gives NaN; infinities are ordinary values;
+ * q = T(p) / T(100), vi = T(n - 1) * q, lo = floor(vi), hi = min(lo + 1, n - 1)
+ * (both n - 1 where vi >= T(n - 1)), g = vi - lo; with A, B the values of rank
+ * lo, hi and d = B - A the result is A + d * g, or B - d * (1 - g) where
+ * g >= 0.5: every operation rounded to T, none fused.  For float32 planes of more
+ * than 2^24 values the index is therefore as coarse as numpy's.
+ * The selection is exact (digit histograms of order-preserving keys: 3 reads of
+ * the planes for float32, 6 for float64).  Nothing is synchronised.
+ * Limits: 0 <= pmin, pmax <= 100, ny * nx <= 2^31, nframes * nchan <= 65535.
+ * workspace: >= nd_amd_rgb_limits_workspace_bytes(dtype, nframes * nchan) bytes,
+ * 256-byte aligned (96 KiB per float32 plane, 192 KiB per float64 plane); the
+ * query returns 0 for arguments the call refuses.
+ * ---------------------------------------------------------------------- */
+size_t nd_amd_rgb_limits_workspace_bytes(int dtype, int64_t nplanes);
+
+int nd_amd_rgb_limits(const void *const *num, const void *const *den, int nchan, int dtype,
+                      int64_t nframes, int64_t ny, int64_t nx,
+                      int64_t stride_frame, int64_t stride_y, int64_t stride_x,
+                      double pmin, double pmax, void *limits, int64_t *counts,
+                      void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * RGB composites, step 2: the 8-bit image.  Replaces, per channel c of frame f
+ * (nd/visualize.py:189-193, 206 without the cv2 calls),
+ *   if maxval > minval: channel = (channel - minval) / (maxval - minval) * 255
+ *   np.clip(channel as float64, 0, 255).astype(np.uint8);  pixels outside mask = 0
+ * Planes as for nd_amd_rgb_limits.  minval / maxval of plane p = f * nchan + c:
+ * vmin[c] / vmax[c] (host arrays of nchan doubles, the Python numbers a caller
+ * passed) where the array is not NULL, else limits[2 p] / limits[2 p + 1] (device,
+ * type T, as nd_amd_rgb_limits wrote them; may be NULL when both arrays are
+ * given).  Arithmetic in T as numpy does it: two given numbers are compared and
+ * subtracted in double and the span rounded to T; a given number beside a
+ * percentile is rounded to T first.  NaN limits, or maxval <= minval, leave the
+ * channel unscaled.  NaN and values below 0 give 0, values above 255 give 255,
+ * the rest is truncated.  mask: NULL or ny * nx bytes (device), 0 = black.
+ * out: device, (nframes, ny, nx, 3) uint8, 4-byte aligned; one channel is
+ * replicated into the three bytes.  Nothing is synchronised.
+ * ---------------------------------------------------------------------- */
+int nd_amd_rgb_compose(const void *const *num, const void *const *den, int nchan, int dtype,
+                       int64_t nframes, int64_t ny, int64_t nx,
+                       int64_t stride_frame, int64_t stride_y, int64_t stride_x,
+                       const void *limits, const double *vmin, const double *vmax,
+                       const uint8_t *mask, uint8_t *out, void *hip_stream);
 
 #ifdef __cplusplus
 }

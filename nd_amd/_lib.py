@@ -18,7 +18,7 @@ MODES = {'reflect': 0, 'constant': 1, 'nearest': 2, 'mirror': 3, 'wrap': 4,
 KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 4: 'nlmeans', 5: 'boxcar_tiled', 6: 'nlmeans_tiled', 7: 'correlate1d',
                 8: 'relayout', 9: 'omnibus_c2_dense', 10: 'omnibus_c2_fused', 11: 'omnibus_c2_sample', 12: 'omnibus_c2_exact',
-                13: 'coregister_shifts', 14: 'warp_translate'}
+                13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 
 # every symbol include/nd_amd.h declares
@@ -33,7 +33,8 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_timing_enable', 'nd_amd_timing_collect', 'nd_amd_timing_dropped',
            'nd_amd_timing_select',
            'nd_amd_coregister_shifts_workspace_bytes', 'nd_amd_coregister_shifts',
-           'nd_amd_warp_translate_workspace_bytes', 'nd_amd_warp_translate')
+           'nd_amd_warp_translate_workspace_bytes', 'nd_amd_warp_translate',
+           'nd_amd_rgb_limits_workspace_bytes', 'nd_amd_rgb_limits', 'nd_amd_rgb_compose')
 
 _lib = None
 
@@ -125,6 +126,14 @@ def lib():
     L.nd_amd_warp_translate.restype = i32
     L.nd_amd_warp_translate.argtypes = ([C.POINTER(vp), C.POINTER(vp), i32, i32] + [i64] * 3
                                         + [i32, vp, i64, vp, C.c_size_t, vp])
+    L.nd_amd_rgb_limits_workspace_bytes.restype = C.c_size_t
+    L.nd_amd_rgb_limits_workspace_bytes.argtypes = [i32, i64]
+    L.nd_amd_rgb_limits.restype = i32
+    L.nd_amd_rgb_limits.argtypes = ([C.POINTER(vp), C.POINTER(vp), i32, i32] + [i64] * 6 + [dbl, dbl]
+                                    + [vp, vp, vp, C.c_size_t, vp])
+    L.nd_amd_rgb_compose.restype = i32
+    L.nd_amd_rgb_compose.argtypes = ([C.POINTER(vp), C.POINTER(vp), i32, i32] + [i64] * 6
+                                     + [vp, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp])
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

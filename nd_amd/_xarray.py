@@ -1,7 +1,7 @@
 """
 nd_amd/_xarray.py -- optional xarray accessors mirroring nd/_xarray.py:135-161 for the algorithms
 this package provides: `ds.nd_amd.change_omnibus(...)`, `ds.nd_amd.nlmeans(...)`,
-`ds.nd_amd.boxcar(...)`, `ds.nd_amd.convolve(...)`, `ds.nd_amd.gaussian(...)`.
+`ds.nd_amd.boxcar(...)`, `ds.nd_amd.convolve(...)`, `ds.nd_amd.gaussian(...)`, `ds.nd_amd.to_rgb(...)`.
 
 Registered only when xarray is importable (it is not installed in the build or GPU images); the
 accessor name differs from the reference's (`nd`, `filter`) so both can be loaded side by side.
@@ -30,6 +30,21 @@ def _forward(target):
     return method
 
 
+def _to_rgb(accessor, rgb=None, *args, **kwargs):
+    """nd/_xarray.py:98-115: a DataArray is one grey channel; a Dataset goes through `rgb`, a callable
+    returning the R, G, B channels (default [C11, C22, C11 / C22]).  See nd_amd.visualize.to_rgb."""
+    from . import visualize
+    obj = accessor._obj
+    if isinstance(obj, xr.DataArray) and rgb is None:
+        data = obj
+    else:
+        if rgb is None:
+            def rgb(d):
+                return [d.C11, d.C22, d.C11 / d.C22]
+        data = rgb(obj)
+    return visualize.to_rgb(data, *args, **kwargs)
+
+
 def register():
     """Attach the `nd_amd` accessor to xarray Datasets and DataArrays; False without xarray."""
     if xr is None:
@@ -39,6 +54,7 @@ def register():
     namespace = {'__init__': lambda accessor, obj: setattr(accessor, '_obj', obj)}
     for name, (module, function) in _METHODS.items():
         namespace[name] = _forward(getattr(modules[module], function))
+    namespace['to_rgb'] = _to_rgb
     accessor = type('NdAmdAccessor', (), namespace)
     xr.register_dataset_accessor('nd_amd')(accessor)
     xr.register_dataarray_accessor('nd_amd')(accessor)

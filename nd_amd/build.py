@@ -49,7 +49,8 @@ PER_FILE = {'nlmeans.hip': ['-fno-slp-vectorize'] + os.environ.get('ND_AMD_NLM_F
 # compiler's own resource report (-Rpass-analysis=kernel-resource-usage) and warns (fails under
 # ND_AMD_STRICT_SCRATCH=1) if an instantiation exceeds its budget: none for the sparse form (pass A of the benchmark regime), what the fused-search
 # and statistics forms are known to spill in their tails (bytes per lane) otherwise.
-NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel'}
+# rgb.hip: the histogram passes and the composite are streaming kernels; none of its kernels may spill
+NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_'}
 # bytes per lane by the kernel's template arguments <K, KMAX, STATS, CHAIN>, keyed (STATS, CHAIN)
 SCRATCH_BUDGET = {(False, False): 0, (False, True): 96, (True, False): 256, (True, True): 384}
 

@@ -810,3 +810,119 @@ def warp_translate(planes, shifts, reference=-1, layout='planar'):
         for t in ins:
             t.record_stream(torch.cuda.current_stream(dev))
     return outs
+
+
+# ---------------------------------------------------------------------------
+# RGB composites (nd/visualize.py:176-193)
+# ---------------------------------------------------------------------------
+def _rgb_strides(t):
+    """element strides (frame, y, x) of a (frames, y, x) view; the stride of a dimension of size 1 is
+    arbitrary in torch and is replaced by the contiguous one, which keeps single planes on the fast path"""
+    (k, ny, nx), (st, sy, sx) = t.shape, t.stride()
+    if nx == 1:
+        sx = 1
+    if ny == 1:
+        sy = nx * sx
+    if k == 1:
+        st = ny * sy
+    return st, sy, sx
+
+
+def _rgb_planes(channels, name):
+    """channels: one or three entries, each a (frames, y, x) device view or a (numerator, denominator)
+    pair of such views (the channel is their quotient, never stored).  All views share shape, dtype,
+    device and strides (any non-negative strides: a (y, x, time) variable is passed as
+    v.permute(2, 0, 1)).  -> (num tensors, den tensors or None, ctypes pointer arrays)."""
+    channels = list(channels)
+    if len(channels) not in (1, 3):
+        raise ValueError('%s: a frame has 1 or 3 channels, got %d' % (name, len(channels)))
+    num, den = [], []
+    for ch in channels:
+        n, d = ch if isinstance(ch, (tuple, list)) else (ch, None)
+        num.append(n)
+        den.append(d)
+    first = num[0]
+    for i, t in enumerate(num + [d for d in den if d is not None]):
+        _require_cuda(t, '%s: channel %d' % (name, i % len(num)))
+        if (t.dim() != 3 or t.shape != first.shape or t.dtype != first.dtype or t.device != first.device
+                or _rgb_strides(t) != _rgb_strides(first)):
+            raise ValueError('%s: the planes must be (frames, y, x) views that share shape, dtype, device '
+                             'and strides' % name)
+    pn = (C.c_void_p * len(num))(*[t.data_ptr() for t in num])
+    pd = (C.c_void_p * len(num))(*[(d.data_ptr() if d is not None else None) for d in den])
+    return num, den, pn, pd
+
+
+def rgb_limits(channels, pmin=2, pmax=98):
+    """np.nanpercentile(channel, pmin) and (channel, pmax) of every channel plane of every frame, as numpy
+    2.2.6 computes them in the data type (exact selection, include/nd_amd.h).  `channels` as in
+    _rgb_planes.  Returns device tensors: limits (frames, channels, 2) of the data type and the number of
+    non-NaN values per plane, int64 (frames, channels).  Nothing is synchronised."""
+    num, den, pn, pd = _rgb_planes(channels, 'rgb_limits')
+    t0 = num[0]
+    k, ny, nx = t0.shape
+    nch = len(num)
+    if not (0 <= float(pmin) <= 100 and 0 <= float(pmax) <= 100):
+        raise ValueError('Percentiles must be in the range [0, 100]')
+    dev = t0.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        limits = torch.empty((k, nch, 2), dtype=t0.dtype, device=dev)
+        counts = torch.zeros((k, nch), dtype=torch.int64, device=dev)
+        if k == 0:
+            return limits, counts
+        nbytes = L.nd_amd_rgb_limits_workspace_bytes(_DT[t0.dtype], k * nch)
+        if nbytes == 0:
+            raise ValueError('rgb_limits: unsupported batch of %d planes' % (k * nch))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        st, sy, sx = _rgb_strides(t0)
+        _lib.check(L.nd_amd_rgb_limits(pn, pd, nch, _DT[t0.dtype], k, ny, nx, st, sy, sx, float(pmin),
+                                       float(pmax), _ptr(limits), _ptr(counts), _ptr(ws), nbytes,
+                                       _stream_ptr(dev)))
+        stream = torch.cuda.current_stream(dev)
+        for t in [ws] + num + [d for d in den if d is not None]:
+            t.record_stream(stream)
+    return limits, counts
+
+
+def rgb_compose(channels, limits=None, vmin=None, vmax=None, mask=None):
+    """The 8-bit composite of every frame: (frames, y, x, 3) uint8 on the device.  Per channel
+    minval / maxval are vmin[c] / vmax[c] (sequences of Python numbers, one per channel) where given,
+    else limits[frame, c] (rgb_limits' output); channels with maxval > minval are stretched to 0 .. 255 in
+    the data type, NaN gives 0.  mask: bool or uint8 (y, x) device tensor, pixels where it is 0 are
+    black.  One channel is replicated into the three bytes."""
+    num, den, pn, pd = _rgb_planes(channels, 'rgb_compose')
+    t0 = num[0]
+    k, ny, nx = t0.shape
+    nch = len(num)
+    dev = t0.device
+    for v, nm in ((vmin, 'vmin'), (vmax, 'vmax')):
+        if v is not None and len(v) != nch:
+            raise ValueError('rgb_compose: %s needs one value per channel' % nm)
+    if limits is None and (vmin is None or vmax is None):
+        raise ValueError('rgb_compose: without limits both vmin and vmax must be given')
+    if limits is not None:
+        if not (torch.is_tensor(limits) and limits.device == dev and limits.dtype == t0.dtype
+                and tuple(limits.shape) == (k, nch, 2)):
+            raise ValueError('rgb_compose: limits must be a %s device tensor of shape (%d, %d, 2)'
+                             % (t0.dtype, k, nch))
+        limits = limits.contiguous()
+    if mask is not None:
+        if not (torch.is_tensor(mask) and mask.device == dev and tuple(mask.shape) == (ny, nx)
+                and mask.dtype in (torch.bool, torch.uint8)):
+            raise ValueError('rgb_compose: mask must be a bool or uint8 device tensor of shape (%d, %d)'
+                             % (ny, nx))
+        mask = mask.contiguous()
+    dbl = C.c_double * nch
+    pmin_ = dbl(*[float(v) for v in vmin]) if vmin is not None else None
+    pmax_ = dbl(*[float(v) for v in vmax]) if vmax is not None else None
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        out = torch.empty((k, ny, nx, 3), dtype=torch.uint8, device=dev)
+        st, sy, sx = _rgb_strides(t0)
+        _lib.check(L.nd_amd_rgb_compose(pn, pd, nch, _DT[t0.dtype], k, ny, nx, st, sy, sx, _ptr(limits),
+                                        pmin_, pmax_, _ptr(mask), _ptr(out), _stream_ptr(dev)))
+        stream = torch.cuda.current_stream(dev)
+        for t in num + [d for d in den if d is not None] + [x for x in (limits, mask) if x is not None]:
+            t.record_stream(stream)
+    return out
