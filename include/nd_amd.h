@@ -70,10 +70,18 @@ extern "C" {
 #define ND_AMD_KERNEL_COREG_WARP     14   /* nd_amd_warp_translate, the whole call */
 #define ND_AMD_KERNEL_RGB_LIMITS     15   /* nd_amd_rgb_limits, the whole call (every selection pass) */
 #define ND_AMD_KERNEL_RGB_COMPOSE    16   /* nd_amd_rgb_compose */
+#define ND_AMD_KERNEL_CLASSIFY_FOREST 17  /* nd_amd_classify_forest */
+#define ND_AMD_KERNEL_CLASSIFY_KMEANS 18  /* nd_amd_classify_kmeans */
+#define ND_AMD_KERNEL_CLASSIFY_GATHER 19  /* nd_amd_classify_select (mask + scan) and nd_amd_classify_gather */
+#define ND_AMD_KERNEL_CLASS_MEAN      20  /* nd_amd_class_stats and nd_amd_class_fill */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
 #define ND_AMD_LAYOUT_PIXEL_MAJOR  1   /* (row, col, time), time fastest: the reference's (y, x, time) */
+
+/* rows per block of nd_amd_classify_select / _gather: block_offsets has one entry per that many rows */
+#define ND_AMD_CLASSIFY_BLOCK_ROWS 1024
+#define ND_AMD_CLASSIFY_MAX_FEATURES 1024
 
 #define ND_AMD_COREG_MAX_UPSAMPLING 128
 #define ND_AMD_COREG_MAX_VARS       16
@@ -519,6 +527,118 @@ int nd_amd_rgb_compose(const void *const *num, const void *const *den, int nchan
                        int64_t stride_frame, int64_t stride_y, int64_t stride_x,
                        const void *limits, const double *vmin, const double *vmax,
                        const uint8_t *mask, uint8_t *out, void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Pixel classification (nd/classify.py).  Common to the four nd_amd_classify_*
+ * entries: the FEATURE TABLE.  The reference stacks every variable into a host
+ * matrix X of (rows, nfeat) (_build_X, nd/classify.py:47-59); here X is never
+ * formed.  feat: host array of nfeat (1 .. ND_AMD_CLASSIFY_MAX_FEATURES) device
+ * pointers of type T = dtype; sizes[4] / strides[4]: host arrays, the row
+ * dimensions (pad with size 1) and their element strides, shared by every
+ * feature and not negative.  Row r, counted row-major over sizes, has
+ *   X[r, f] = feat[f][i0 * strides[0] + i1 * strides[1] + i2 * strides[2] + i3 * strides[3]].
+ * A variable with a feature dimension contributes one pointer per position along
+ * it.  Neighbouring dimensions that are contiguous are merged inside the call, so
+ * the usual stacks cost no index arithmetic; lanes run along the row index.
+ * workspace: >= nd_amd_classify_workspace_bytes(nfeat) device bytes, 256-byte
+ * aligned (the pointer table; the query returns 0 for an nfeat the calls refuse).
+ * The table is copied with hipMemcpyAsync from `feat`, which may be reused when
+ * the call returns.  At most 2^40 rows.  Nothing is synchronised.
+ *
+ * Optional scaler, mean / scale: device, nfeat doubles each, both or neither.
+ * Replaces StandardScaler.transform (nd/classify.py:230) as numpy evaluates it in
+ * place on X of type T:  x = T(double(x) - mean[f]);  x = T(double(x) / scale[f]).
+ * ---------------------------------------------------------------------- */
+size_t nd_amd_classify_workspace_bytes(int nfeat);
+
+/* ------------------------------------------------------------------------
+ * Decision forest.  Replaces  clf.predict(X) / clf.predict_proba(X)  and the mask
+ * and scatter around it (nd/classify.py:222-241) for scikit-learn's
+ * DecisionTreeClassifier, ExtraTreeClassifier, RandomForestClassifier and
+ * ExtraTreesClassifier with one output, bit for bit with scikit-learn 1.7.2 at
+ * n_jobs = 1.
+ *
+ * nodes: device, nnodes x 16 bytes {float t32, int32 feature, int32 left, int32 right},
+ * 16-byte aligned, node indices absolute.  feature < 0 marks a leaf, whose `left`
+ * is its row in values.  values: device, (.., nclasses) doubles, the leaf
+ * distributions (tree_.value[node, 0, :]).  roots: device, ntrees int32, in
+ * estimator order.  classes: device, nclasses doubles (classes_).
+ * scikit-learn casts X to float32 and goes left where float32 x <= float64
+ * threshold; for a float32 x that is x <= t32 with t32 the largest float32 not
+ * above the threshold, which is what a node stores.  Per row: x_f = float32 of the
+ * (scaled) feature, rounded to nearest; for every tree in order walk to a leaf and
+ * add its distribution, one float64 add per class; p_c = sum_c / ntrees;
+ * labels[r] = classes[first c with the largest p_c].  A row with a NaN feature
+ * gives NaN in labels and in every p_c.
+ * labels: device, rows doubles, or NULL.  proba: device, (rows, nclasses)
+ * doubles, or NULL.  Not both NULL.  The caller guarantees that child and value
+ * indices lie inside the arrays and node features below nfeat.
+ * ---------------------------------------------------------------------- */
+int nd_amd_classify_forest(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                           const int64_t *strides, const void *nodes, int64_t nnodes,
+                           const double *values, const int32_t *roots, int ntrees,
+                           const double *classes, int nclasses, const double *mean, const double *scale,
+                           double *labels, double *proba, void *workspace, size_t workspace_bytes,
+                           void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * K-means.  Replaces  KMeans / MiniBatchKMeans .predict(X)  (nd/classify.py:232):
+ * centers: device, (k, nfeat) doubles.  d_j = sum over f, in feature order and in
+ * float64, of (double(x_f) - centers[j, f])^2 with x_f the (scaled) feature in
+ * type T; labels[r] = the first j with the smallest d_j, NaN for a row with a NaN
+ * feature.  labels: device, rows doubles.
+ * ---------------------------------------------------------------------- */
+int nd_amd_classify_kmeans(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                           const int64_t *strides, const double *centers, int k, const double *mean,
+                           const double *scale, double *labels, void *workspace, size_t workspace_bytes,
+                           void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Training rows.  Replaces the masks and boolean indexing of make_Xy
+ * (nd/classify.py:164-178):  ymask = ~isnan(labels) & (labels > 0),
+ * Xmask = ~isnan(X).any(axis=1),  X = X[ymask][Xmask],  y = labels[ymask][Xmask].
+ * labels: device doubles read at the row's offset under label_strides[4] (0 along
+ * a dimension the labels are broadcast over), or NULL for an unsupervised fit
+ * (then only Xmask applies).
+ * nd_amd_classify_select writes mask[r] (rows bytes, 1 = kept), block_offsets[b] =
+ * the number of kept rows before row b * ND_AMD_CLASSIFY_BLOCK_ROWS (one int64 per
+ * block of rows, rounded up) and *count = the number of kept rows (device).
+ * nd_amd_classify_gather, given the same arguments and those two arrays, writes
+ * the kept rows in row order -- the order scikit-learn's fit depends on -- into
+ * X (device, (count, nfeat) of type T, unscaled) and, where y is not NULL, their
+ * labels into y (device, count doubles).  Both are deterministic.
+ * ---------------------------------------------------------------------- */
+int nd_amd_classify_select(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                           const int64_t *strides, const double *labels, const int64_t *label_strides,
+                           uint8_t *mask, int64_t *block_offsets, int64_t *count, void *workspace,
+                           size_t workspace_bytes, void *hip_stream);
+
+int nd_amd_classify_gather(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                           const int64_t *strides, const double *labels, const int64_t *label_strides,
+                           const uint8_t *mask, const int64_t *block_offsets, void *X, double *y,
+                           void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * class_mean (nd/classify.py:36-44), the two device passes around a closed form
+ * the caller evaluates on the host.  var: device, one variable of type T over
+ * sizes[4] / strides[4] (any order of its dimensions; pass them by decreasing
+ * stride for coalesced reads); labels as above.  The class of an element is l
+ * where its label equals an integer l in 0 .. nclasses-1, else none.
+ * nd_amd_class_stats: sum[l] (float64 sum of the non-NaN values of class l),
+ * count[l] (how many) and nan_count[l] (NaN values of class l); device arrays of
+ * nclasses entries, zeroed by the call.  Sums are combined with float64 atomics:
+ * the last bits may differ from run to run.
+ * nd_amd_class_fill: out[e] = fill[l] for an element of class l; for an element
+ * of no class its own value, or fill[nclasses] where that is NaN.  fill: device,
+ * nclasses + 1 values of type T.  out has var's strides and must not overlap it.
+ * ---------------------------------------------------------------------- */
+int nd_amd_class_stats(const void *var, int dtype, const int64_t *sizes, const int64_t *strides,
+                       const double *labels, const int64_t *label_strides, int nclasses, double *sum,
+                       int64_t *count, int64_t *nan_count, void *hip_stream);
+
+int nd_amd_class_fill(const void *var, void *out, int dtype, const int64_t *sizes, const int64_t *strides,
+                      const double *labels, const int64_t *label_strides, int nclasses, const void *fill,
+                      void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,8 @@ MODES = {'reflect': 0, 'constant': 1, 'nearest': 2, 'mirror': 3, 'wrap': 4,
 KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 4: 'nlmeans', 5: 'boxcar_tiled', 6: 'nlmeans_tiled', 7: 'correlate1d',
                 8: 'relayout', 9: 'omnibus_c2_dense', 10: 'omnibus_c2_fused', 11: 'omnibus_c2_sample', 12: 'omnibus_c2_exact',
-                13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose'}
+                13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose',
+                17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 
 # every symbol include/nd_amd.h declares
@@ -34,7 +35,10 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_timing_select',
            'nd_amd_coregister_shifts_workspace_bytes', 'nd_amd_coregister_shifts',
            'nd_amd_warp_translate_workspace_bytes', 'nd_amd_warp_translate',
-           'nd_amd_rgb_limits_workspace_bytes', 'nd_amd_rgb_limits', 'nd_amd_rgb_compose')
+           'nd_amd_rgb_limits_workspace_bytes', 'nd_amd_rgb_limits', 'nd_amd_rgb_compose',
+           'nd_amd_classify_workspace_bytes', 'nd_amd_classify_forest', 'nd_amd_classify_kmeans',
+           'nd_amd_classify_select', 'nd_amd_classify_gather', 'nd_amd_class_stats', 'nd_amd_class_fill')
+CLASSIFY_BLOCK_ROWS, CLASSIFY_MAX_FEATURES = 1024, 1024
 
 _lib = None
 
@@ -134,6 +138,22 @@ def lib():
     L.nd_amd_rgb_compose.restype = i32
     L.nd_amd_rgb_compose.argtypes = ([C.POINTER(vp), C.POINTER(vp), i32, i32] + [i64] * 6
                                      + [vp, C.POINTER(dbl), C.POINTER(dbl), vp, vp, vp])
+    pi64 = C.POINTER(i64)
+    L.nd_amd_classify_workspace_bytes.restype = C.c_size_t
+    L.nd_amd_classify_workspace_bytes.argtypes = [i32]
+    table = [C.POINTER(vp), i32, i32, pi64, pi64]
+    L.nd_amd_classify_forest.restype = i32
+    L.nd_amd_classify_forest.argtypes = table + [vp, i64, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_classify_kmeans.restype = i32
+    L.nd_amd_classify_kmeans.argtypes = table + [vp, i32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_classify_select.restype = i32
+    L.nd_amd_classify_select.argtypes = table + [vp, pi64, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_classify_gather.restype = i32
+    L.nd_amd_classify_gather.argtypes = table + [vp, pi64, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_class_stats.restype = i32
+    L.nd_amd_class_stats.argtypes = [vp, i32, pi64, pi64, vp, pi64, i32, vp, vp, vp, vp]
+    L.nd_amd_class_fill.restype = i32
+    L.nd_amd_class_fill.argtypes = [vp, vp, i32, pi64, pi64, vp, pi64, i32, vp, vp]
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

@@ -50,7 +50,9 @@ PER_FILE = {'nlmeans.hip': ['-fno-slp-vectorize'] + os.environ.get('ND_AMD_NLM_F
 # ND_AMD_STRICT_SCRATCH=1) if an instantiation exceeds its budget: none for the sparse form (pass A of the benchmark regime), what the fused-search
 # and statistics forms are known to spill in their tails (bytes per lane) otherwise.
 # rgb.hip: the histogram passes and the composite are streaming kernels; none of its kernels may spill
-NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_'}
+# classify.hip: the forest kernel picks a row's feature by a select chain so that its register copies are
+# never indexed at run time; a spill would mean that form was lost
+NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_', 'classify.hip': 'class'}
 # bytes per lane by the kernel's template arguments <K, KMAX, STATS, CHAIN>, keyed (STATS, CHAIN)
 SCRATCH_BUDGET = {(False, False): 0, (False, True): 96, (True, False): 256, (True, True): 384}
 

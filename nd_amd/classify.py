@@ -1,0 +1,622 @@
+"""
+nd_amd/classify.py -- pixel classification (nd/classify.py) with prediction on the GPU.
+
+  Classifier      nd.classify.Classifier: make_Xy, fit, predict, fit_predict, score
+  class_mean      nd.classify.class_mean
+  ForestModel, KMeansModel, predict_forest, predict_kmeans
+                  the device path for callers that hold a fitted model as plain arrays
+
+Training is scikit-learn's and runs on the host: it sees only the labelled pixels and is not a hot path.
+What the device does for it is the selection of those pixels -- label > 0 and not NaN, no NaN feature --
+and their gather into a dense (n, n_features) matrix, in the reference's row order, straight from the
+variables.  Prediction sees every pixel and runs on the device without ever forming the reference's
+(n_pixels, n_features) matrix: the kernels read each feature where it lies.
+
+Supported for `predict` (anything else raises NotImplementedError; there is no CPU fallback):
+  DecisionTreeClassifier, ExtraTreeClassifier, RandomForestClassifier, ExtraTreesClassifier with one
+  output and numeric classes_: func='predict' and func='predict_proba'.  Probabilities are bit-equal to
+  scikit-learn 1.7.2 at n_jobs=1 (with n_jobs > 1 scikit-learn adds the trees in thread order and does
+  not reproduce its own last bit); labels are equal everywhere, ties included.
+  KMeans, MiniBatchKMeans: func='predict', the first nearest centre in float64.
+
+Row order and feature order are the reference's (_build_X, _get_data_dims): rows run over the data
+dimensions in the order of the dataset's dimension coordinates (for an xr_lite object without coordinates:
+the first variable's dimension order), feature = (position along feature_dims) * n_variables + variable.
+Variables may be numpy arrays (copied up, results copied down) or torch ROCm tensors (results stay on the
+device).  float32 and float64 are computed as they are, integers as float64.
+"""
+from collections import OrderedDict
+
+import numpy as np
+
+from . import _adapter, _device, xr_lite
+
+__all__ = ['Classifier', 'class_mean', 'ForestModel', 'KMeansModel', 'predict_forest', 'predict_kmeans',
+           'pack_forest']
+
+FORESTS = ('DecisionTreeClassifier', 'ExtraTreeClassifier', 'RandomForestClassifier', 'ExtraTreesClassifier')
+KMEANS = ('KMeans', 'MiniBatchKMeans')
+_SUPPORTED = ('nd_amd.classify predicts on the device with %s (func "predict" or "predict_proba"; one output, '
+              'numeric classes_) and %s (func "predict"); there is no CPU fallback.  '
+              % (', '.join(FORESTS), ', '.join(KMEANS)))
+
+
+# ---------------------------------------------------------------------------
+# models as plain arrays
+# ---------------------------------------------------------------------------
+def pack_forest(feature, threshold, left, right, tree_offsets):
+    """-> (nodes (n, 4) int32, roots int32).  A node is {bits of t32, feature, left, right} with absolute
+    child indices; a leaf has feature -1 and its own index in `left` (its row in the value table).
+    scikit-learn goes left where float32(x) <= float64 threshold; for a float32 x that is x <= t32 with
+    t32 the largest float32 not above the threshold."""
+    feature, left, right = (np.asarray(a, np.int64) for a in (feature, left, right))
+    threshold = np.asarray(threshold, np.float64)
+    offsets = np.asarray(tree_offsets, np.int64)
+    n = feature.size
+    with np.errstate(over='ignore'):
+        t32 = threshold.astype(np.float32)
+    above = t32.astype(np.float64) > threshold
+    t32[above] = np.nextafter(t32[above], np.float32(-np.inf))
+    base = np.repeat(offsets[:-1], np.diff(offsets))
+    leaf = left < 0
+    nodes = np.empty((n, 4), np.int32)
+    nodes[:, 0] = t32.view(np.int32)
+    nodes[:, 1] = np.where(leaf, -1, feature)
+    nodes[:, 2] = np.where(leaf, np.arange(n), left + base)
+    nodes[:, 3] = np.where(leaf, np.arange(n), right + base)
+    nodes[leaf, 0] = 0
+    return nodes, offsets[:-1].astype(np.int32)
+
+
+class ForestModel:
+    """A fitted decision forest as arrays: the trees' nodes concatenated in estimator order.
+    feature, threshold, left, right : (n_nodes,) as scikit-learn's tree_.feature / threshold / children_left /
+        children_right (children are indices inside their own tree, -1 at a leaf)
+    value : (n_nodes, n_classes) float64, tree_.value[:, 0, :]
+    tree_offsets : (n_trees + 1,) first node of every tree, and n_nodes
+    classes : (n_classes,) numeric classes_"""
+
+    def __init__(self, feature, threshold, left, right, value, tree_offsets, classes, n_features=None):
+        self.feature = np.ascontiguousarray(feature, np.int64)
+        self.threshold = np.ascontiguousarray(threshold, np.float64)
+        self.left = np.ascontiguousarray(left, np.int64)
+        self.right = np.ascontiguousarray(right, np.int64)
+        self.value = np.ascontiguousarray(value, np.float64)
+        self.tree_offsets = np.ascontiguousarray(tree_offsets, np.int64)
+        classes = np.asarray(classes)
+        if classes.dtype.kind not in 'iufb':
+            raise NotImplementedError(_SUPPORTED + 'classes_ of type %s are not numeric.' % classes.dtype)
+        self.classes = np.ascontiguousarray(classes, np.float64)
+        n = self.feature.size
+        off = self.tree_offsets
+        if not (self.threshold.shape == self.left.shape == self.right.shape == self.feature.shape == (n,)
+                and self.value.shape == (n, self.classes.size) and n >= 1 and self.classes.size >= 1):
+            raise ValueError('ForestModel: the node arrays must be (n_nodes,) and value (n_nodes, n_classes)')
+        if off.ndim != 1 or off.size < 2 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 1):
+            raise ValueError('ForestModel: tree_offsets must rise from 0 to n_nodes')
+        if n >= 2 ** 31:
+            raise ValueError('ForestModel: too many nodes')
+        size = np.repeat(np.diff(off), np.diff(off))
+        leaf = self.left < 0
+        inner = ~leaf
+        if (np.any(self.left[inner] >= size[inner]) or np.any(self.right[inner] >= size[inner])
+                or np.any(self.right[inner] < 0) or np.any(self.feature[inner] < 0)):
+            raise ValueError('ForestModel: a child index or feature lies outside its tree')
+        local = np.arange(n) - np.repeat(off[:-1], np.diff(off))
+        if np.any(self.left[inner] <= local[inner]) or np.any(self.right[inner] <= local[inner]):
+            raise ValueError('ForestModel: a child must follow its parent (a walk must end)')
+        if np.any(np.isnan(self.threshold[inner])):
+            raise ValueError('ForestModel: NaN threshold')
+        need = int(self.feature[inner].max()) + 1 if inner.any() else 1
+        self.n_features = int(n_features) if n_features is not None else need
+        if self.n_features < need:
+            raise ValueError('ForestModel: a node asks for feature %d of %d' % (need - 1, self.n_features))
+        self._packed = None
+        self._device = {}
+
+    n_trees = property(lambda self: self.tree_offsets.size - 1)
+    n_classes = property(lambda self: self.classes.size)
+
+    @classmethod
+    def from_sklearn(cls, clf):
+        names = {c.__name__ for c in type(clf).__mro__}
+        if not names & set(FORESTS):
+            raise NotImplementedError(_SUPPORTED + 'Got %s.' % type(clf).__name__)
+        from sklearn.utils.validation import check_is_fitted
+        check_is_fitted(clf)
+        if getattr(clf, 'n_outputs_', 1) != 1:
+            raise NotImplementedError(_SUPPORTED + 'Got a multi-output %s.' % type(clf).__name__)
+        trees = [e.tree_ for e in getattr(clf, 'estimators_', [clf])]
+        nc = len(clf.classes_)
+        offsets = np.concatenate([[0], np.cumsum([t.node_count for t in trees])])
+        cat = lambda key: np.concatenate([getattr(t, key) for t in trees])
+        return cls(cat('feature'), cat('threshold'), cat('children_left'), cat('children_right'),
+                   np.concatenate([t.value[:, 0, :nc] for t in trees]), offsets, clf.classes_,
+                   n_features=clf.n_features_in_)
+
+    def packed(self):
+        if self._packed is None:
+            self._packed = pack_forest(self.feature, self.threshold, self.left, self.right, self.tree_offsets)
+        return self._packed
+
+    def depth(self):
+        """the longest root-to-leaf path of any tree, in edges"""
+        nodes, roots = self.packed()
+        front, d = roots.astype(np.int64), 0
+        while True:
+            inner = front[nodes[front, 1] >= 0]
+            if not inner.size:
+                return d
+            front = np.concatenate([nodes[inner, 2], nodes[inner, 3]]).astype(np.int64)
+            d += 1
+
+    def _on(self, dev):
+        import torch
+        if dev not in self._device:
+            nodes, roots = self.packed()
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            self._device[dev] = (up(nodes.view(np.uint8).reshape(-1)), up(self.value), up(roots), up(self.classes))
+        return self._device[dev]
+
+
+class KMeansModel:
+    """Fitted k-means centres, (k, n_features), held as float64."""
+
+    def __init__(self, centers):
+        self.centers = np.ascontiguousarray(centers, np.float64)
+        if self.centers.ndim != 2 or self.centers.shape[0] < 1 or self.centers.shape[1] < 1:
+            raise ValueError('KMeansModel: centers must be (k, n_features)')
+        self.n_features = self.centers.shape[1]
+        self._device = {}
+
+    @classmethod
+    def from_sklearn(cls, clf):
+        names = {c.__name__ for c in type(clf).__mro__}
+        if not names & set(KMEANS):
+            raise NotImplementedError(_SUPPORTED + 'Got %s.' % type(clf).__name__)
+        from sklearn.utils.validation import check_is_fitted
+        check_is_fitted(clf)
+        return cls(clf.cluster_centers_)
+
+    def _on(self, dev):
+        import torch
+        if dev not in self._device:
+            self._device[dev] = torch.from_numpy(self.centers).to(dev)
+        return self._device[dev]
+
+
+def _fitted_state(clf):
+    """what a model was built from: ('trees', the tree_ objects in estimator order) or ('centres', a copy
+    of cluster_centers_); None for an estimator that holds neither (unfitted)"""
+    if hasattr(clf, 'estimators_'):
+        return 'trees', [getattr(e, 'tree_', None) for e in clf.estimators_]
+    if getattr(clf, 'tree_', None) is not None:
+        return 'trees', [clf.tree_]
+    if getattr(clf, 'cluster_centers_', None) is not None:
+        return 'centres', np.array(clf.cluster_centers_, copy=True)
+    return None
+
+
+def _same_state(a, b):
+    if a is None or b is None or a[0] != b[0]:
+        return False
+    if a[0] == 'trees':
+        return len(a[1]) == len(b[1]) and all(x is y and x is not None for x, y in zip(a[1], b[1]))
+    return a[1].shape == b[1].shape and a[1].dtype == b[1].dtype and bool(np.array_equal(a[1], b[1]))
+
+
+def _model_for(clf, func, build=True):
+    """the model of a fitted estimator for `func`; build=False only checks that the pair is served"""
+    names = {c.__name__ for c in type(clf).__mro__}
+    if names & set(FORESTS):
+        if func not in ('predict', 'predict_proba'):
+            raise NotImplementedError(_SUPPORTED + 'Got func=%r.' % func)
+        return ForestModel.from_sklearn(clf) if build else None
+    if names & set(KMEANS):
+        if func != 'predict':
+            raise NotImplementedError(_SUPPORTED + 'Got func=%r for %s.' % (func, type(clf).__name__))
+        return KMeansModel.from_sklearn(clf) if build else None
+    raise NotImplementedError(_SUPPORTED + 'Got %s.' % type(clf).__name__)
+
+
+# ---------------------------------------------------------------------------
+# layout: which element is feature f of row r
+# ---------------------------------------------------------------------------
+def _data_dims(ds, feature_dims):
+    """nd/classify.py:62-65, the order of the dimension coordinates; without them (xr_lite), the first
+    variable's dimension order"""
+    every = [d for d in ds.dims if d not in feature_dims]
+    dims = [d for d in ds.coords if d in every]
+    if set(dims) == set(every):
+        return tuple(dims)
+    if _adapter.namespace(ds) is not xr_lite:
+        raise ValueError('dimensions %s have no coordinates' % sorted(set(every) - set(dims)))
+    if isinstance(ds, xr_lite.DataArray):
+        return tuple(every)
+    first = next(iter(ds.data_vars.values()))
+    return tuple([d for d in first.dims if d in every] + [d for d in every if d not in first.dims])
+
+
+def _variables(ds, data_dims):
+    ns = _adapter.namespace(ds)
+    if isinstance(ds, ns.DataArray):
+        return [ds]
+    names = _adapter.get_vars_for_dims(ds, data_dims)
+    if not names:
+        raise ValueError('no variable spans the data dimensions %s' % (data_dims,))
+    return [ds[n] for n in names]
+
+
+class _Layout:
+    """The feature table of a dataset: device views, one per feature, that share the row strides."""
+
+    def __init__(self, ds, feature_dims):
+        import torch
+        feature_dims = tuple(feature_dims)
+        self.ns = _adapter.namespace(ds)
+        self.data_dims = _data_dims(ds, feature_dims)
+        if len(self.data_dims) > 4:
+            raise ValueError('at most four data dimensions, got %s' % (self.data_dims,))
+        variables = _variables(ds, self.data_dims)
+        values = [v.values for v in variables]
+        for v in values:
+            if _device.np_dtype(v).kind == 'c':
+                raise TypeError('Classifier: complex variables cannot be features; split them into real ones '
+                                'first (disassemble_complex)')
+            if _device.np_dtype(v).kind not in 'fiub' or _device.np_dtype(v) == np.float16:
+                raise TypeError('Classifier: unsupported dtype %s' % _device.np_dtype(v))
+        self.host = not any(_device.is_tensor(v) and v.is_cuda for v in values)
+        self.device = _device.device_of(*values)
+        sizes = ds.sizes
+        self.shape = tuple(int(sizes[d]) for d in self.data_dims)
+        self.coords = OrderedDict((d, ds.coords[d]) for d in self.data_dims if d in ds.coords)
+        fdims = [d for d in feature_dims if d in ds.dims]
+        fshape = [int(sizes[d]) for d in fdims]
+        all32 = all(_device.np_dtype(v) == np.float32 for v in values)
+        dtype = torch.float32 if all32 else torch.float64
+        self.np_dtype = np.dtype(np.float32 if all32 else np.float64)
+        with torch.cuda.device(self.device):
+            views = []
+            for da, v in zip(variables, values):
+                t = _device.to_device(v, self.device)
+                t = t if t.dtype == dtype else t.to(dtype)
+                own = [d for d in fdims if d in da.dims]
+                t = t.permute(*[da.dims.index(d) for d in own + list(self.data_dims)])
+                views.append((t, own))
+            nrow = len(self.data_dims)
+            strides = {tuple(s for s, n in zip(t.stride()[t.dim() - nrow:], self.shape) if n > 1) for t, _ in views}
+            if len(strides) > 1:
+                views = [(t.contiguous(), own) for t, own in views]
+            t0 = views[0][0]
+            self.strides = tuple(int(s) for s in t0.stride()[t0.dim() - nrow:])
+            # feature = (position along feature_dims) * n_variables + variable; a variable without one of the
+            # feature dimensions is the same at every position along it, as xarray's to_array broadcasts it
+            self.features = []
+            for pos in np.ndindex(*fshape):
+                for t, own in views:
+                    idx = tuple(p for p, d in zip(pos, fdims) if d in own)
+                    self.features.append(t[idx] if idx else t)
+        self.n_features = len(self.features)
+
+    def label_args(self, labels):
+        """labels squeezed and broadcast over the data dimensions they lack (_broadcast_labels,
+        nd/classify.py:74-100) -> (float64 device tensor, element strides per data dimension, label dtype)"""
+        import torch
+        if hasattr(labels, 'data_vars'):
+            raise ValueError("`labels` should be an xarray.DataArray or numpy array of the same dimensions "
+                             "as the dataset.")
+        if hasattr(labels, 'dims') and hasattr(labels, 'values'):
+            vals, dims = labels.values, tuple(labels.dims)
+            keep = [i for i, n in enumerate(vals.shape) if n != 1]
+            vals = vals.reshape([vals.shape[i] for i in keep])
+            dims = [dims[i] for i in keep]
+            extra = set(dims) - set(self.data_dims)
+            if extra:
+                raise ValueError('labels have dimensions %s the data lacks' % sorted(extra))
+            for d, n in zip(dims, vals.shape):
+                if n != self.shape[self.data_dims.index(d)]:
+                    raise ValueError('labels have size %d along %s, the data %d'
+                                     % (n, d, self.shape[self.data_dims.index(d)]))
+            t = self._label_tensor(vals)
+            strides = [t.stride(dims.index(d)) if d in dims else 0 for d in self.data_dims]
+        else:
+            vals = labels if _device.is_tensor(labels) else np.asarray(labels)
+            vals = vals.reshape([n for n in vals.shape if n != 1])
+            matching = list(self.shape)
+            new_shape = [1] * len(matching)
+            for n in vals.shape:
+                i = matching.index(n)          # ValueError where no dimension has that size, as the reference
+                new_shape[i] = n
+                matching[i] = None
+            t = self._label_tensor(vals).reshape(new_shape)
+            strides = [t.stride(i) if new_shape[i] != 1 else 0 for i in range(len(new_shape))]
+        strides = [s if n > 1 else 0 for s, n in zip(strides, self.shape)]
+        return t, strides, _device.np_dtype(vals)
+
+    def _label_tensor(self, vals):
+        import torch
+        with torch.cuda.device(self.device):
+            return _device.to_device(vals, self.device).to(torch.float64).contiguous()
+
+    def wrap(self, values, extra_dim=None):
+        """values over the data dimensions (+ extra_dim) -> a DataArray of the input's kind"""
+        dims = self.data_dims + ((extra_dim,) if extra_dim else ())
+        coords = OrderedDict(self.coords)
+        if extra_dim:
+            coords[extra_dim] = np.arange(values.shape[-1])
+        if self.host:
+            values = _device.to_host(values)
+        if self.ns is xr_lite:
+            return xr_lite.DataArray(values, dims, coords)
+        return self.ns.DataArray(values, dims=dims, coords=coords)
+
+
+def _scaler_arrays(scaler):
+    if scaler is None:
+        return None, None
+    mean, scale = getattr(scaler, 'mean_', None), getattr(scaler, 'scale_', None)
+    if mean is None or scale is None:
+        raise NotImplementedError('nd_amd.classify: the device scaler needs a StandardScaler with mean_ and scale_')
+    return np.asarray(mean, np.float64), np.asarray(scale, np.float64)
+
+
+def _check_features(layout, model):
+    if layout.n_features != model.n_features:
+        raise ValueError('the model was fitted on %d features, the dataset gives %d'
+                         % (model.n_features, layout.n_features))
+
+
+def predict_forest(ds, model, feature_dims=(), func='predict', scaler=None):
+    """`model` (a ForestModel) applied to every pixel of `ds` on the device.  func: 'predict' or
+    'predict_proba'.  scaler: None, or an object with mean_ and scale_ (a fitted StandardScaler).
+    Returns a float64 DataArray over the data dimensions (with a trailing `label` dimension for
+    predict_proba), NaN where any feature of the pixel is NaN."""
+    from . import kernels
+    if func not in ('predict', 'predict_proba'):
+        raise NotImplementedError(_SUPPORTED + 'Got func=%r.' % func)
+    layout = _Layout(ds, feature_dims)
+    _check_features(layout, model)
+    mean, scale = _scaler_arrays(scaler)
+    nodes, values, roots, classes = model._on(layout.device)
+    proba = func == 'predict_proba'
+    labels, p = kernels.classify_forest(layout.features, layout.shape, layout.strides, nodes, values, roots,
+                                        classes, mean, scale, want_labels=not proba, want_proba=proba)
+    return layout.wrap(p, 'label') if proba else layout.wrap(labels)
+
+
+def predict_kmeans(ds, model, feature_dims=(), scaler=None):
+    """The index of the nearest centre of `model` (a KMeansModel) for every pixel of `ds`, the first
+    where several are equally near; distances are summed in float64 in feature order.  Returns a float64
+    DataArray over the data dimensions, NaN where any feature is NaN."""
+    from . import kernels
+    layout = _Layout(ds, feature_dims)
+    _check_features(layout, model)
+    mean, scale = _scaler_arrays(scaler)
+    labels = kernels.classify_kmeans(layout.features, layout.shape, layout.strides, model._on(layout.device),
+                                     mean, scale)
+    return layout.wrap(labels)
+
+
+# ---------------------------------------------------------------------------
+# nd.classify.Classifier
+# ---------------------------------------------------------------------------
+class Classifier:
+    """
+    Parameters
+    ----------
+    clf : sklearn classifier
+        An initialized classifier object as provided by ``scikit-learn``.  Must provide ``fit``; see the
+        module docstring for the estimators ``predict`` serves.
+    feature_dims : list, optional
+        Additional dimensions to use as features: with ``'time'`` every time step is an independent
+        variable; otherwise time steps are further data dimensions like ``'x'`` and ``'y'``.
+    scale : bool, optional
+        If True, scale the input data to zero mean and unit variance (default: False).
+
+    Fitting (``clf.fit``, ``StandardScaler().fit``) is scikit-learn's, on the host, on the labelled pixels
+    only: it is not a hot path.  Selecting and gathering those pixels, and ``predict``, run on the device.
+    """
+
+    def __init__(self, clf, feature_dims=[], scale=False):
+        self.clf = clf
+        self.feature_dims = feature_dims
+        self.scale = scale
+        self._scaler = None
+        self._model = None          # (clf, the fitted state it was built from, model): see _cached_model
+
+    def make_Xy(self, ds, labels=None):
+        """scikit-learn compatible X and y (numpy arrays, X in the data's type) from `ds` and `labels`
+        (a DataArray or numpy array; pixels whose label is NaN or <= 0, or with a NaN feature, are left
+        out).  The rows are selected and gathered on the device; only they reach the host."""
+        from . import kernels
+        layout = _Layout(ds, self.feature_dims)
+        lab = strides = ldtype = None
+        if labels is not None:
+            lab, strides, ldtype = layout.label_args(labels)
+        X, y, _ = kernels.classify_gather(layout.features, layout.shape, layout.strides, lab, strides)
+        X = np.asarray(_device.to_host(X))
+        y = np.asarray(_device.to_host(y)).astype(ldtype) if y is not None else None
+        if self.scale:
+            from sklearn import preprocessing
+            self._scaler = preprocessing.StandardScaler()
+            self._scaler.fit(X)
+            X = self._scaler.transform(X)
+        return (X, y)
+
+    def fit(self, ds, labels=None):
+        """Train the classifier with scikit-learn on the pixels make_Xy selects (labels may be omitted for
+        an unsupervised estimator such as KMeans)."""
+        X, y = self.make_Xy(ds, labels=labels)
+        self._model = None
+        self.clf.fit(X, y)
+        return self
+
+    def predict(self, ds, func='predict'):
+        """The predicted class labels of every pixel (func='predict'), or the class probabilities with a
+        trailing `label` dimension (func='predict_proba'), computed on the device: a float64 DataArray over
+        the data dimensions, NaN where any feature is NaN."""
+        if func not in dir(self.clf):
+            raise AttributeError('Classifier has no method {}.'.format(func))
+        model = self._cached_model(func)
+        scaler = None
+        if self.scale:
+            if self._scaler is None:
+                raise AttributeError('Classifier(scale=True) has no fitted scaler: call fit first')
+            scaler = self._scaler
+        if isinstance(model, ForestModel):
+            return predict_forest(ds, model, self.feature_dims, func, scaler)
+        return predict_kmeans(ds, model, self.feature_dims, scaler)
+
+    def _cached_model(self, func):
+        """The arrays of the fitted estimator, packed and uploaded once while the fitted state stays what it
+        was.  The state is compared by content where scikit-learn may change it in place: the tree objects
+        of every estimator, one by one (warm_start extends estimators_ in place), and a copy of the k-means
+        centres (partial_fit updates cluster_centers_ in place)."""
+        clf = self.clf
+        _model_for(clf, func, build=False)
+        state = _fitted_state(clf)
+        if self._model is not None and state is not None:
+            old_clf, old_state, model = self._model
+            if old_clf is clf and _same_state(state, old_state):
+                return model
+        model = _model_for(clf, func)
+        self._model = (clf, state, model)
+        return model
+
+    def fit_predict(self, ds, labels=None):
+        self.fit(ds, labels)
+        return self.predict(ds)
+
+    def score(self, ds, labels=None, method='accuracy'):
+        """The classification score (a scikit-learn scorer name) on the labelled pixels.  As in the
+        reference this goes through make_Xy, which with scale=True re-fits the scaler on `ds`."""
+        from sklearn import metrics
+        try:
+            scorer = metrics.get_scorer(method)
+        except Exception:
+            raise ValueError("'{}' is not a valid scoring method".format(method))
+        X, y = self.make_Xy(ds, labels=labels)
+        return scorer(self.clf, X, y)
+
+
+# ---------------------------------------------------------------------------
+# class_mean
+# ---------------------------------------------------------------------------
+def class_mean_fill(sums, counts, nans, dtype):
+    """The closed form of the reference's loop (nd/classify.py:36-44) for one variable.  Round l gives every
+    pixel of class l -- and every pixel of ANY class that is still NaN -- the mean m_l of the class's
+    non-NaN pixels.  So the NaN pixels of a class take the first non-NaN mean of an earlier round and then
+    count, at that value, in their own class's mean; a class whose mean is NaN ends at the first non-NaN
+    mean after it.  -> fill values (n + 1,) of `dtype`: one per class, and the value NaN pixels of no
+    class end at."""
+    n = len(sums)
+    fill = np.full(n + 1, np.nan, np.float64)
+    first = np.nan
+    for l in range(n):
+        s, c = float(sums[l]), int(counts[l])
+        if nans[l] and not np.isnan(first):
+            s += int(nans[l]) * float(first)
+            c += int(nans[l])
+        m = np.dtype(dtype).type(s / c) if c else np.nan
+        fill[l] = m
+        if np.isnan(first) and not np.isnan(m):
+            first = m
+    fill[np.isnan(fill)] = first
+    return fill.astype(dtype)
+
+
+def _n_labels(vals):
+    """len(np.unique(labels)), NaN counting once"""
+    if _device.is_tensor(vals):
+        import torch
+        v = vals.reshape(-1)
+        if v.is_floating_point():
+            nan = torch.isnan(v)
+            return int(torch.unique(v[~nan]).numel()) + int(bool(nan.any()))
+        return int(torch.unique(v).numel())
+    return len(np.unique(np.asarray(vals)))
+
+
+def _class_label_strides(da, ldims, lshape, lstrides, name):
+    """element strides of the labels along every dimension of the variable `da` (0 where they are broadcast).
+    ldims: the labels' dimension names (matched by name, sizes must agree) or None for an array of shape
+    `lshape` matched by size as _broadcast_array does.  lstrides None: only validate."""
+    shape = tuple(da.shape)
+    lstrides = lstrides if lstrides is not None else (0,) * len(lshape)
+    if ldims is not None:
+        missing = [d for d in ldims if d not in da.dims]
+        if missing:
+            raise ValueError('class_mean: variable %r lacks the label dimensions %s' % (name, missing))
+        for d, size in zip(ldims, lshape):
+            if size != shape[da.dims.index(d)]:
+                raise ValueError('class_mean: labels have size %d along %s, variable %r has %d'
+                                 % (size, d, name, shape[da.dims.index(d)]))
+        return [lstrides[ldims.index(d)] if d in ldims else 0 for d in da.dims]
+    matching, ls = list(shape), [0] * len(shape)
+    for ax, size in enumerate(lshape):
+        if size not in matching:
+            raise ValueError('class_mean: no dimension of variable %r %s has the labels\' size %d'
+                             % (name, shape, size))
+        i = matching.index(size)
+        ls[i], matching[i] = lstrides[ax], None
+    return ls
+
+
+def class_mean(ds, labels):
+    """Replace every pixel of the dataset with the mean of its class (or cluster, or segment).
+
+    ds : Dataset or DataArray.  labels : DataArray whose dimensions may be a subset of those of `ds`
+    (such as ('y', 'x') against a stack with a 'time' dimension), or an array matched to the dimensions by
+    size.  Returns an object like `ds` in the data's type (integers as float64).
+
+    The reference's loop is reproduced with its consequences: with n = len(np.unique(labels)) only the
+    labels 0 .. n-1 are classes, pixels with another label keep their value; a NaN pixel of any class takes
+    the mean of the first class that has one (class 0 in the first round) and then counts, at that value,
+    in its own class's mean.  Per-class sums are float64, formed on the device in one pass; a second pass
+    fills."""
+    import torch
+    from . import kernels
+    ns = _adapter.namespace(ds)
+    single = isinstance(ds, ns.DataArray)
+    variables = OrderedDict([(None, ds)]) if single else OrderedDict((k, ds[k]) for k in ds.data_vars)
+    named = hasattr(labels, 'dims') and hasattr(labels, 'values')
+    lvals = labels.values if named else (labels if _device.is_tensor(labels) else np.asarray(labels))
+    # dimensions of size 1 are squeezed, as make_Xy squeezes them
+    ldims = tuple(d for d, size in zip(labels.dims, lvals.shape) if size != 1) if named else None
+    lvals = lvals.reshape([size for size in lvals.shape if size != 1])
+    for name, da in variables.items():          # before any device work: a wrong extent would read past the labels
+        _class_label_strides(da, ldims, tuple(lvals.shape), None, name)
+    n = _n_labels(lvals)
+    values = [v.values for v in variables.values()]
+    host = not any(_device.is_tensor(v) and v.is_cuda for v in values)
+    dev = _device.device_of(*values)
+    out = OrderedDict()
+    with torch.cuda.device(dev):
+        lab = _device.to_device(lvals, dev).to(torch.float64).contiguous()
+        for name, da in variables.items():
+            v = da.values
+            if _device.np_dtype(v).kind == 'c':
+                raise TypeError('class_mean: complex variables are not supported (disassemble_complex)')
+            t = _device.to_device(v, dev)
+            if t.dtype not in (torch.float32, torch.float64):
+                t = t.to(torch.float64)
+            if torch.empty_like(t).stride() != t.stride():
+                t = t.contiguous()
+            ls = _class_label_strides(da, ldims, tuple(lab.shape), lab.stride(), name)
+            s, c, k = kernels.class_stats(t, lab, ls, n)
+            fill = class_mean_fill(s.cpu().numpy(), c.cpu().numpy(), k.cpu().numpy(), _device.np_dtype(t))
+            res = kernels.class_fill(t, lab, ls, torch.from_numpy(fill).to(dev))
+            out[name] = _device.to_host(res) if host else res
+    if single:
+        if ns is xr_lite:
+            return xr_lite.DataArray(out[None], ds.dims, ds.coords, ds.attrs, ds.name)
+        return ds.copy(data=out[None])
+    if ns is xr_lite:
+        res = xr_lite.Dataset(coords=ds.coords, attrs=ds.attrs)
+        for k, v in out.items():
+            res[k] = (tuple(ds[k].dims), v, ds[k].attrs)
+        return res
+    res = ds.copy()
+    for k, v in out.items():
+        res[k] = (ds[k].dims, v, ds[k].attrs)
+    return res

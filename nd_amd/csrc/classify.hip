@@ -1,0 +1,808 @@
+// nd_amd/csrc/classify.hip -- pixel classification (nd/classify.py) on the device:
+//   nd_amd_classify_forest   decision-forest predict / predict_proba, scikit-learn's arithmetic
+//   nd_amd_classify_kmeans   nearest centre in float64
+//   nd_amd_classify_select / _gather   the training rows, compacted in row order
+//   nd_amd_class_stats / _fill         per-class statistics and the fill of class_mean
+// No (rows, features) matrix is ever formed: a row's feature f is read from feat[f] + row offset.
+// The definitions are in include/nd_amd.h.
+#include <math.h>
+
+#include "common.hpp"
+
+using namespace nd_amd;
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int SELECT_ITEMS = ND_AMD_CLASSIFY_BLOCK_ROWS / BLOCK;   // rows per thread of select / gather
+constexpr int MAX_LDS_FEATURES = ND_AMD_CLASSIFY_MAX_FEATURES;             // pointer table staged in LDS: 8 KiB
+constexpr int STATS_REG_CLASSES = 8;
+constexpr int STATS_LDS_CLASSES = 1024;
+
+static_assert(ND_AMD_CLASSIFY_BLOCK_ROWS % BLOCK == 0, "block rows");
+
+// Up to four row dimensions, row-major, after the host merged what is contiguous: most stacks arrive
+// here as ONE dimension and rows need no division.
+struct RowDims {
+    int64_t n1, n2, n3;       // sizes of dimensions 1..3 (dimension 0 is whatever remains)
+    int64_t s[4];             // element strides of the features
+    int64_t ls[4];            // element strides of the labels (0 where they are broadcast)
+};
+
+__device__ __forceinline__ void row_offsets(const RowDims &R, int64_t row, int64_t &off, int64_t &loff)
+{
+    if (R.n1 == 1 && R.n2 == 1 && R.n3 == 1) {
+        off = row * R.s[0];
+        loff = row * R.ls[0];
+        return;
+    }
+    const int64_t i3 = row % R.n3;
+    row /= R.n3;
+    const int64_t i2 = row % R.n2;
+    row /= R.n2;
+    const int64_t i1 = row % R.n1;
+    const int64_t i0 = row / R.n1;
+    off = i0 * R.s[0] + i1 * R.s[1] + i2 * R.s[2] + i3 * R.s[3];
+    loff = i0 * R.ls[0] + i1 * R.ls[1] + i2 * R.ls[2] + i3 * R.ls[3];
+}
+
+// StandardScaler.transform as numpy evaluates it in place on X of type T with float64 operands:
+// X -= mean_ ; X /= scale_  -- each step computed in float64 and rounded to T.
+template <typename T>
+__device__ __forceinline__ T scaled(T v, const double *mean, const double *scale, int f)
+{
+    if (mean != nullptr) {
+        v = (T)((double)v - mean[f]);
+        v = (T)((double)v / scale[f]);
+    }
+    return v;
+}
+
+template <int NREG>
+__device__ __forceinline__ void stage_table(const void **sbase, const void *const *tab, int nfeat)
+{
+    if (NREG == 0) {
+        for (int i = threadIdx.x; i < nfeat; i += BLOCK) sbase[i] = tab[i];
+        __syncthreads();
+    }
+}
+
+// ---- forest -----------------------------------------------------------------------------------
+// node: {bits of t32, feature (-1: leaf), left | row of `values`, right}, absolute node indices.
+// NREG > 0: the row's nfeat <= NREG features live in registers (as float32, what the trees see) and a
+// node picks one by a select chain.  NREG == 0: the feature a node asks for is read from memory.
+// NC class accumulators in registers; more classes than NC walk the forest once per NC classes, which
+// keeps every class's sum in tree order.
+template <typename T, int NREG, int NC>
+__global__ __launch_bounds__(BLOCK) void classify_forest_kernel(
+    const void *const *tab, int nfeat, RowDims R, int64_t rows, const int4 *__restrict__ nodes,
+    const double *__restrict__ values, const int32_t *__restrict__ roots, int ntrees,
+    const double *__restrict__ classes, int nclasses, const double *__restrict__ mean,
+    const double *__restrict__ scale, double *__restrict__ labels, double *__restrict__ proba)
+{
+    __shared__ const void *sbase[NREG == 0 ? MAX_LDS_FEATURES : 1];
+    stage_table<NREG>(sbase, tab, nfeat);
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < rows; row += (int64_t)gridDim.x * BLOCK) {
+        int64_t off, loff;
+        row_offsets(R, row, off, loff);
+        float x[NREG > 0 ? NREG : 1];
+        bool masked = false;
+        if (NREG > 0) {
+#pragma unroll
+            for (int j = 0; j < NREG; j++) {
+                x[j] = 0.f;
+                if (j < nfeat) {
+                    const T v = static_cast<const T *>(tab[j])[off];
+                    masked |= (v != v);
+                    x[j] = (float)scaled<T>(v, mean, scale, j);
+                }
+            }
+        } else {
+            for (int f = 0; f < nfeat; f++) {
+                const T v = static_cast<const T *>(sbase[f])[off];
+                masked |= (v != v);
+            }
+        }
+        if (masked) {
+            if (labels) labels[row] = nan;
+            if (proba)
+                for (int c = 0; c < nclasses; c++) proba[row * nclasses + c] = nan;
+            continue;
+        }
+        double best = -1.0;
+        int besti = 0;
+        for (int c0 = 0; c0 < nclasses; c0 += NC) {
+            double acc[NC];
+#pragma unroll
+            for (int c = 0; c < NC; c++) acc[c] = 0.0;
+            for (int t = 0; t < ntrees; t++) {
+                int4 nd = nodes[roots[t]];
+                while (nd.y >= 0) {
+                    float xv;
+                    if (NREG > 0) {
+                        xv = x[0];
+#pragma unroll
+                        for (int j = 1; j < NREG; j++) xv = (nd.y == j) ? x[j] : xv;
+                    } else {
+                        const T v = static_cast<const T *>(sbase[nd.y])[off];
+                        xv = (float)scaled<T>(v, mean, scale, nd.y);
+                    }
+                    nd = nodes[(xv <= __int_as_float(nd.x)) ? nd.z : nd.w];
+                }
+                const double *lv = values + (int64_t)nd.z * nclasses + c0;
+#pragma unroll
+                for (int c = 0; c < NC; c++)
+                    if (c0 + c < nclasses) acc[c] += lv[c];
+            }
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                if (c0 + c < nclasses) {
+                    const double p = acc[c] / (double)ntrees;
+                    if (proba) proba[row * nclasses + c0 + c] = p;
+                    if (p > best) {
+                        best = p;
+                        besti = c0 + c;
+                    }
+                }
+            }
+        }
+        if (labels) labels[row] = classes[besti];
+    }
+}
+
+// ---- k-means ----------------------------------------------------------------------------------
+template <typename T, int NREG>
+__global__ __launch_bounds__(BLOCK) void classify_kmeans_kernel(
+    const void *const *tab, int nfeat, RowDims R, int64_t rows, const double *__restrict__ centers, int k,
+    const double *__restrict__ mean, const double *__restrict__ scale, double *__restrict__ labels)
+{
+    __shared__ const void *sbase[NREG == 0 ? MAX_LDS_FEATURES : 1];
+    stage_table<NREG>(sbase, tab, nfeat);
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < rows; row += (int64_t)gridDim.x * BLOCK) {
+        int64_t off, loff;
+        row_offsets(R, row, off, loff);
+        T x[NREG > 0 ? NREG : 1];
+        bool masked = false;
+        if (NREG > 0) {
+#pragma unroll
+            for (int j = 0; j < NREG; j++) {
+                x[j] = (T)0;
+                if (j < nfeat) {
+                    const T v = static_cast<const T *>(tab[j])[off];
+                    masked |= (v != v);
+                    x[j] = scaled<T>(v, mean, scale, j);
+                }
+            }
+        } else {
+            for (int f = 0; f < nfeat; f++) {
+                const T v = static_cast<const T *>(sbase[f])[off];
+                masked |= (v != v);
+            }
+        }
+        if (masked) {
+            labels[row] = nan;
+            continue;
+        }
+        double best = INFINITY;
+        int besti = 0;
+        for (int j = 0; j < k; j++) {
+            const double *c = centers + (int64_t)j * nfeat;
+            double d = 0.0;
+            if (NREG > 0) {
+#pragma unroll
+                for (int f = 0; f < NREG; f++) {
+                    if (f < nfeat) {
+                        const double e = (double)x[f] - c[f];
+                        d += e * e;
+                    }
+                }
+            } else {
+                for (int f = 0; f < nfeat; f++) {
+                    const T v = scaled<T>(static_cast<const T *>(sbase[f])[off], mean, scale, f);
+                    const double e = (double)v - c[f];
+                    d += e * e;
+                }
+            }
+            if (d < best) {
+                best = d;
+                besti = j;
+            }
+        }
+        labels[row] = (double)besti;
+    }
+}
+
+// ---- select / gather --------------------------------------------------------------------------
+// One block per ND_AMD_CLASSIFY_BLOCK_ROWS rows; thread t takes rows base + i * BLOCK + t.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void classify_select_kernel(
+    const void *const *tab, int nfeat, RowDims R, int64_t rows, const double *__restrict__ labels,
+    uint8_t *__restrict__ mask, int64_t *__restrict__ block_counts)
+{
+    __shared__ int swave[BLOCK / 64];
+    const int64_t base = (int64_t)blockIdx.x * ND_AMD_CLASSIFY_BLOCK_ROWS;
+    int count = 0;
+    for (int i = 0; i < SELECT_ITEMS; i++) {
+        const int64_t row = base + i * BLOCK + threadIdx.x;
+        if (row >= rows) break;
+        int64_t off, loff;
+        row_offsets(R, row, off, loff);
+        bool m = true;
+        if (labels) {
+            const double l = labels[loff];
+            m = (l == l) && l > 0.0;
+        }
+        if (m) {
+            for (int f = 0; f < nfeat; f++) {
+                const T v = static_cast<const T *>(tab[f])[off];
+                m &= (v == v);
+            }
+        }
+        mask[row] = m ? 1 : 0;
+        count += m ? 1 : 0;
+    }
+    for (int d = 32; d > 0; d >>= 1) count += __shfl_down(count, d, 64);
+    if ((threadIdx.x & 63) == 0) swave[threadIdx.x >> 6] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int w = 0; w < BLOCK / 64; w++) s += swave[w];
+        block_counts[blockIdx.x] = s;
+    }
+}
+
+// exclusive scan of the block counts, in place; one block.  total -> *count
+__global__ __launch_bounds__(BLOCK) void classify_scan_kernel(int64_t *__restrict__ v, int64_t n,
+                                                              int64_t *__restrict__ count)
+{
+    __shared__ int64_t ssum[BLOCK];
+    const int64_t chunk = (n + BLOCK - 1) / BLOCK;
+    const int64_t lo = chunk * threadIdx.x < n ? chunk * threadIdx.x : n;
+    const int64_t hi = lo + chunk < n ? lo + chunk : n;
+    int64_t s = 0;
+    for (int64_t i = lo; i < hi; i++) s += v[i];
+    ssum[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t run = 0;
+        for (int i = 0; i < BLOCK; i++) {
+            const int64_t c = ssum[i];
+            ssum[i] = run;
+            run += c;
+        }
+        *count = run;
+    }
+    __syncthreads();
+    int64_t run = ssum[threadIdx.x];
+    for (int64_t i = lo; i < hi; i++) {
+        const int64_t c = v[i];
+        v[i] = run;
+        run += c;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void classify_gather_kernel(
+    const void *const *tab, int nfeat, RowDims R, int64_t rows, const double *__restrict__ labels,
+    const uint8_t *__restrict__ mask, const int64_t *__restrict__ block_offsets, T *__restrict__ X,
+    double *__restrict__ y)
+{
+    constexpr int WAVES = BLOCK / 64;
+    __shared__ int sseg[SELECT_ITEMS * WAVES];
+    const int64_t base = (int64_t)blockIdx.x * ND_AMD_CLASSIFY_BLOCK_ROWS;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    bool m[SELECT_ITEMS];
+    int before[SELECT_ITEMS];
+#pragma unroll
+    for (int i = 0; i < SELECT_ITEMS; i++) {
+        const int64_t row = base + i * BLOCK + threadIdx.x;
+        m[i] = row < rows && mask[row] != 0;
+        const unsigned long long b = __ballot(m[i]);
+        before[i] = __popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) sseg[i * WAVES + wave] = __popcll(b);
+    }
+    __syncthreads();
+    const int64_t out0 = block_offsets[blockIdx.x];
+#pragma unroll
+    for (int i = 0; i < SELECT_ITEMS; i++) {
+        if (!m[i]) continue;
+        int prefix = 0;
+        for (int s = 0; s < i * WAVES + wave; s++) prefix += sseg[s];
+        const int64_t dst = out0 + prefix + before[i];
+        const int64_t row = base + i * BLOCK + threadIdx.x;
+        int64_t off, loff;
+        row_offsets(R, row, off, loff);
+        for (int f = 0; f < nfeat; f++) X[dst * nfeat + f] = static_cast<const T *>(tab[f])[off];
+        if (y) y[dst] = labels[loff];
+    }
+}
+
+// ---- class statistics and fill ----------------------------------------------------------------
+// class of a label: l in 0 .. n-1 where the label equals the integer l, else n ("other")
+__device__ __forceinline__ int class_of(double l, int n)
+{
+    return (l >= 0.0 && l < (double)n && l == floor(l)) ? (int)l : n;
+}
+
+// MODE 0: n <= 8, per-lane registers, one LDS + global atomic round per block.  MODE 1: n <= 1024,
+// LDS atomics per element.  MODE 2: global atomics per element.
+template <typename T, int MODE>
+__global__ __launch_bounds__(BLOCK) void class_stats_kernel(
+    const T *__restrict__ var, RowDims R, int64_t rows, const double *__restrict__ labels, int n,
+    double *__restrict__ sum, unsigned long long *__restrict__ cnt, unsigned long long *__restrict__ nanc)
+{
+    constexpr int NL = MODE == 0 ? STATS_REG_CLASSES : (MODE == 1 ? STATS_LDS_CLASSES : 1);
+    __shared__ double ssum[NL];
+    __shared__ unsigned long long scnt[NL], snan[NL];
+    if (MODE != 2) {
+        for (int i = threadIdx.x; i < NL; i += BLOCK) {
+            ssum[i] = 0.0;
+            scnt[i] = 0;
+            snan[i] = 0;
+        }
+        __syncthreads();
+    }
+    double rs[STATS_REG_CLASSES];
+    unsigned int rc[STATS_REG_CLASSES], rn[STATS_REG_CLASSES];
+#pragma unroll
+    for (int c = 0; c < STATS_REG_CLASSES; c++) {
+        rs[c] = 0.0;
+        rc[c] = 0;
+        rn[c] = 0;
+    }
+    // a lane sees at most rows / (gridDim * BLOCK) + 1 < 2^32 elements: the host sizes the grid for that
+    for (int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < rows; row += (int64_t)gridDim.x * BLOCK) {
+        int64_t off, loff;
+        row_offsets(R, row, off, loff);
+        const int cls = class_of(labels[loff], n);
+        if (cls >= n) continue;
+        const T v = var[off];
+        const bool isn = (v != v);
+        if (MODE == 0) {
+#pragma unroll
+            for (int c = 0; c < STATS_REG_CLASSES; c++) {
+                const bool hit = (cls == c);
+                rs[c] += (hit && !isn) ? (double)v : 0.0;
+                rc[c] += (hit && !isn) ? 1u : 0u;
+                rn[c] += (hit && isn) ? 1u : 0u;
+            }
+        } else if (MODE == 1) {
+            if (isn) {
+                atomicAdd(&snan[cls], 1ull);
+            } else {
+                atomicAdd(&ssum[cls], (double)v);
+                atomicAdd(&scnt[cls], 1ull);
+            }
+        } else {
+            if (isn) {
+                atomicAdd(&nanc[cls], 1ull);
+            } else {
+                atomicAdd(&sum[cls], (double)v);
+                atomicAdd(&cnt[cls], 1ull);
+            }
+        }
+    }
+    if (MODE == 0) {
+#pragma unroll
+        for (int c = 0; c < STATS_REG_CLASSES; c++) {
+            double s = rs[c];
+            unsigned int a = rc[c], b = rn[c];
+            for (int d = 32; d > 0; d >>= 1) {
+                s += __shfl_down(s, d, 64);
+                a += __shfl_down(a, d, 64);
+                b += __shfl_down(b, d, 64);
+            }
+            if ((threadIdx.x & 63) == 0 && c < n) {
+                atomicAdd(&ssum[c], s);
+                atomicAdd(&scnt[c], (unsigned long long)a);
+                atomicAdd(&snan[c], (unsigned long long)b);
+            }
+        }
+    }
+    if (MODE != 2) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < n && i < NL; i += BLOCK) {
+            if (scnt[i]) {
+                atomicAdd(&sum[i], ssum[i]);
+                atomicAdd(&cnt[i], scnt[i]);
+            }
+            if (snan[i]) atomicAdd(&nanc[i], snan[i]);
+        }
+    }
+}
+
+// out = fill[class] for labels in 0 .. n-1; elsewhere the value, or fill[n] where the value is NaN
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void class_fill_kernel(
+    const T *__restrict__ var, T *__restrict__ out, RowDims R, int64_t rows, const double *__restrict__ labels,
+    int n, const T *__restrict__ fill)
+{
+    for (int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < rows; row += (int64_t)gridDim.x * BLOCK) {
+        int64_t off, loff;
+        row_offsets(R, row, off, loff);
+        const int cls = class_of(labels[loff], n);
+        T v;
+        if (cls < n) {
+            v = fill[cls];
+        } else {
+            v = var[off];
+            if (v != v) v = fill[n];
+        }
+        out[off] = v;
+    }
+}
+
+// ---- host -------------------------------------------------------------------------------------
+// validate, drop dimensions of size 1, merge neighbours that are contiguous in both stride sets
+static int make_dims(const char *who, const int64_t *sizes, const int64_t *strides, const int64_t *lstrides,
+                     RowDims &R, int64_t &rows)
+{
+    if (!sizes || !strides) {
+        set_error("%s: sizes / strides are NULL", who);
+        return ND_AMD_EINVAL;
+    }
+    int64_t n[4], s[4], ls[4];
+    int nd = 0;
+    rows = 1;
+    for (int d = 0; d < 4; d++) {
+        if (sizes[d] < 0) {
+            set_error("%s: bad shape (%lld, %lld, %lld, %lld)", who, (long long)sizes[0], (long long)sizes[1],
+                      (long long)sizes[2], (long long)sizes[3]);
+            return ND_AMD_EINVAL;
+        }
+        if (strides[d] < 0 || (lstrides && lstrides[d] < 0)) {
+            set_error("%s: a stride is negative", who);
+            return ND_AMD_EINVAL;
+        }
+        if (sizes[d] != 0 && rows > (INT64_C(1) << 40) / sizes[d]) {
+            set_error("%s: bad shape: more than 2^40 rows", who);
+            return ND_AMD_EINVAL;
+        }
+        rows *= sizes[d];
+    }
+    for (int d = 0; d < 4; d++) {
+        if (sizes[d] == 1) continue;
+        const int64_t l = lstrides ? lstrides[d] : 0;
+        if (nd > 0 && s[nd - 1] == strides[d] * sizes[d] && ls[nd - 1] == l * sizes[d]) {
+            n[nd - 1] *= sizes[d];
+            s[nd - 1] = strides[d];
+            ls[nd - 1] = l;
+        } else {
+            n[nd] = sizes[d];
+            s[nd] = strides[d];
+            ls[nd] = l;
+            nd++;
+        }
+    }
+    for (; nd < 4; nd++) {
+        n[nd] = 1;
+        s[nd] = 0;
+        ls[nd] = 0;
+    }
+    R.n1 = n[1];
+    R.n2 = n[2];
+    R.n3 = n[3];
+    for (int d = 0; d < 4; d++) {
+        R.s[d] = s[d];
+        R.ls[d] = ls[d];
+    }
+    return ND_AMD_OK;
+}
+
+static int check_table(const char *who, const void *const *feat, int nfeat, int dtype, void *workspace,
+                       size_t workspace_bytes)
+{
+    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
+        set_error("%s: bad dtype %d", who, dtype);
+        return ND_AMD_EINVAL;
+    }
+    if (nfeat < 1 || nfeat > MAX_LDS_FEATURES || !feat) {
+        set_error("%s: needs 1 to %d features, got %d", who, MAX_LDS_FEATURES, nfeat);
+        return ND_AMD_EINVAL;
+    }
+    for (int f = 0; f < nfeat; f++) {
+        if (!feat[f]) {
+            set_error("%s: feature pointer %d is NULL", who, f);
+            return ND_AMD_EINVAL;
+        }
+    }
+    if (!workspace || workspace_bytes < nd_amd_classify_workspace_bytes(nfeat)) {
+        set_error("%s: workspace missing or smaller than nd_amd_classify_workspace_bytes(%d)", who, nfeat);
+        return ND_AMD_EWORKSPACE;
+    }
+    return ND_AMD_OK;
+}
+
+static int grid_for(int64_t rows)
+{
+    const int64_t b = ceil_div(rows, BLOCK);
+    return (int)(b < 8192 ? b : 8192);
+}
+
+template <typename T, int NREG>
+static void launch_forest(int nc_slot, int grid, hipStream_t st, const void *const *tab, int nfeat, const RowDims &R,
+                          int64_t rows, const int4 *nodes, const double *values, const int32_t *roots, int ntrees,
+                          const double *classes, int nclasses, const double *mean, const double *scale,
+                          double *labels, double *proba)
+{
+#define ND_FOREST(NC)                                                                                          \
+    hipLaunchKernelGGL((classify_forest_kernel<T, NREG, NC>), dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, \
+                       nodes, values, roots, ntrees, classes, nclasses, mean, scale, labels, proba)
+    if (nc_slot == 2) ND_FOREST(2);
+    else if (nc_slot == 4) ND_FOREST(4);
+    else ND_FOREST(8);
+#undef ND_FOREST
+}
+
+}  // namespace
+
+extern "C" size_t nd_amd_classify_workspace_bytes(int nfeat)
+{
+    if (nfeat < 1 || nfeat > MAX_LDS_FEATURES) return 0;
+    return ((size_t)nfeat * sizeof(void *) + 255) / 256 * 256;
+}
+
+extern "C" int nd_amd_classify_forest(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                                      const int64_t *strides, const void *nodes, int64_t nnodes,
+                                      const double *values, const int32_t *roots, int ntrees,
+                                      const double *classes, int nclasses, const double *mean,
+                                      const double *scale, double *labels, double *proba, void *workspace,
+                                      size_t workspace_bytes, void *hip_stream)
+{
+    const char *who = "nd_amd_classify_forest";
+    int rc = check_table(who, feat, nfeat, dtype, workspace, workspace_bytes);
+    if (rc != ND_AMD_OK) return rc;
+    RowDims R;
+    int64_t rows;
+    rc = make_dims(who, sizes, strides, nullptr, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (!nodes || !values || !roots || !classes || nnodes < 1 || nnodes > INT32_MAX || ntrees < 1 || nclasses < 1) {
+        set_error("%s: bad forest (%lld nodes, %d trees, %d classes)", who, (long long)nnodes, ntrees, nclasses);
+        return ND_AMD_EINVAL;
+    }
+    if ((mean == nullptr) != (scale == nullptr)) {
+        set_error("%s: scaler needs both mean and scale", who);
+        return ND_AMD_EINVAL;
+    }
+    if (!labels && !proba) {
+        set_error("%s: no output: labels and proba are both NULL", who);
+        return ND_AMD_EINVAL;
+    }
+    if (rows == 0) return ND_AMD_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    ND_HIP_CHECK(hipMemcpyAsync(workspace, feat, (size_t)nfeat * sizeof(void *), hipMemcpyHostToDevice, st));
+    const void *const *tab = (const void *const *)workspace;
+    const int slot = nclasses <= 2 ? 2 : (nclasses <= 4 ? 4 : 8);
+    const int grid = grid_for(rows);
+    const int4 *nd = (const int4 *)nodes;
+    {
+        KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_FOREST, st);
+#define ND_ARGS slot, grid, st, tab, nfeat, R, rows, nd, values, roots, ntrees, classes, nclasses, mean, scale, labels, proba
+        if (dtype == ND_AMD_F32) {
+            if (nfeat <= 4) launch_forest<float, 4>(ND_ARGS);
+            else if (nfeat <= 8) launch_forest<float, 8>(ND_ARGS);
+            else launch_forest<float, 0>(ND_ARGS);
+        } else {
+            if (nfeat <= 4) launch_forest<double, 4>(ND_ARGS);
+            else if (nfeat <= 8) launch_forest<double, 8>(ND_ARGS);
+            else launch_forest<double, 0>(ND_ARGS);
+        }
+#undef ND_ARGS
+    }
+    ND_HIP_CHECK(hipGetLastError());
+    return ND_AMD_OK;
+}
+
+extern "C" int nd_amd_classify_kmeans(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                                      const int64_t *strides, const double *centers, int k, const double *mean,
+                                      const double *scale, double *labels, void *workspace,
+                                      size_t workspace_bytes, void *hip_stream)
+{
+    const char *who = "nd_amd_classify_kmeans";
+    int rc = check_table(who, feat, nfeat, dtype, workspace, workspace_bytes);
+    if (rc != ND_AMD_OK) return rc;
+    RowDims R;
+    int64_t rows;
+    rc = make_dims(who, sizes, strides, nullptr, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (!centers || k < 1 || !labels) {
+        set_error("%s: needs k >= 1 centres and a labels output (k = %d)", who, k);
+        return ND_AMD_EINVAL;
+    }
+    if ((mean == nullptr) != (scale == nullptr)) {
+        set_error("%s: scaler needs both mean and scale", who);
+        return ND_AMD_EINVAL;
+    }
+    if (rows == 0) return ND_AMD_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    ND_HIP_CHECK(hipMemcpyAsync(workspace, feat, (size_t)nfeat * sizeof(void *), hipMemcpyHostToDevice, st));
+    const void *const *tab = (const void *const *)workspace;
+    const int grid = grid_for(rows);
+    {
+        KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_KMEANS, st);
+#define ND_KMEANS(T, NREG)                                                                                      \
+    hipLaunchKernelGGL((classify_kmeans_kernel<T, NREG>), dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, \
+                       centers, k, mean, scale, labels)
+        if (dtype == ND_AMD_F32) {
+            if (nfeat <= 4) ND_KMEANS(float, 4);
+            else if (nfeat <= 8) ND_KMEANS(float, 8);
+            else ND_KMEANS(float, 0);
+        } else {
+            if (nfeat <= 4) ND_KMEANS(double, 4);
+            else if (nfeat <= 8) ND_KMEANS(double, 8);
+            else ND_KMEANS(double, 0);
+        }
+#undef ND_KMEANS
+    }
+    ND_HIP_CHECK(hipGetLastError());
+    return ND_AMD_OK;
+}
+
+extern "C" int nd_amd_classify_select(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                                      const int64_t *strides, const double *labels, const int64_t *label_strides,
+                                      uint8_t *mask, int64_t *block_offsets, int64_t *count, void *workspace,
+                                      size_t workspace_bytes, void *hip_stream)
+{
+    const char *who = "nd_amd_classify_select";
+    int rc = check_table(who, feat, nfeat, dtype, workspace, workspace_bytes);
+    if (rc != ND_AMD_OK) return rc;
+    RowDims R;
+    int64_t rows;
+    rc = make_dims(who, sizes, strides, labels ? label_strides : nullptr, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (!count || (rows > 0 && (!mask || !block_offsets)) || (labels && !label_strides)) {
+        set_error("%s: mask, block_offsets, count (and label_strides with labels) must be given", who);
+        return ND_AMD_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (rows == 0) {
+        ND_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int64_t), st));
+        return ND_AMD_OK;
+    }
+    ND_HIP_CHECK(hipMemcpyAsync(workspace, feat, (size_t)nfeat * sizeof(void *), hipMemcpyHostToDevice, st));
+    const void *const *tab = (const void *const *)workspace;
+    const int64_t nblocks = ceil_div(rows, ND_AMD_CLASSIFY_BLOCK_ROWS);
+    {
+        KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_GATHER, st);
+        if (dtype == ND_AMD_F32)
+            hipLaunchKernelGGL(classify_select_kernel<float>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat,
+                               R, rows, labels, mask, block_offsets);
+        else
+            hipLaunchKernelGGL(classify_select_kernel<double>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat,
+                               R, rows, labels, mask, block_offsets);
+        hipLaunchKernelGGL(classify_scan_kernel, dim3(1), dim3(BLOCK), 0, st, block_offsets, nblocks, count);
+    }
+    ND_HIP_CHECK(hipGetLastError());
+    return ND_AMD_OK;
+}
+
+extern "C" int nd_amd_classify_gather(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                                      const int64_t *strides, const double *labels, const int64_t *label_strides,
+                                      const uint8_t *mask, const int64_t *block_offsets, void *X, double *y,
+                                      void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    const char *who = "nd_amd_classify_gather";
+    int rc = check_table(who, feat, nfeat, dtype, workspace, workspace_bytes);
+    if (rc != ND_AMD_OK) return rc;
+    RowDims R;
+    int64_t rows;
+    rc = make_dims(who, sizes, strides, labels ? label_strides : nullptr, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (rows == 0) return ND_AMD_OK;
+    if (!mask || !block_offsets || !X || (y && !labels) || (labels && !label_strides)) {
+        set_error("%s: mask, block_offsets and X must be given, y needs labels and label_strides", who);
+        return ND_AMD_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    ND_HIP_CHECK(hipMemcpyAsync(workspace, feat, (size_t)nfeat * sizeof(void *), hipMemcpyHostToDevice, st));
+    const void *const *tab = (const void *const *)workspace;
+    const int64_t nblocks = ceil_div(rows, ND_AMD_CLASSIFY_BLOCK_ROWS);
+    {
+        KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_GATHER, st);
+        if (dtype == ND_AMD_F32)
+            hipLaunchKernelGGL(classify_gather_kernel<float>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat,
+                               R, rows, labels, mask, block_offsets, (float *)X, y);
+        else
+            hipLaunchKernelGGL(classify_gather_kernel<double>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat,
+                               R, rows, labels, mask, block_offsets, (double *)X, y);
+    }
+    ND_HIP_CHECK(hipGetLastError());
+    return ND_AMD_OK;
+}
+
+static int class_common(const char *who, const void *var, int dtype, const int64_t *sizes, const int64_t *strides,
+                        const double *labels, const int64_t *label_strides, int nclasses, RowDims &R, int64_t &rows)
+{
+    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
+        set_error("%s: bad dtype %d", who, dtype);
+        return ND_AMD_EINVAL;
+    }
+    if (!label_strides) {
+        set_error("%s: label_strides is NULL", who);
+        return ND_AMD_EINVAL;
+    }
+    int rc = make_dims(who, sizes, strides, label_strides, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (nclasses < 1 || nclasses > (1 << 24)) {
+        set_error("%s: needs 1 to 2^24 classes, got %d", who, nclasses);
+        return ND_AMD_EINVAL;
+    }
+    if (rows > 0 && (!var || !labels)) {
+        set_error("%s: variable or labels pointer is NULL", who);
+        return ND_AMD_EINVAL;
+    }
+    return ND_AMD_OK;
+}
+
+extern "C" int nd_amd_class_stats(const void *var, int dtype, const int64_t *sizes, const int64_t *strides,
+                                  const double *labels, const int64_t *label_strides, int nclasses, double *sum,
+                                  int64_t *count, int64_t *nan_count, void *hip_stream)
+{
+    const char *who = "nd_amd_class_stats";
+    RowDims R;
+    int64_t rows;
+    int rc = class_common(who, var, dtype, sizes, strides, labels, label_strides, nclasses, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (!sum || !count || !nan_count) {
+        set_error("%s: an output pointer is NULL", who);
+        return ND_AMD_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    ND_HIP_CHECK(hipMemsetAsync(sum, 0, sizeof(double) * nclasses, st));
+    ND_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int64_t) * nclasses, st));
+    ND_HIP_CHECK(hipMemsetAsync(nan_count, 0, sizeof(int64_t) * nclasses, st));
+    if (rows == 0) return ND_AMD_OK;
+    // 2048 blocks: one atomic round per block and class, and far fewer than 2^32 elements per lane
+    const int64_t b = ceil_div(rows, BLOCK);
+    const int grid = (int)(b < 2048 ? b : 2048);
+    unsigned long long *c = (unsigned long long *)count, *nn = (unsigned long long *)nan_count;
+    {
+        KernelTimer timer(ND_AMD_KERNEL_CLASS_MEAN, st);
+#define ND_STATS(T, MODE)                                                                                     \
+    hipLaunchKernelGGL((class_stats_kernel<T, MODE>), dim3(grid), dim3(BLOCK), 0, st, (const T *)var, R, rows, \
+                       labels, nclasses, sum, c, nn)
+        if (dtype == ND_AMD_F32) {
+            if (nclasses <= STATS_REG_CLASSES) ND_STATS(float, 0);
+            else if (nclasses <= STATS_LDS_CLASSES) ND_STATS(float, 1);
+            else ND_STATS(float, 2);
+        } else {
+            if (nclasses <= STATS_REG_CLASSES) ND_STATS(double, 0);
+            else if (nclasses <= STATS_LDS_CLASSES) ND_STATS(double, 1);
+            else ND_STATS(double, 2);
+        }
+#undef ND_STATS
+    }
+    ND_HIP_CHECK(hipGetLastError());
+    return ND_AMD_OK;
+}
+
+extern "C" int nd_amd_class_fill(const void *var, void *out, int dtype, const int64_t *sizes,
+                                 const int64_t *strides, const double *labels, const int64_t *label_strides,
+                                 int nclasses, const void *fill, void *hip_stream)
+{
+    const char *who = "nd_amd_class_fill";
+    RowDims R;
+    int64_t rows;
+    int rc = class_common(who, var, dtype, sizes, strides, labels, label_strides, nclasses, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (rows == 0) return ND_AMD_OK;
+    if (!out || !fill) {
+        set_error("%s: out or fill is NULL", who);
+        return ND_AMD_EINVAL;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int grid = grid_for(rows);
+    {
+        KernelTimer timer(ND_AMD_KERNEL_CLASS_MEAN, st);
+        if (dtype == ND_AMD_F32)
+            hipLaunchKernelGGL(class_fill_kernel<float>, dim3(grid), dim3(BLOCK), 0, st, (const float *)var,
+                               (float *)out, R, rows, labels, nclasses, (const float *)fill);
+        else
+            hipLaunchKernelGGL(class_fill_kernel<double>, dim3(grid), dim3(BLOCK), 0, st, (const double *)var,
+                               (double *)out, R, rows, labels, nclasses, (const double *)fill);
+    }
+    ND_HIP_CHECK(hipGetLastError());
+    return ND_AMD_OK;
+}

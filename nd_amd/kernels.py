@@ -926,3 +926,205 @@ def rgb_compose(channels, limits=None, vmin=None, vmax=None, mask=None):
         for t in num + [d for d in den if d is not None] + [x for x in (limits, mask) if x is not None]:
             t.record_stream(stream)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Pixel classification (nd/classify.py)
+# ---------------------------------------------------------------------------
+def _dims4(values, name):
+    values = [int(v) for v in values]
+    if len(values) > 4:
+        raise ValueError('%s: at most four row dimensions, got %d' % (name, len(values)))
+    return values
+
+
+def _feature_table(features, sizes, strides, name):
+    """features: device tensors of one dtype and device, one per feature; element (0, .., 0) of feature f is
+    features[f]'s first element and row (i0, .., i3) lies at i . strides from it (the caller passes views whose
+    data_ptr() is that element).  -> (ctypes pointer array, sizes[4], strides[4], workspace tensor)."""
+    features = list(features)
+    if not features:
+        raise ValueError('%s: no features' % name)
+    if len(features) > _lib.CLASSIFY_MAX_FEATURES:
+        raise ValueError('%s: at most %d features, got %d' % (name, _lib.CLASSIFY_MAX_FEATURES, len(features)))
+    first = features[0]
+    for i, t in enumerate(features):
+        _require_cuda(t, '%s: feature %d' % (name, i))
+        if t.dtype != first.dtype or t.device != first.device:
+            raise ValueError('%s: the features must share dtype and device' % name)
+    sizes, strides = _dims4(sizes, name), _dims4(strides, name)
+    if len(sizes) != len(strides) or any(s < 0 for s in strides) or any(n < 0 for n in sizes):
+        raise ValueError('%s: sizes and strides must pair up and not be negative' % name)
+    pad = 4 - len(sizes)
+    sizes, strides = [1] * pad + sizes, [0] * pad + strides
+    ptrs = (C.c_void_p * len(features))(*[t.data_ptr() for t in features])
+    nbytes = _lib.lib().nd_amd_classify_workspace_bytes(len(features))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=first.device)
+    return ptrs, _lib.i64_array(sizes), _lib.i64_array(strides), ws
+
+
+def _scaler_args(mean, scale, nfeat, dev, name):
+    if (mean is None) != (scale is None):
+        raise ValueError('%s: scaler needs both mean and scale' % name)
+    if mean is None:
+        return None, None
+    out = []
+    for v in (mean, scale):
+        v = torch.as_tensor(v, dtype=torch.float64).to(dev).contiguous()
+        if v.numel() != nfeat:
+            raise ValueError('%s: the scaler has %d entries for %d features' % (name, v.numel(), nfeat))
+        out.append(v)
+    return out
+
+
+def _record(tensors, dev):
+    stream = torch.cuda.current_stream(dev)
+    for t in tensors:
+        if t is not None:
+            t.record_stream(stream)
+
+
+def classify_forest(features, sizes, strides, nodes, values, roots, classes, mean=None, scale=None,
+                    want_labels=True, want_proba=False):
+    """clf.predict / clf.predict_proba of a decision forest over rows that are never stacked
+    (nd/classify.py:222-241; include/nd_amd.h nd_amd_classify_forest).  nodes: uint8 device tensor of
+    16-byte packed nodes (classify.ForestModel.packed), values float64 (n, classes), roots int32, classes
+    float64, all on the features' device.  -> (labels float64 sizes | None, proba float64 sizes + (classes,)
+    | None); NaN for rows with a NaN feature."""
+    name = 'classify_forest'
+    ptrs, sz, st, ws = _feature_table(features, sizes, strides, name)
+    dev = features[0].device
+    ncls, ntrees, nnodes = int(classes.numel()), int(roots.numel()), int(nodes.numel()) // 16
+    for t, dt, nm in ((nodes, torch.uint8, 'nodes'), (values, torch.float64, 'values'),
+                      (roots, torch.int32, 'roots'), (classes, torch.float64, 'classes')):
+        if not (torch.is_tensor(t) and t.device == dev and t.dtype == dt and t.is_contiguous()):
+            raise ValueError('%s: %s must be a contiguous %s tensor on %s' % (name, nm, dt, dev))
+    if values.dim() != 2 or values.shape[1] != ncls or nodes.numel() % 16 or nodes.data_ptr() % 16:
+        raise ValueError('%s: values must be (leaves, %d) and nodes 16-byte records' % (name, ncls))
+    if not (want_labels or want_proba):
+        raise ValueError('%s: nothing to compute' % name)
+    shape = tuple(int(n) for n in sizes)
+    with torch.cuda.device(dev):
+        mean, scale = _scaler_args(mean, scale, len(features), dev, name)
+        labels = torch.empty(shape, dtype=torch.float64, device=dev) if want_labels else None
+        proba = torch.empty(shape + (ncls,), dtype=torch.float64, device=dev) if want_proba else None
+        _lib.check(_lib.lib().nd_amd_classify_forest(
+            ptrs, len(features), _DT[features[0].dtype], sz, st, _ptr(nodes), nnodes, _ptr(values), _ptr(roots),
+            ntrees, _ptr(classes), ncls, _ptr(mean), _ptr(scale), _ptr(labels), _ptr(proba), _ptr(ws), ws.numel(),
+            _stream_ptr(dev)))
+        _record(list(features) + [nodes, values, roots, classes, mean, scale, ws], dev)
+    return labels, proba
+
+
+def classify_kmeans(features, sizes, strides, centers, mean=None, scale=None):
+    """KMeans.predict over unstacked rows: the first nearest centre in float64 (nd_amd_classify_kmeans).
+    centers: float64 (k, features) device tensor.  -> float64 labels of shape sizes, NaN for masked rows."""
+    name = 'classify_kmeans'
+    ptrs, sz, st, ws = _feature_table(features, sizes, strides, name)
+    dev = features[0].device
+    if not (torch.is_tensor(centers) and centers.device == dev and centers.dtype == torch.float64
+            and centers.dim() == 2 and centers.shape[1] == len(features) and centers.shape[0] >= 1):
+        raise ValueError('%s: centers must be a float64 (k, %d) tensor on %s' % (name, len(features), dev))
+    centers = centers.contiguous()
+    with torch.cuda.device(dev):
+        mean, scale = _scaler_args(mean, scale, len(features), dev, name)
+        labels = torch.empty(tuple(int(n) for n in sizes), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().nd_amd_classify_kmeans(
+            ptrs, len(features), _DT[features[0].dtype], sz, st, _ptr(centers), int(centers.shape[0]), _ptr(mean),
+            _ptr(scale), _ptr(labels), _ptr(ws), ws.numel(), _stream_ptr(dev)))
+        _record(list(features) + [centers, mean, scale, ws], dev)
+    return labels
+
+
+def _label_args(labels, label_strides, sizes, dev, name):
+    nd = len(sizes)
+    if labels is None:
+        return None, None
+    if not (torch.is_tensor(labels) and labels.device == dev and labels.dtype == torch.float64):
+        raise ValueError('%s: labels must be a float64 tensor on %s' % (name, dev))
+    ls = _dims4(label_strides, name)
+    if len(ls) != nd or any(s < 0 for s in ls):
+        raise ValueError('%s: one non-negative label stride per row dimension' % name)
+    reach = sum((int(n) - 1) * s for n, s in zip(sizes, ls)) if all(int(n) > 0 for n in sizes) else -1
+    if reach >= labels.numel():
+        raise ValueError('%s: the label strides reach element %d of %d labels' % (name, reach, labels.numel()))
+    return labels, _lib.i64_array([0] * (4 - nd) + ls)
+
+
+def classify_gather(features, sizes, strides, labels=None, label_strides=None):
+    """The training rows of make_Xy (nd/classify.py:164-178): rows whose label is > 0 and not NaN (all rows
+    without labels) and whose features hold no NaN, compacted in row order.  labels: float64 device tensor
+    read at i . label_strides.  -> (X (n, features) of the data type, y float64 (n,) | None, mask uint8
+    (rows,)).  Synchronises once, to learn n."""
+    name = 'classify_gather'
+    ptrs, sz, st, ws = _feature_table(features, sizes, strides, name)
+    dev = features[0].device
+    lab, ls = _label_args(labels, label_strides, list(sizes), dev, name)
+    rows = 1
+    for n in sizes:
+        rows *= int(n)
+    nblocks = -(-rows // _lib.CLASSIFY_BLOCK_ROWS)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        mask = torch.empty(rows, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(max(nblocks, 1), dtype=torch.int64, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        args = (ptrs, len(features), _DT[features[0].dtype], sz, st, _ptr(lab), ls)
+        _lib.check(L.nd_amd_classify_select(*args, _ptr(mask), _ptr(offsets), _ptr(count), _ptr(ws), ws.numel(),
+                                            _stream_ptr(dev)))
+        n = int(count.item())
+        X = torch.empty((n, len(features)), dtype=features[0].dtype, device=dev)
+        y = torch.empty(n, dtype=torch.float64, device=dev) if lab is not None else None
+        if n:
+            _lib.check(L.nd_amd_classify_gather(*args, _ptr(mask), _ptr(offsets), _ptr(X), _ptr(y), _ptr(ws),
+                                                ws.numel(), _stream_ptr(dev)))
+        _record(list(features) + [lab, ws, offsets], dev)
+    return X, y, mask
+
+
+def _class_args(var, labels, label_strides, name):
+    _require_cuda(var, name + ': var')
+    order = sorted(range(var.dim()), key=lambda d: -var.stride(d))
+    if var.dim() > 4:
+        raise ValueError('%s: at most four dimensions' % name)
+    lab, _ = _label_args(labels, label_strides, list(var.shape), var.device, name)
+    pad = 4 - var.dim()
+    sizes = [1] * pad + [var.shape[d] for d in order]
+    strides = [0] * pad + [var.stride(d) for d in order]
+    ls = [0] * pad + [int(label_strides[d]) for d in order]
+    return lab, _lib.i64_array(sizes), _lib.i64_array(strides), _lib.i64_array(ls)
+
+
+def class_stats(var, labels, label_strides, nclasses):
+    """Per class l in 0 .. nclasses-1 of `var` under labels read at i . label_strides (one stride per dimension
+    of var, 0 = broadcast): float64 sum and int64 count of the non-NaN values, int64 count of the NaN values
+    (nd_amd_class_stats; the statistics class_mean needs, nd/classify.py:36-44).  Device tensors."""
+    name = 'class_stats'
+    lab, sz, st, ls = _class_args(var, labels, label_strides, name)
+    dev = var.device
+    with torch.cuda.device(dev):
+        out = [torch.empty(int(nclasses), dtype=dt, device=dev) for dt in (torch.float64, torch.int64, torch.int64)]
+        _lib.check(_lib.lib().nd_amd_class_stats(_ptr(var), _DT[var.dtype], sz, st, _ptr(lab), ls, int(nclasses),
+                                                 _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream_ptr(dev)))
+        _record([var, lab], dev)
+    return tuple(out)
+
+
+def class_fill(var, labels, label_strides, fill):
+    """A new tensor like var: fill[l] where the label is l in 0 .. len(fill)-2, elsewhere var's value, or
+    fill[-1] where that is NaN (nd_amd_class_fill).  var must be dense; fill: device tensor of var's dtype."""
+    name = 'class_fill'
+    lab, sz, st, ls = _class_args(var, labels, label_strides, name)
+    dev = var.device
+    if not (torch.is_tensor(fill) and fill.device == dev and fill.dtype == var.dtype and fill.dim() == 1
+            and fill.numel() >= 2):
+        raise ValueError('%s: fill must be a 1-D %s tensor on %s' % (name, var.dtype, dev))
+    fill = fill.contiguous()
+    with torch.cuda.device(dev):
+        out = torch.empty_like(var)
+        if out.stride() != var.stride():
+            raise ValueError('%s: var must be a dense tensor (call .contiguous())' % name)
+        _lib.check(_lib.lib().nd_amd_class_fill(_ptr(var), _ptr(out), _DT[var.dtype], sz, st, _ptr(lab), ls,
+                                                int(fill.numel()) - 1, _ptr(fill), _stream_ptr(dev)))
+        _record([var, lab, fill], dev)
+    return out

@@ -1,0 +1,136 @@
+"""Classification timing on the headline stack (k x n x n, four variables from nd_amd.synth, device resident):
+
+    python tools/bench_classify.py [--k 24] [--n 4096] [--reps 5] [--trees 20] [--json out.json]
+
+  forest      Classifier(RandomForestClassifier(trees)).predict, fitted by scikit-learn on 10 % of a
+              256 x 256 crop (labels: terciles of the crop's C11), at feature_dims=[] (k n^2 rows x 4 features)
+              and feature_dims=['time'] (n^2 rows x 4 k features); node count and depth are recorded
+  kmeans      Classifier(KMeans(3)).predict at feature_dims=[]
+  class_mean  class_mean of the stack under the forest's (y, x) labels
+
+Every case: device events around whole calls, one warm-up, min and median of --reps; the kernels' own time from
+the library's event timers (KernelTimer).  Yardstick, measured in the same run: the reference path on the host,
+scikit-learn's predict on the (rows, features) matrix of a crop at 16 threads (n_jobs=16 for the forest), as
+rows per second.  Building that matrix is not counted in the host's favour."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+VARS = ('C11', 'C12re', 'C12im', 'C22')
+
+
+def timed(fn, reps):
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = []
+    for _ in range(reps):
+        s.record()
+        fn()
+        e.record()
+        e.synchronize()
+        out.append(s.elapsed_time(e))
+    return min(out), sorted(out)[len(out) // 2]
+
+
+def kernel_ms(fn, name):
+    from nd_amd import _lib
+    _lib.timing_enable(64)
+    fn()
+    per = _lib.timing_collect()
+    _lib.timing_enable(0)
+    return sum(ms for n, ms in per if n == name)
+
+
+def host_rate(predict, X, reps=3):
+    predict(X[:1000])
+    best = None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        predict(X)
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+    return X.shape[0] / best
+
+
+def main():
+    import numpy as np
+    import torch
+    from sklearn.cluster import KMeans
+    from sklearn.ensemble import RandomForestClassifier
+    from nd_amd import classify, synth, xr_lite
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--k', type=int, default=24)
+    ap.add_argument('--n', type=int, default=4096)
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--trees', type=int, default=20)
+    ap.add_argument('--crop', type=int, default=256)
+    ap.add_argument('--host-rows', type=int, default=2000000)
+    ap.add_argument('--json', default=None)
+    a = ap.parse_args()
+    dev = torch.device('cuda:0')
+    k, n, crop = a.k, a.n, min(a.crop, a.n)
+    stack = synth.wishart_c2_stack(k, n, n, device=dev)
+    dims = ('time', 'y', 'x')
+    ds = xr_lite.Dataset()
+    small = xr_lite.Dataset()
+    for i, v in enumerate(VARS):
+        ds[v] = (dims, stack[i])
+        small[v] = (dims, stack[i][:, :crop, :crop])
+    rng = np.random.default_rng(0)
+    c11 = stack[0][:, :crop, :crop].mean(0).cpu().numpy()
+    truth = 1 + (c11 > np.quantile(c11, 1 / 3)).astype(np.int64) + (c11 > np.quantile(c11, 2 / 3))
+    train = np.where(rng.random(truth.shape) < 0.1, truth, 0)
+    rows = []
+
+    def record(case, nrows, nfeat, ms, kms, host, extra=None):
+        row = dict(case=case, rows=nrows, features=nfeat, ms_min=ms[0], ms_median=ms[1], kernel_ms=kms,
+                   device_rows_per_s=nrows / (ms[0] * 1e-3), host_rows_per_s=host,
+                   device_over_host=nrows / (ms[0] * 1e-3) / host if host else None)
+        row.update(extra or {})
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+
+    labels_yx = None
+    for fdims in ([], ['time']):
+        c = classify.Classifier(RandomForestClassifier(a.trees, random_state=0, n_jobs=16), feature_dims=fdims)
+        c.fit(small, train)
+        model = classify.ForestModel.from_sklearn(c.clf)
+        Xh = c.make_Xy(small)[0]
+        reps_h = max(1, a.host_rows // Xh.shape[0])
+        Xh = np.concatenate([Xh] * reps_h)[:a.host_rows]
+        host = host_rate(c.clf.predict, Xh)
+        ms = timed(lambda: c.predict(ds), a.reps)
+        kms = kernel_ms(lambda: c.predict(ds), 'classify_forest')
+        nrows = n * n * (1 if fdims else k)
+        record('forest feature_dims=%s' % fdims, nrows, len(VARS) * (k if fdims else 1), ms, kms, host,
+               dict(trees=a.trees, nodes=int(model.feature.size), depth=model.depth(),
+                    forest_mb=model.feature.size * (16 + 8 * model.n_classes) / 1e6))
+        if fdims:
+            labels_yx = c.predict(ds)
+    c = classify.Classifier(KMeans(3, n_init=2, random_state=0))
+    c.fit(small)
+    Xh = c.make_Xy(small)[0]
+    Xh = np.concatenate([Xh] * max(1, a.host_rows // Xh.shape[0]))[:a.host_rows]
+    host = host_rate(c.clf.predict, Xh)
+    ms = timed(lambda: c.predict(ds), a.reps)
+    record('kmeans k=3 feature_dims=[]', k * n * n, len(VARS), ms, kernel_ms(lambda: c.predict(ds), 'classify_kmeans'),
+           host)
+    lab = xr_lite.DataArray(labels_yx.values - 1, ('y', 'x'))
+    ms = timed(lambda: classify.class_mean(ds, lab), a.reps)
+    record('class_mean 3 classes', len(VARS) * k * n * n, 1, ms, kernel_ms(lambda: classify.class_mean(ds, lab), 'class_mean'),
+           None)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        json.dump(dict(k=k, n=n, threads=int(os.environ.get('OMP_NUM_THREADS', '0') or 0), rows=rows),
+                  open(a.json, 'w'), indent=1)
+
+
+if __name__ == '__main__':
+    main()
