@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/nd_amd.h"
 
@@ -32,5 +33,18 @@ struct KernelTimer {
 };
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// A library switch from the environment (README.md lists them all); `def` where it is unset.  Callers keep the
+// value in a `static const`: one look per process.
+static inline int env_int(const char *name, int def)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : def;
+}
+static inline double env_double(const char *name, double def)
+{
+    const char *e = getenv(name);
+    return e ? atof(e) : def;
+}
 
 }  // namespace nd_amd

@@ -17,14 +17,12 @@
 
 #include "common.hpp"
 
+namespace nd_amd {
+
 // cache policy of the window kernels' 16-byte output stores: 2 = non-temporal (written once, never read
 // back by the kernel; boxcar 3 x 3 / 5 x 5 on 24 x 4096^2: 0.632 / 0.640 -> 0.612 / 0.620 ms, the fused
 // Gaussian unchanged).  Non-temporal LOADS of the rows measured slower (0.611 -> 0.623 ms).
-#ifndef ND_CORR_ST_AUX
-#define ND_CORR_ST_AUX 2
-#endif
-
-namespace nd_amd {
+constexpr int kStoreAux = 2;
 
 constexpr int kTapsArgs = 128;   // taps that travel as a kernel argument
 
@@ -632,7 +630,7 @@ __global__ void __launch_bounds__(256, (K == 3 ? 6 : (K == 5 ? 4 : 2))) correlat
                     if (writer) {
                         if (store_vec) {
                             const f32x4 o = {(float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]};
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rout, x * 4, ooff, ND_CORR_ST_AUX);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rout, x * 4, ooff, kStoreAux);
                         } else {
 #pragma unroll
                             for (int c = 0; c < 4; ++c)
@@ -661,8 +659,7 @@ int try_roll<float>(const void *in, void *out, const int64_t dims[4], const int6
                     const int64_t so[4], int64_t ntaps, const int64_t *offsets,
                     const double *weights, int mode, hipStream_t stream)
 {
-    static const bool disabled = getenv("ND_AMD_NO_ROLL") != nullptr || getenv("ND_AMD_NO_TILED") != nullptr;
-    if (disabled || mode == ND_AMD_MODE_CONSTANT) return 0;
+    if (mode == ND_AMD_MODE_CONSTANT) return 0;
     if (ntaps != 9 && ntaps != 25 && ntaps != 49) return 0;
     const int K = ntaps == 9 ? 3 : (ntaps == 25 ? 5 : 7);
     if (si[3] != 1 || so[3] != 1 || si[2] < 0 || so[2] < 0) return 0;
@@ -743,8 +740,7 @@ static int try_tiled(const void *in, void *out, const int64_t dims[4], const int
                      const int64_t so[4], int64_t ntaps, const int64_t *offsets,
                      const double *weights, int mode, double cval, hipStream_t stream)
 {
-    static const bool disabled = getenv("ND_AMD_NO_TILED") != nullptr;
-    if (disabled || ntaps < 1) return 0;
+    if (ntaps < 1) return 0;
     if (si[3] != 1 || so[3] != 1) return 0;
     int64_t ymin = 0, ymax = 0, xmin = 0, xmax = 0, tmin = 0, tmax = 0;
     for (int64_t t = 0; t < ntaps; ++t) {
@@ -1281,8 +1277,7 @@ static int correlate1d_impl(const void *in, void *out, const int64_t dims[4], co
         }
     }
     if (a.total == 0) return ND_AMD_OK;
-    static const bool no_tiled = getenv("ND_AMD_NO_TILED") != nullptr;
-    if (!no_tiled && n <= kT1MaxW && si[3] == 1 && so[3] == 1) {
+    if (n <= kT1MaxW && si[3] == 1 && so[3] == 1) {
         // rows = the filtered axis, or (filter along the contiguous axis) axis 2; the two
         // remaining axes form the batch
         Corr1dTiledArgs<T> t;
@@ -1623,7 +1618,7 @@ __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs
                         if constexpr (sizeof(T) == 4) {
                             if (store_vec) {
                                 const f32x4 o4 = {res[0], res[1], res[2], res[3]};
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o4), rout, x * 4, ooff, ND_CORR_ST_AUX);
+                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o4), rout, x * 4, ooff, kStoreAux);
                             } else {
 #pragma unroll
                                 for (int c = 0; c < 4; ++c)
@@ -1634,8 +1629,8 @@ __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs
                         } else {
                             if (store_vec) {
                                 const f64x2 lo = {res[0], res[1]}, hi = {res[2], res[3]};
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), rout, x * 8, ooff, ND_CORR_ST_AUX);
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), rout, x * 8 + 16, ooff, ND_CORR_ST_AUX);
+                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), rout, x * 8, ooff, kStoreAux);
+                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), rout, x * 8 + 16, ooff, kStoreAux);
                             } else {
 #pragma unroll
                                 for (int c = 0; c < 4; ++c)
@@ -1686,14 +1681,11 @@ extern "C" int nd_amd_correlate1d_yx(const void *in, void *out, int dtype, const
         set_error("nd_amd_correlate1d_yx: null or aliased data pointers");
         return ND_AMD_EINVAL;
     }
-    static const bool disabled = getenv("ND_AMD_NO_ROLL") != nullptr || getenv("ND_AMD_NO_TILED") != nullptr;
     const int R = nweights / 2;
     const int64_t *si = in_strides, *so = out_strides;
     const int64_t ny = dims[2], nx = dims[3];
     const int64_t es = dtype == ND_AMD_F64 ? 8 : 4;
-    static const bool no_f64 = getenv("ND_AMD_YX_F64") != nullptr && atoi(getenv("ND_AMD_YX_F64")) == 0;
-    bool fits = !disabled && (dtype == ND_AMD_F32 || (dtype == ND_AMD_F64 && !no_f64)) && mode != ND_AMD_MODE_CONSTANT &&
-                (nweights & 1) &&
+    bool fits = (dtype == ND_AMD_F32 || dtype == ND_AMD_F64) && mode != ND_AMD_MODE_CONSTANT && (nweights & 1) &&
                 R >= 1 && R <= 8 && R != 7 && corr1d_symmetric(weights_y, nweights) &&
                 corr1d_symmetric(weights_x, nweights) && si[3] == 1 && so[3] == 1 && si[2] >= 0 &&
                 so[2] >= 0 && ny <= 0x3fffffff && nx <= 0x3fffffff && nx >= 8 &&
@@ -1721,8 +1713,6 @@ extern "C" int nd_amd_correlate1d_yx(const void *in, void *out, int dtype, const
     // rows per wave: the 2 R rows read ahead of the first output are re-read by the next chunk
     int64_t rpc = R >= 3 ? 128 : 64;
     while (rpc > 16 && (int64_t)nstrips * ceil_div(ny, rpc) * nb < 12288) rpc /= 2;
-    static const int rpc_env = getenv("ND_AMD_YX_RPC") ? atoi(getenv("ND_AMD_YX_RPC")) : 0;
-    if (rpc_env > 0) rpc = rpc_env;
     const int nchunks = (int)ceil_div(ny, rpc);
     const int64_t nwaves = (int64_t)nstrips * nchunks * nb;
     const int64_t nblocks = ceil_div(nwaves, 4);
@@ -1771,22 +1761,14 @@ extern "C" int nd_amd_correlate1d_yx(const void *in, void *out, int dtype, const
             a.in = static_cast<const float *>(in);
             a.out = static_cast<float *>(out);
             fill(a);
-            static const int dwin_env = getenv("ND_AMD_YX_DWIN") ? atoi(getenv("ND_AMD_YX_DWIN")) : -1;
-            // measured on 24 x 4096 x 4096 (tools/exp_gauss_yx.py): the float64 window wins from radius 6
-            // (sigma 1.5: 0.90 -> 0.85 ms, sigma 2: 1.14 -> 0.98 ms) and loses below (registers: 118 vs 82
-            // at radius 4)
-            const bool dw = dwin_env >= 0 ? dwin_env != 0 : R >= 6;
+            // measured on 24 x 4096 x 4096: the float64 window wins from radius 6 (sigma 1.5: 0.90 -> 0.85 ms,
+            // sigma 2: 1.14 -> 0.98 ms) and loses below (registers: 118 vs 82 at radius 4)
 #define ND_YX(RR)                                                                                  \
-    case RR:                                                                                       \
-        if (dw) hipLaunchKernelGGL((correlate1d_yx_kernel<float, RR, true>), grid, block, 0, stream, a);   \
-        else hipLaunchKernelGGL((correlate1d_yx_kernel<float, RR, false>), grid, block, 0, stream, a);     \
-        break;
+    case RR: hipLaunchKernelGGL((correlate1d_yx_kernel<float, RR, false>), grid, block, 0, stream, a); break;
             switch (R) {
-                ND_YX(1) ND_YX(2) ND_YX(3) ND_YX(4) ND_YX(5) ND_YX(6)
-            default:
-                if (dw) hipLaunchKernelGGL((correlate1d_yx_kernel<float, 8, true>), grid, block, 0, stream, a);
-                else hipLaunchKernelGGL((correlate1d_yx_kernel<float, 8, false>), grid, block, 0, stream, a);
-                break;
+                ND_YX(1) ND_YX(2) ND_YX(3) ND_YX(4) ND_YX(5)
+            case 6: hipLaunchKernelGGL((correlate1d_yx_kernel<float, 6, true>), grid, block, 0, stream, a); break;
+            default: hipLaunchKernelGGL((correlate1d_yx_kernel<float, 8, true>), grid, block, 0, stream, a); break;
             }
 #undef ND_YX
         }

@@ -873,16 +873,12 @@ static bool launch_stream3(const NlmTiledArgs &a, int64_t nb, hipStream_t stream
         const size_t nw = ((2 * (size_t)R + 4) + 3) / 4 * 4;
         return 2 * (size_t)(kWinTY + 2 * R) * (kWinTX - 4 + nw) * sizeof(float);
     };
-    // 512 threads x (2 x 4) outputs by default; the 256-thread form (4 x 4 outputs per thread, half
-    // the waves) measures the same to 1 % -- the kernel is bound by VALU issue, not by latency
+    // 512 threads x (2 x 4) outputs; a 256-thread form (4 x 4 outputs per thread, half the waves)
+    // measured the same to 1 % -- the kernel is bound by VALU issue, not by latency
     // (profiles/r02_nlmeans_window_pmc.txt)
-    static const bool oy4 = getenv("ND_AMD_NLM_S3_OY4") != nullptr;
     const dim3 grid((unsigned)nb);
 #define ND_S3(RR)                                                                                          \
-    if (oy4)                                                                                               \
-        hipLaunchKernelGGL((nlmeans_window_stream3_kernel<RR, 4, 3>), grid, dim3(256), lds(RR), stream, a); \
-    else                                                                                                   \
-        hipLaunchKernelGGL((nlmeans_window_stream3_kernel<RR, 2, 4>), grid, dim3(512), lds(RR), stream, a); \
+    hipLaunchKernelGGL((nlmeans_window_stream3_kernel<RR, 2, 4>), grid, dim3(512), lds(RR), stream, a); \
     return true
     switch (a.r1) {
     case 1: ND_S3(1);
@@ -946,9 +942,6 @@ template <int F, int V>
 __device__ __forceinline__ bool nlm_own_patch_nan(const float *lds, int plane, int cols, int py, int px)
 {
     bool nan = false;
-#ifdef ND_NO_OWN_NAN
-    return false;
-#endif
     for (int i = -F; i <= F; ++i)
         for (int j = -F; j <= F; ++j)
 #pragma unroll
@@ -1192,12 +1185,9 @@ __device__ __forceinline__ float dpp_from_next(float x)      // lane i <- lane i
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x130, 0xF, 0xF, true));
 }
 
-#ifndef ND_PATCH2_TYW1
-#define ND_PATCH2_TYW1 8
-#endif
 template <int V>
 struct Patch2Rows {
-    static constexpr int TYW = (V == 1) ? ND_PATCH2_TYW1 : 4;      // rows per thread
+    static constexpr int TYW = (V == 1) ? 8 : 4;      // rows per thread
 };
 template <int F>
 struct Patch2Geom {
@@ -1250,14 +1240,8 @@ constexpr int kPatch2Margin = 16;
 // 53 -> 46 ms; 4 waves gain nothing more.  Several variables: 2 (3 spills inside the loop:
 // 4 variables 34 -> 59 ms); unbounded, the n_eff forms pass 256 registers and run one wave per
 // SIMD (58 -> 93 ms).  Measured with tools/exp_nlm_cc.py.
-#ifndef ND_P2_W1
-#define ND_P2_W1 3
-#endif
-#ifndef ND_P2_WV
-#define ND_P2_WV 2
-#endif
 template <int F, int V, int TYW, bool NEFF, int MC>
-__global__ void __launch_bounds__(256, V == 1 ? ND_P2_W1 : ND_P2_WV) nlmeans_patch2_kernel(const NlmTiledArgs a)
+__global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(const NlmTiledArgs a)
 {
     extern __shared__ __align__(16) unsigned char nd_smem_n[];
     constexpr int HL = Patch2Geom<F>::HL, TX = Patch2Geom<F>::TX, TY = 4 * TYW;
@@ -1940,8 +1924,6 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
                          const int64_t toff[3], const int64_t clo[3], const int64_t chi[3],
                          hipStream_t stream)
 {
-    static const bool disabled = getenv("ND_AMD_NO_TILED") != nullptr;
-    if (disabled) return 0;
     // float64 arrays: the uniform-weight window kernel only (the reference-compatible mode with
     // f > 0); everything else of float64 stays in the per-pixel kernel
     const bool f64 = dtype != ND_AMD_F32;
@@ -1993,9 +1975,7 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
         if (a.r1 > 16) return 0;
         a.tiles_x = (int)ceil_div(ex, kWinTX);
         a.tiles_y = (int)ceil_div(ey, kWinTY);
-        static const bool no_roll = getenv("ND_AMD_NLM_NOROLL") != nullptr;
-        static const bool no_stream3 = getenv("ND_AMD_NLM_NOSTREAM3") != nullptr;
-        if (!f64 && !no_roll && !no_stream3 && rz == 1 && a.r0 == a.r1 && a.r1 >= 1 && a.r1 <= 5 &&
+        if (!f64 && rz == 1 && a.r0 == a.r1 && a.r1 >= 1 && a.r1 <= 5 &&
             a.si0 >= 0 && (a.N0 * a.si0 + a.N1) * 4 < 0x7fffffffLL) {
             const int64_t nbr = (int64_t)a.tiles_x * a.tiles_y * nvars;
             if (nbr <= 0x7fffffffLL) {
@@ -2003,7 +1983,7 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
                 if (launch_stream3(a, nbr, stream)) return 1;
             }
         }
-        if (!f64 && !no_roll && a.r0 <= kRollR0Max && a.r1 <= 10) {
+        if (!f64 && a.r0 <= kRollR0Max && a.r1 <= 10) {
             const size_t nw = ((2 * (size_t)a.r1 + 4) + 3) / 4 * 4;
             const size_t lds_r = (size_t)(2 * rz + 1) * (kWinTY + 2 * a.r0) * (kWinTX - 4 + nw) * sizeof(float);
             const int64_t nbr = (int64_t)a.tiles_x * a.tiles_y * nvars;
@@ -2050,10 +2030,9 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
     if (rz != 0 || fz != 0) {
         // a window along the third axis (round 6): nlmeans_patch3_kernel -- the visiting order is the
         // reference's only where that axis is the outermost filter dimension (layout B)
-        static const bool no_patch3 = getenv("ND_AMD_NLM_NOPATCH3") != nullptr;
         const uint32_t F0z = (patch_mode == 1) ? f[A0] : 0u, F1z = (patch_mode == 1) ? f[A1] : 0u;
         const uint32_t FZz = (patch_mode == 1) ? fz : 0u;
-        if (no_patch3 || A2 != 0 || f64 || nvars > 4) return 0;
+        if (A2 != 0 || f64 || nvars > 4) return 0;
         if (patch_mode == 0 && (f[A0] != 0 || f[A1] != 0 || fz != 0)) return 0;
         // (3 x 3 patches, or none, in the plane; 5 x 5 and larger: the per-pixel kernel -- every instantiation costs
         //  build time, and no caller of the reference uses them with a window along time)
@@ -2092,7 +2071,7 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
     // (round 6: patches of 9 x 9 and 11 x 11 -- f = 4, 5 -- in the one-column-per-lane kernel, whose sliding sums are
     //  generic in F; before, they took the per-pixel kernel: r = 5, f = 4 on 4 x 1024 x 2048 177 ms)
     if (F0 != F1 || F0 > 5 || nvars > 4) return 0;
-    static const bool no_patch2 = getenv("ND_AMD_NLM_PATCH1") != nullptr;
+    static const bool no_patch2 = env_int("ND_AMD_NLM_PATCH1", 0) != 0;      // 1: one column per lane for every patch size
     if (!no_patch2 && F0 >= 1 && F0 <= 3) {
         // cross-lane form: two columns per lane
         const int hl = (F0 == 3) ? 2 : 1, tx2 = 2 * (64 - 2 * hl), tyw2 = (nvars == 1) ? Patch2Rows<1>::TYW : Patch2Rows<2>::TYW;

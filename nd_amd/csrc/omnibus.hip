@@ -3240,10 +3240,7 @@ static void launch_retain_k(const OmniGlobalArgs<T> &g, const OmniTab &tab, int6
                             bool stats, hipStream_t stream)
 {
     const dim3 grid((unsigned)nblocks), block(kRetainThreads);
-#ifndef ND_RETAIN_EXACT
-#define ND_RETAIN_EXACT 1
-#endif
-    if (ND_RETAIN_EXACT && g.k == KMAX && g.sx == 1 &&
+    if (g.k == KMAX && g.sx == 1 &&
         (int64_t)g.k * g.st * (int64_t)sizeof(T) < 0x7fffffffLL && g.st >= 0) {
         if (stats)
             hipLaunchKernelGGL((omnibus_c2_retain_kernel<T, KMAX, true, true>), grid, block, 0,
@@ -3329,10 +3326,7 @@ static void launch_retain(const OmniGlobalArgs<T> &g, const OmniTab &tab, int64_
 // behind the time-split pass A has the float32 screen only)
 static bool search_fs_enabled()
 {
-    static const bool v = [] {
-        const char *e = getenv("ND_AMD_SEARCH_FS");
-        return e ? atoi(e) != 0 : true;
-    }();
+    static const bool v = env_int("ND_AMD_SEARCH_FS", 1) != 0;
     return v;
 }
 
@@ -3345,10 +3339,7 @@ static bool search_fs_enabled()
 // round 4.)
 static int fused_form_env()
 {
-    static const int v = [] {
-        const char *e = getenv("ND_AMD_FUSED_FORM");
-        return e ? atoi(e) : -1;
-    }();
+    static const int v = env_int("ND_AMD_FUSED_FORM", -1);
     return v;
 }
 
@@ -3419,12 +3410,8 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
     g.dense_idx = reinterpret_cast<uint32_t *>(ws + w.off_dense);
     g.segd = w.segd;
     // the register search exists for the series lengths whose arrays fit the register file
-    static const int dense_env = [] {
-        const char *e = getenv("ND_AMD_DENSE_MIN");
-        return e ? atoi(e) : 16;
-    }();
     const bool dense_ok = k <= (sizeof(T) == 4 ? 32 : 16) && pm_ids == nullptr && mlp == nullptr;
-    g.dense_min = dense_ok ? dense_env : 65;
+    g.dense_min = dense_ok ? kDenseMin : 65;
     const bool stats = (z_out != nullptr) || (p_out != nullptr);
     const bool retain = k <= (sizeof(T) == 4 ? kRetainMaxF32 : kRetainMaxF64);
     // (round 6) The screen of the whole-series test is unusable where omega2 leaves [0, 1] (omni_bounds): P is then not
@@ -3433,57 +3420,38 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
     // (24 x 2048 x 4096, n = 1: 9.2 ms against 0.7 ms with n = 9).  Pass A evaluates that one test exactly instead
     // (its STATS instantiation: z, the chi-square pair, P > alpha as the reference decides it) and lists only the
     // pixels whose whole-series test fires -- for n = 1 on multilooked data none, as in the reference.
-    // ND_AMD_EXACT_FLAGS=0: as before.
-    static const bool exact_flags_env = [] {
-        const char *e = getenv("ND_AMD_EXACT_FLAGS");
-        return e ? atoi(e) != 0 : true;
-    }();
     const bool global_screen_ok = (htab[(size_t)k].zlo > -INFINITY) || (htab[(size_t)k].zhi < INFINITY);
-    const bool exact_flags = exact_flags_env && !global_screen_ok && mlp == nullptr && k >= 2;
+    const bool exact_flags = !global_screen_ok && mlp == nullptr && k >= 2;
     const bool stats_a = stats || exact_flags;      // the pass A instantiation that evaluates the whole-series test exactly
     // Low thresholds make nearly every wave dense (P > alpha holds for a fraction 1 - alpha of
     // stationary pixels): the search is then fused into pass A.  Speed only -- every form gives the
     // same map.  ND_AMD_FUSED_ALPHA overrides the switch-over (0 = never fuse, 2 = always).
-    static const double fused_alpha = [] {
-        const char *e = getenv("ND_AMD_FUSED_ALPHA");
-        return e ? atof(e) : 0.75;
-    }();
+    static const double fused_alpha = env_double("ND_AMD_FUSED_ALPHA", 0.75);
     // The chain form in registers costs the same at every threshold (1.55 ms on 24 x 4096^2), and the
     // sparse design passes that where a tenth of the pixels are candidates (alpha = 0.76 / 0.8 / 0.85:
     // 2.9 / 2.5 / 2.1 ms): it is offered up to 0.93, and the device-side sample decides.  The forms
     // that pay more for fusing (pixel-major: the LDS images; longer series: two streaming passes)
     // keep 0.75.
-    static const double fused_alpha_regs = [] {
-        const char *e = getenv("ND_AMD_FUSED_ALPHA");
-        return e ? atof(e) : 0.93;
-    }();
+    static const double fused_alpha_regs = env_double("ND_AMD_FUSED_ALPHA", 0.93);
     // (z / P rasters asked for on top: they come from one launch of the plain pass A first, see below)
-    const bool fused = retain && dense_ok && g.dense_min <= 64 && alpha < fused_alpha_regs && !exact_flags;
+    const bool fused = retain && dense_ok && alpha < fused_alpha_regs && !exact_flags;
     const bool fused_stats = fused && stats;
     // Series beyond the register forms (33 .. 128 dates; float64: 17 .. 128): the streaming search with
     // 64- or 128-bit masks.  Without it every pixel of a low-threshold run went through pass B one by one
     // (k = 48 at alpha = 0.01: 118 ms per 16.7 Mpx).
     // (round 6, later) 129 .. 192 dates: the chain search in two streaming passes with three-word masks -- before,
     // every pixel of a low-threshold run on such a series went through pass B (136 dates x 512 x 4096 at the
-    // reference's default alpha = 0.01: 340 ms; 128 dates: 2.3 ms).  ND_AMD_STREAM_CHAIN_192=0: as before.
-    static const bool chain192_env = [] {
-        const char *e = getenv("ND_AMD_STREAM_CHAIN_192");
-        return e ? atoi(e) != 0 : true;
-    }();
-    const bool stream_long = !dense_ok && pm_ids == nullptr && mlp == nullptr &&
-                             k <= (chain192_env ? kStreamChainMax : kDenseMax) &&
-                             dense_env <= 64 && alpha < fused_alpha && !exact_flags;
+    // reference's default alpha = 0.01: 340 ms; 128 dates: 2.3 ms).
+    const bool stream_long = !dense_ok && pm_ids == nullptr && mlp == nullptr && k <= kStreamChainMax &&
+                             alpha < fused_alpha && !exact_flags;
     // multilooking pass A: the search fused in (dense_chain on the retained, multilooked series) at
     // every threshold below the sparse regime -- by alpha alone: the density sample reads the planes
     // as they are, not multilooked
-    const bool ml_chain = mlp != nullptr && k >= 2 && dense_env <= 64 && alpha < fused_alpha_regs;
+    const bool ml_chain = mlp != nullptr && k >= 2 && alpha < fused_alpha_regs;
     // z / P rasters asked for on top: they come from one launch of the plain pass A (which
     // evaluates the whole-series test of every pixel anyway), the map from the streaming search
     // ND_AMD_STATS_SPLIT=1: the rasters from a pass of their own in front of every fused search, as before round 6
-    static const bool stats_split_env0 = [] {
-        const char *e = getenv("ND_AMD_STATS_SPLIT");
-        return e ? atoi(e) != 0 : false;
-    }();
+    static const bool stats_split_env0 = env_int("ND_AMD_STATS_SPLIT", 0) != 0;
     // (round 6) with rasters, a long series takes the chain form at EVERY low threshold -- in registers (float64,
     // 17 .. 24 dates) or in two streaming passes -- whose forward pass carries the whole-series fold: no separate
     // read for the rasters
@@ -3492,28 +3460,17 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
     // (round 6) the sparse regime beyond the register-retaining lengths: the time-split pass A hands the
     // candidates' series to pass B from its registers (omnibus_c2_split_kernel).  ND_AMD_C2_SPLIT=0: the
     // plain pass A and the gather, as before.
-    static const bool split_env = [] {
-        const char *e = getenv("ND_AMD_C2_SPLIT");
-        return e ? atoi(e) != 0 : true;
-    }();
-    // ND_AMD_C2_SPLIT_STATS=0: with rasters the plain pass A and the gather, as before
-    static const bool split_stats_env = [] {
-        const char *e = getenv("ND_AMD_C2_SPLIT_STATS");
-        return e ? atoi(e) != 0 : true;
-    }();
+    static const bool split_env = env_int("ND_AMD_C2_SPLIT", 1) != 0;
     // (float64 beyond 48 dates -- eight slices of doubles in turn -- measured slower with the rasters than the
     //  plain pass A and the gather: 3.65 against 3.43 ms on 96 x 1024 x 4096)
-    const bool split_stats_ok = split_stats_env && !(sizeof(T) == 8 && k > 48);
+    const bool split_stats_ok = !(sizeof(T) == 8 && k > 48);
     const bool split_ok = split_env && search_fs_enabled() && !retain && !stream_long && (!stats || split_stats_ok) && !exact_flags &&
                           k <= (sizeof(T) == 4 ? 192 : 96) && pm_ids == nullptr && mlp == nullptr && sx == 1;
     // The threshold only says that dense waves are LIKELY; whether they are is a property of the
     // data (a low alpha on strongly filtered data fires rarely).  Above a minimum size the choice
     // is therefore made on the device from a sample (omnibus_c2_sample_kernel): both variants are
     // launched, the unfavoured one returns at once.  ND_AMD_GATE=0: decide by alpha alone.
-    static const bool gate_env = [] {
-        const char *e = getenv("ND_AMD_GATE");
-        return e ? atoi(e) != 0 : true;
-    }();
+    static const bool gate_env = env_int("ND_AMD_GATE", 1) != 0;
     g.gate = flag_count + 2;            // word 2 of shard 0's counter line (zeroed with the counters)
     g.gate_n = 0;
     g.gate_mode = 0;
@@ -3687,10 +3644,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         if (per_shard > 64) per_shard = 64;
         if (per_shard < 1) per_shard = 1;
         const int64_t sblocks = per_shard * kShards;
-        static const int mode_env = [] {
-            const char *e = getenv("ND_AMD_SEARCH_MODE");     // 0 LDS image, 1 from memory, 3 chain form
-            return e ? atoi(e) : -1;
-        }();
+        static const int mode_env = env_int("ND_AMD_SEARCH_MODE", -1);     // 0 LDS image, 1 from memory, 3 chain form
         // The register form serves the series lengths of dense_search, as long as the screen can
         // decide tests at all (it cannot where omega2 leaves [0, 1], e.g. single-look data: every
         // test would cost a second walk of its segment).
@@ -3709,10 +3663,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         // pixels, nearly every date of them a change) one lane per segment start; long ones (the
         // candidates of sparse waves, few changes each) in the register form.  The choice is made
         // per shard, on the device.
-        static const int starts_env = [] {
-            const char *e = getenv("ND_AMD_SEARCH_STARTS");      // list length per shard up to which ...; 0 = off
-            return e ? atoi(e) : 512;
-        }();
+        static const int starts_env = env_int("ND_AMD_SEARCH_STARTS", 512);     // list length per shard up to which ...; 0 = off
         const bool starts_form = low_threshold && k >= 2 && k <= 193 && starts_env > 0 && mode_env < 0;
         if (starts_form) {
             s.starts_max = (uint32_t)starts_env;
@@ -3773,10 +3724,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         }
         // images beyond 48 KB (three waves per CU or fewer at 64 series per wave): 16 series per wave
         // (96 dates x 8.4 Mpx at alpha = 0.99: pass B 1.84 ms with 64, 1.35 with 32, 1.30 with 16)
-        static const int pxw_env = [] {
-            const char *e = getenv("ND_AMD_SEARCH_PXW");        // 64: always full waves; 32 / 16
-            return e ? atoi(e) : 0;
-        }();
+        static const int pxw_env = env_int("ND_AMD_SEARCH_PXW", 0);        // 64: always full waves; 32 / 16
         const int pxw = pxw_env ? pxw_env : (lds_bytes > 48 * 1024 ? 16 : 64);
         if (mode == 0 && use_lds && !behind && (pxw == 32 || pxw == 16)) {
             const size_t lds_n = (size_t)k * 4 * (size_t)pxw * sizeof(T) + scr_bytes;
@@ -3932,23 +3880,14 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
                         static_cast<const T *>(c12im) == static_cast<const T *>(c12re) + 1) ? 1 : 0;
         // LDS-DMA form: 16-byte aligned variables, k a multiple of the 16-byte vector, k <= 24
         constexpr int VE = 16 / (int)sizeof(T);
-        static const int pm_form = [] {
-            const char *e = getenv("ND_AMD_PM_FORM");        // 1 = always the register-staged form
-            return e ? atoi(e) : 0;
-        }();
+        static const int pm_form = env_int("ND_AMD_PM_FORM", 0);        // 1 = always the register-staged form
         // (round 6: any series length -- the spans of 64 pixels are 16-byte pieces whatever k is; lanes whose runs
-        //  are not 16-byte aligned in the image read it element by element, pm_pick.  ND_AMD_PM_ANYK=0: as before,
-        //  multiples of the vector only)
-        static const bool pm_anyk = [] {
-            const char *e = getenv("ND_AMD_PM_ANYK");
-            return e ? atoi(e) != 0 : true;
-        }();
+        //  are not 16-byte aligned in the image read it element by element, pm_pick)
         const bool kvec = (k % VE) == 0;
-        const bool dma_ok = pm_form != 1 && (kvec || pm_anyk) &&
-                            (((uintptr_t)c11 | (uintptr_t)c22 | (uintptr_t)c12re) & 15) == 0 &&
+        const bool dma_ok = pm_form != 1 && (((uintptr_t)c11 | (uintptr_t)c22 | (uintptr_t)c12re) & 15) == 0 &&
                             (pm.c12_joint || ((uintptr_t)c12im & 15) == 0);
-        const bool fused_pm = dma_ok && !stats && !exact_flags && k <= 32 && dense_env <= 64 && alpha < fused_alpha;
-        if (fused_pm) g.dense_min = dense_env;
+        const bool fused_pm = dma_ok && !stats && !exact_flags && k <= 32 && alpha < fused_alpha;
+        if (fused_pm) g.dense_min = kDenseMin;
         if (dma_ok) {
             OmniPmDmaArgs<T> dm;
             int off = 0;
@@ -3981,21 +3920,11 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
                 // to issue per date six waves per CU keep up and the single fetch wins.
                 // ND_AMD_PM_STREAM_LDS=0 selects the from-memory forms, ND_AMD_PM_STREAM_SECTOR=0/1
                 // one of the two.
-                static const bool pm_lds = [] {
-                    const char *e = getenv("ND_AMD_PM_STREAM_LDS");
-                    if (e) return atoi(e) != 0;
-                    return getenv("ND_AMD_PM_STREAM_SECTOR") == nullptr;
-                }();
-                static const int pm_sector_env = [] {
-                    const char *e = getenv("ND_AMD_PM_STREAM_SECTOR");
-                    return e ? atoi(e) : -1;
-                }();
+                static const int pm_sector_env = env_int("ND_AMD_PM_STREAM_SECTOR", -1);
+                static const bool pm_lds = env_int("ND_AMD_PM_STREAM_LDS", pm_sector_env < 0 ? 1 : 0) != 0;
                 const bool pm_direct4 = pm_sector_env >= 0 ? pm_sector_env != 0 : alpha <= 1e-3;
                 const int fused_form_pm = fused_form_env();
-                static const int pm_direct_env = [] {
-                    const char *e = getenv("ND_AMD_PM_DIRECT");        // 0: every variable through an LDS image
-                    return e ? atoi(e) : 1;
-                }();
+                static const int pm_direct_env = env_int("ND_AMD_PM_DIRECT", 1);        // 0: every variable through an LDS image
                 // dense_chain behind the staging, C11 / C22 straight into registers and only C12 through
                 // LDS: at every threshold below the sparse regime (2.0 ms; the streaming search on full
                 // LDS images: 2.05 / 2.37 ms at alpha = 1e-4 / 0.01, dense_chain on full images: 2.5 ms)
@@ -4085,11 +4014,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         // retains (one read of the planes; up to round 3 a plain pass A of its own produced them in front
         // of the search: 24 x 2048 x 4096 at alpha = 0.01 1.54 ms against 0.77 without rasters).
         // ND_AMD_STATS_SPLIT=1: the separate pass as before.
-        static const bool stats_split_env = [] {
-            const char *e = getenv("ND_AMD_STATS_SPLIT");
-            return e ? atoi(e) != 0 : false;
-        }();
-        const bool stats_in_chain = fused_stats && !stats_split_env;
+        const bool stats_in_chain = fused_stats && !stats_split_env0;
         if (fused_stats && !stats_in_chain) {
             const int dm = g.dense_min;
             const uint32_t cap = g.dump_cap;
@@ -4172,7 +4097,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             g.p_out = nullptr;
             g.dump_cap = cap_keep;
         }
-        g.dense_min = dense_env;
+        g.dense_min = kDenseMin;
         gated = take_sample();                      // only where the sparse form can retain (k <= 48)
         const DenseScreen scr = make_dense_screen<T>(htab, (int)k, n_looks);
         g.gate_mode = gated ? 1 : 0;

@@ -146,16 +146,10 @@ __device__ __forceinline__ bool omni_gate_skip(const OmniGlobalArgs<T> &g)
 }
 
 constexpr int kGlobalThreads = 256;
-#ifndef ND_RETAIN_THREADS
-#define ND_RETAIN_THREADS 256
-#endif
-constexpr int kRetainThreads = ND_RETAIN_THREADS;   // block size of the register-retaining pass A
+constexpr int kRetainThreads = 256;   // block size of the register-retaining pass A
 constexpr int kShards = 128;
 constexpr int kCounterStride = 32;   // uint32 words between shard counters (128 B)
-#ifndef ND_TIME_CHUNK
-#define ND_TIME_CHUNK 4
-#endif
-constexpr int kTimeChunk = ND_TIME_CHUNK;
+constexpr int kTimeChunk = 4;
 
 
 __device__ __forceinline__ void zero_fill_span(uint8_t *ob, const int nb, const int lane)

@@ -1872,20 +1872,11 @@ static C3Workspace c3_layout(int64_t npix, int64_t ny, int64_t k)
     return w;
 }
 
-// ND_AMD_C3_RETAIN: 0 = never the time-split pass A, 1 (default) = where it applies; ND_AMD_C3_RETAIN_MIN_K: the
-// shortest series it takes (default 2)
+// where the time-split pass A applies
 template <typename T>
 static bool c3_retain_ok(const C3Workspace &w, const C3Args<T> &g)
 {
-    static const int on = [] {
-        const char *e = getenv("ND_AMD_C3_RETAIN");
-        return e ? atoi(e) : 1;
-    }();
-    static const int min_k = [] {
-        const char *e = getenv("ND_AMD_C3_RETAIN_MIN_K");
-        return e ? atoi(e) : 2;
-    }();
-    return sizeof(T) == 4 && on != 0 && w.dump_cap > 0 && g.k >= min_k && g.k <= kC3RetainMaxK && g.lane32 != 0;
+    return sizeof(T) == 4 && w.dump_cap > 0 && g.k >= 2 && g.k <= kC3RetainMaxK && g.lane32 != 0;
 }
 
 static int c3_launch_retain(const C3Workspace &, C3Args<double> &, const OmniTab &, unsigned char *, hipStream_t)
@@ -1983,19 +1974,11 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     ND_HIP_CHECK(hipMemsetAsync(g.flag_count, 0, kC3CounterBytes, stream));
     const bool stats = z_out != nullptr || p_out != nullptr;
     // Low thresholds: the search fused into the streaming pass (speed only, same map).
-    // ND_AMD_C3_FUSED_ALPHA overrides the switch-over (0 = never, 2 = always).
-    static const double fused_alpha = [] {
-        const char *e = getenv("ND_AMD_C3_FUSED_ALPHA");
-        return e ? atof(e) : 0.75;
-    }();
+    constexpr double fused_alpha = 0.75;
     // (round 6) the whole-series test's screen is unusable where omega2 leaves [0, 1] (the default n = 1 on a series of
     // more than a few dates): pass A then evaluates that test exactly and lists only what fires, as the dual-pol entry
-    // point does (omnibus.hip, exact_flags) -- instead of handing every pixel to pass B.  ND_AMD_EXACT_FLAGS=0: as before.
-    static const bool exact_flags_env = [] {
-        const char *e = getenv("ND_AMD_EXACT_FLAGS");
-        return e ? atoi(e) != 0 : true;
-    }();
-    const bool exact_flags = exact_flags_env && pm_ids == nullptr && k >= 2 &&
+    // point does (omnibus.hip, exact_flags) -- instead of handing every pixel to pass B.
+    const bool exact_flags = pm_ids == nullptr && k >= 2 &&
                              !((htab[(size_t)k].zlo > -INFINITY) || (htab[(size_t)k].zhi < INFINITY));
     const bool fused = pm_ids == nullptr && k >= 2 && k <= kDenseMax && k <= kTabArgs && alpha < fused_alpha && g.off32 &&
                        !exact_flags;
@@ -2010,15 +1993,10 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
         for (int c = 0; c < 9; ++c)
             if (!(joint && c >= 3 && ((c - 3) & 1))) aligned = aligned && (((uintptr_t)g.pl[c]) & 15) == 0;
         const int64_t per_px = 9 * k * (int64_t)sizeof(T);
-        static const int pxw_env = [] {
-            const char *e = getenv("ND_AMD_C3_PM_PXW");          // 64 / 32 / 16: pixels per wave (diagnostic)
-            return e ? atoi(e) : 0;
-        }();
         // images of ~28 KB (five waves per CU, every SIMD with a wave to fold) where that leaves at least 16
         // pixels per wave; 16 pixels up to 56 KB.  48 dates: 32 pixels per wave (55 KB, two waves per CU: two
         // SIMDs idle) 4.56 ms, 16 pixels 3.39 ms
-        int pxw = 64 * per_px <= 32 * 1024 ? 64 : (32 * per_px <= 32 * 1024 ? 32 : (16 * per_px <= 56 * 1024 ? 16 : 0));
-        if ((pxw_env == 32 || pxw_env == 16) && pxw_env < pxw) pxw = pxw_env;
+        const int pxw = 64 * per_px <= 32 * 1024 ? 64 : (32 * per_px <= 32 * 1024 ? 32 : (16 * per_px <= 56 * 1024 ? 16 : 0));
         if (!(all_real || joint) || !aligned || (k % VE) != 0 || pxw == 0 || !(alpha >= fused_alpha)) {
             set_error("nd_amd_omnibus_c3_pixel_major: nine real (y, x, time) arrays, or three real and three interleaved "
                       "complex ones, 16-byte aligned, a multiple of %d dates up to 56 KB per 16 pixels, alpha >= %g "
@@ -2079,49 +2057,37 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     if (fused) {
         if (stats) ND_HIP_CHECK(hipMemsetAsync(g.flag_count, 0, kC3CounterBytes, stream));   // its lists are not used
         const DenseScreen scr = make_dense_screen<T>(htab, (int)k, n_looks);
-        static const int dense_min = [] {
-            const char *e = getenv("ND_AMD_DENSE_MIN");
-            return e ? atoi(e) : 16;
-        }();
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_FUSED, stream);
         // rounding band of the suffix-sum global tests, 3 x 3: 1.46 j (21 n + 20) u abc / D (the kernel's header)
         const float cu3 = (sizeof(T) == 4 ? 5.9604645e-08f : 1.1102230e-16f) * 1.46f;
-        // ND_AMD_C3_FUSED_FORM: 0 the streaming search at every low threshold, 3 the chain search in two
-        // streaming passes at every one; unset: the chain search above alpha = 0.02 (where marginal tests over
-        // four and more dates stop being rare), speed only
-        static const int form_env = [] {
-            const char *e = getenv("ND_AMD_C3_FUSED_FORM");
-            return e ? atoi(e) : -1;
-        }();
-        const bool chain = k >= 3 && (form_env == 3 || (form_env < 0 && alpha > 0.02));
+        // the chain search in two streaming passes above alpha = 0.02 (where marginal tests over four and more
+        // dates stop being rare), the streaming search below; speed only
+        const bool chain = k >= 3 && alpha > 0.02;
         if (k <= 64) {
             StreamScreen<64> ss = make_stream_screen<T, 64>(htab, scr, (int)k, n_looks);
             for (int j = 0; j <= 64; ++j) ss.e[j].cj = cu3 * (21.f * (float)j + 20.f);
             if (chain)
                 hipLaunchKernelGGL((omnibus_c3_stream_chain_kernel<T, 1>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
-                                   stream, g, tab, ss, dense_min);
+                                   stream, g, tab, ss, kDenseMin);
             else
                 hipLaunchKernelGGL((omnibus_c3_stream_kernel<T, 1>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
-                                   stream, g, tab, scr, ss, dense_min);
+                                   stream, g, tab, scr, ss, kDenseMin);
         } else {
             StreamScreen<kDenseMax> ss = make_stream_screen<T, kDenseMax>(htab, scr, (int)k, n_looks);
             for (int j = 0; j <= kDenseMax; ++j) ss.e[j].cj = cu3 * (21.f * (float)j + 20.f);
             if (chain)
                 hipLaunchKernelGGL((omnibus_c3_stream_chain_kernel<T, 2>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
-                                   stream, g, tab, ss, dense_min);
+                                   stream, g, tab, ss, kDenseMin);
             else
                 hipLaunchKernelGGL((omnibus_c3_stream_kernel<T, 2>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
-                                   stream, g, tab, scr, ss, dense_min);
+                                   stream, g, tab, scr, ss, kDenseMin);
         }
         ND_HIP_CHECK(hipGetLastError());
     }
 
     // behind the streaming search: short lists (what its screen could not decide) one lane per segment
     // start -- ND_AMD_SEARCH_STARTS = list length per shard up to which (0 = never), as for the dual-pol test
-    static const int starts_env = [] {
-        const char *e = getenv("ND_AMD_SEARCH_STARTS");
-        return e ? atoi(e) : 512;
-    }();
+    static const int starts_env = env_int("ND_AMD_SEARCH_STARTS", 512);
     if (fused && k >= 3 && starts_env > 0) {
         g.starts_max = (uint32_t)starts_env;
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_SEARCH, stream);
@@ -2133,16 +2099,12 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     // beats a dependent, TLB-missing plane access per date and lane)
     const size_t scr_bytes = (size_t)(k + 1) * 4 * sizeof(double);
     const size_t lds_bytes = (size_t)k * 9 * 64 * sizeof(T) + scr_bytes;
-    // ND_AMD_C3_SEARCH_MODE=1: always from memory (one date of read-ahead, 8+ waves per CU).
-    // Measured on config 4's share (48 x 1024 x 8192, 2 % of the pixels listed): 2.02 ms against
+    // The search from memory (one date of read-ahead, 8+ waves per CU) serves only the series whose image does
+    // not fit.  Measured on config 4's share (48 x 1024 x 8192, 2 % of the pixels listed): 2.02 ms against
     // 1.55 ms with the image at one wave per CU -- of which 1.13 ms is the gather itself: 72 M isolated
     // 4-byte reads = 4.6 GB of 64-byte sectors at 4.1 TB/s, i.e. the pass is bound by the sector
     // traffic of its gather, not by the occupancy the image costs.
-    static const int c3_mode = [] {
-        const char *e = getenv("ND_AMD_C3_SEARCH_MODE");
-        return e ? atoi(e) : 0;
-    }();
-    const bool use_lds = c3_mode == 1 ? false : lds_bytes <= 150 * 1024;
+    const bool use_lds = lds_bytes <= 150 * 1024;
     if (use_lds && lds_bytes > 64 * 1024) {
         ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c3_search_kernel<T, true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -2154,10 +2116,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     // Pixels per wave: as many as keep the image at ~32 KB, i.e. five waves per CU taking turns at
     // gathering and searching.  Config 4's share (k = 48): 64 / 32 / 16 pixels per wave -> pass B
     // 1.58 / 1.35 / 1.28 ms.  ND_AMD_C3_LANES = 64 / 32 / 16 forces a width.
-    static const int c3_lanes_env = [] {
-        const char *e = getenv("ND_AMD_C3_LANES");
-        return e ? atoi(e) : 0;
-    }();
+    static const int c3_lanes_env = env_int("ND_AMD_C3_LANES", 0);
     const int c3_lanes = (c3_lanes_env == 64 || c3_lanes_env == 32 || c3_lanes_env == 16)
                              ? c3_lanes_env
                              : (lds_bytes <= 33 * 1024 ? 64 : (lds_bytes <= 66 * 1024 ? 32 : 16));
@@ -2175,12 +2134,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
                            (size_t)(k + 1) * sizeof(DenseScreenEntry), stream, g, fscr);
         ND_HIP_CHECK(hipGetLastError());
     }
-    // ND_AMD_C3_PM_SEARCH=image: the LDS-image search on pixel-major inputs, as before round 6 (A/B)
-    static const bool pm_image = [] {
-        const char *e = getenv("ND_AMD_C3_PM_SEARCH");
-        return e != nullptr && strcmp(e, "image") == 0;
-    }();
-    if (g.pm_vec && !pm_image) {
+    if (g.pm_vec) {
         // pixel-major inputs: every listed pixel read where it lies in the caller's arrays
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_SEARCH, stream);
         int64_t per_shard_d = ceil_div(ceil_div(npix, kC3Shards), 64);

@@ -303,6 +303,7 @@ struct DenseScreenEntry {
     float rf, a, b;
 };
 constexpr int kDenseMax = 128;
+constexpr int kDenseMin = 16;     // listed pixels of a wave from which the wave is searched as a whole (65 = never)
 struct DenseScreen {
     DenseScreenEntry e[kDenseMax + 1];
 };

@@ -48,19 +48,9 @@
 
 namespace nd_amd {
 
-// Steps the L2 prefetch of the idle waves (8 .. 11) runs ahead of the transfers.  0 = none, the default:
-// measured in round 5 (24 x 4096^2, 3 x 3 / 5 x 5 window, one box): none 2.03 / 3.13 ms, one step ahead
-// 2.14 / 3.27, two 2.15 / 3.22, three 2.14 / 3.34, five 2.23 / 3.34, eight 2.31 / 3.36 -- the more requests
-// in flight the slower: the walk is not waiting for memory (a staging-only probe of the same walk,
-// tools/probe_tiles.hip, moves the 3 x 3 kernel's bytes in 1.24 ms).
-#ifndef ND_ML_PREFETCH
-#define ND_ML_PREFETCH 0
-#endif
-#ifdef ND_ML_TRACE
-#define ND_ML_TRC_WORDS (12 * 16 * 5)
-#else
-#define ND_ML_TRC_WORDS 0
-#endif
+// The idle waves (8 .. 11) prefetch nothing: an L2 prefetch one to eight steps ahead of the transfers measured
+// slower the further ahead it ran (24 x 4096^2, 3 x 3 / 5 x 5 window: none 2.03 / 3.13 ms, one step 2.14 / 3.27,
+// eight 2.31 / 3.36) -- the walk is not waiting for memory.
 
 template <int K>
 struct MlGeom {
@@ -87,10 +77,6 @@ __device__ __forceinline__ void ml_barrier()
 // four 16-byte or sixteen 4-byte transfers can leave)
 __device__ __forceinline__ void ml_wait_vm(const int n)
 {
-#ifdef ND_ML_WAIT0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return;
-#endif
     if (n >= 16)
         asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
     else if (n >= 4)
@@ -118,21 +104,16 @@ typedef int ml_v4i __attribute__((ext_vector_type(4)));
 //    address register between two transfers -- it cannot guarantee for inline assembly, which it does
 //    not look into.  (Found the hard way: with one statement per transfer, results changed with
 //    register allocation.)
-#ifdef ND_ML_NT
-#define ND_ML_POL " nt"
-#else
-#define ND_ML_POL ""
-#endif
 __device__ __forceinline__ void ml_dma16x4(const ml_v4i rsrc, const unsigned m0, const int a0, const int a1,
                                            const int a2, const int a3, const int so)
 {
     const int o0 = __builtin_amdgcn_readfirstlane(so + 4096), o1 = __builtin_amdgcn_readfirstlane(so + 3072),
               o2 = __builtin_amdgcn_readfirstlane(so + 2048), o3 = __builtin_amdgcn_readfirstlane(so + 1024);
     asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %1, %5, %6 offen offset:0" ND_ML_POL " lds\n\t"
-                 "buffer_load_dwordx4 %2, %5, %7 offen offset:1024" ND_ML_POL " lds\n\t"
-                 "buffer_load_dwordx4 %3, %5, %8 offen offset:2048" ND_ML_POL " lds\n\t"
-                 "buffer_load_dwordx4 %4, %5, %9 offen offset:3072" ND_ML_POL " lds"
+                 "buffer_load_dwordx4 %1, %5, %6 offen offset:0 lds\n\t"
+                 "buffer_load_dwordx4 %2, %5, %7 offen offset:1024 lds\n\t"
+                 "buffer_load_dwordx4 %3, %5, %8 offen offset:2048 lds\n\t"
+                 "buffer_load_dwordx4 %4, %5, %9 offen offset:3072 lds"
                  :
                  : "s"(__builtin_amdgcn_readfirstlane((int)m0)), "v"(a0), "v"(a1), "v"(a2), "v"(a3), "s"(rsrc),
                    "s"(o0), "s"(o1), "s"(o2), "s"(o3)
@@ -148,10 +129,10 @@ __device__ __forceinline__ void ml_dma4x4(const ml_v4i rsrc, const unsigned m0, 
               o2 = __builtin_amdgcn_readfirstlane(s2 + 4096 - 256 * (R + 2)),
               o3 = __builtin_amdgcn_readfirstlane(s3 + 4096 - 256 * (R + 3));
     asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\t"
-                 "buffer_load_dword %1, %2, %3 offen offset:%7" ND_ML_POL " lds\n\t"
-                 "buffer_load_dword %1, %2, %4 offen offset:%8" ND_ML_POL " lds\n\t"
-                 "buffer_load_dword %1, %2, %5 offen offset:%9" ND_ML_POL " lds\n\t"
-                 "buffer_load_dword %1, %2, %6 offen offset:%10" ND_ML_POL " lds"
+                 "buffer_load_dword %1, %2, %3 offen offset:%7 lds\n\t"
+                 "buffer_load_dword %1, %2, %4 offen offset:%8 lds\n\t"
+                 "buffer_load_dword %1, %2, %5 offen offset:%9 lds\n\t"
+                 "buffer_load_dword %1, %2, %6 offen offset:%10 lds"
                  :
                  : "s"(__builtin_amdgcn_readfirstlane((int)m0)), "v"(voff), "s"(rsrc), "s"(o0), "s"(o1), "s"(o2),
                    "s"(o3), "n"(256 * R), "n"(256 * (R + 1)), "n"(256 * (R + 2)), "n"(256 * (R + 3))
@@ -211,11 +192,6 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
     // ---- staging ----
     const float *vp[4] = {g.c11, g.c12r, g.c12i, g.c22};
     const unsigned lds0 = (unsigned)(uintptr_t)(ml_lds_f32 *)slots;       // LDS byte address of the slots
-#if ND_ML_PREFETCH > 0
-    // 256 bytes behind the table (and the trace area of diagnostic builds): where the prefetch reads land
-    const unsigned pf_dump = lds0 + (unsigned)(reinterpret_cast<unsigned char *>(rowtab + 16 + ND_ML_TRC_WORDS) -
-                                               reinterpret_cast<unsigned char *>(slots));
-#endif
     const int sstep = (int)g.st * 4;                             // bytes between dates (host: k * st * 4 < 2^31)
     // Waves 0 .. 7 stage: wave w the plane w of the step (variable w & 3, date w >> 2), whose LDS image
     // (16 rows x 256 bytes) is within reach of the transfers' 12-bit offset from one value of M0.
@@ -316,18 +292,6 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
     float cv = 0.f;                  // carried column element of step S - 1 (see the end of a step)
     float v[KMAX][4];
 
-#ifdef ND_ML_TRACE
-    // time stamps of steps 32 .. 47 of one block, kept in LDS (no memory traffic inside the loop) and
-    // written out when the block ends
-    unsigned *trc = reinterpret_cast<unsigned *>(rowtab + 16);
-#define ML_STAMP(j)                                                                                  \
-    do {                                                                                             \
-        if (ml.trace && b == ml.trace_block && lane == 0 && S >= 32 && S < 48)                        \
-            trc[(wave * 16 + (S - 32)) * 5 + (j)] = (unsigned)__builtin_amdgcn_s_memtime();          \
-    } while (0)
-#else
-#define ML_STAMP(j)
-#endif
     // One barrier per step.  Behind the barrier that opens step S everything of step S - 1 is visible:
     // its window sums (result buffer (S - 1) & 1), and every patch has read its planes.  Step S then
     //   A. saves the carried columns of step S - 1's planes and sends the transfers of step S + PF into
@@ -344,11 +308,9 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
             if (s < nstep_k) {
                 float *cur = slots + slot_i * M::SLOT;
                 const int slot_p = slot_i == 0 ? M::NSLOT - 1 : slot_i - 1;      // slot of step S - 1 = of S + PF
-                ML_STAMP(0);
                 // ---- A ----
                 if (S > 0 && co_lane) carry[s_prev * M::NCAR + co_wr] = cv;
                 int cnt_new = 0;
-#ifndef ND_ML_NO_DMA
                 if (S + PF < total_steps) {
                     int s2 = s + PF, X2 = Xi;
                     while (s2 >= nstep_k) {
@@ -358,45 +320,10 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
                     asm volatile("" : : "v"(cv) : "memory");                    // the columns above are in registers
                     cnt_new = stage(s2, X2, slot_p);
                 }
-#endif
-#if ND_ML_PREFETCH > 0
-                // ---- the waves that stage nothing (8 .. 11) ask for the planes of step S + PF + D: one
-                //      4-byte LDS-DMA read per 128-byte line into a dump area nobody reads (no register
-                //      to keep, nothing to wait for).  The lines then sit in the L2 (or the Infinity Cache)
-                //      when the transfers of that step are issued D steps later ----
-                if (!stager && S + PF + ND_ML_PREFETCH < total_steps) {
-                    int s3 = s + PF + ND_ML_PREFETCH, X3 = Xi;
-                    while (s3 >= nstep_k) {
-                        s3 -= nstep_k;
-                        X3 += 64;
-                    }
-                    constexpr int PFL = 2 * ROWS;                // lines of a plane's 64 new columns
-                    const int hi = lane >= PFL ? 1 : 0;
-                    const int pl = 2 * (wave - 8) + hi, lr = lane - hi * PFL;
-                    if (lane < 2 * PFL && X3 < nx) {
-                        int t = 2 * s3 + (pl >> 2);
-                        t = t < k ? t : k - 1;
-                        int xc = X3 + 32 * (lr & 1);
-                        xc = xc < nx ? xc : nx - 1;
-                        const int var = pl & 3;
-                        const float *pb = var == 0 ? g.c11 : (var == 1 ? g.c12r : (var == 2 ? g.c12i : g.c22));
-                        const float *pp = pb + (int64_t)t * g.st + (rowtab[lr >> 1] >> 2) + xc;
-                        asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\t"
-                                     "global_load_lds_dword %1, off"
-                                     :
-                                     : "s"(__builtin_amdgcn_readfirstlane((int)pf_dump)), "v"(pp)
-                                     : "memory");
-                    }
-                }
-#endif
                 // (a series of one step per tile: the columns saved above are the ones this very step
                 //  reads -- the only case in which A and B of one step touch the same carry entries)
                 if (nstep_k == 1) ml_barrier();
-                ML_STAMP(1);
                 // ---- B: window sums of this thread's patch ----
-#ifdef ND_ML_NO_COMPUTE
-                if (g.k < 0)
-#endif
                 {
                     double acc[2][4];
 #pragma unroll
@@ -448,13 +375,9 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
                         *reinterpret_cast<float4 *>(W + oy * (8 * 64)) = o;
                     }
                 }
-                ML_STAMP(2);
                 // ---- C: the transfers of the next step have landed (this wave's), then everybody's ----
-                // (the waves that stage nothing have nothing to wait for: their prefetch reads go nowhere)
-                if (stager || ND_ML_PREFETCH == 0) ml_wait_vm(PF >= 2 ? cnt_new : 0);
-                ML_STAMP(3);
+                ml_wait_vm(PF >= 2 ? cnt_new : 0);
                 ml_barrier();
-                ML_STAMP(4);
                 // the last 2h new columns of this step's planes, for the next tile (saved by the wave that
                 // staged the plane, in front of its next transfers into this slot: part A of the next step)
                 if (co_lane) cv = cur[co_rd];
@@ -583,11 +506,6 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
         // ---- a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275) ----
         if (!dense && wnp > 0 && ml.list) zero_fill_span(wob, wnp * k, lane);
     }
-#ifdef ND_ML_TRACE
-    __syncthreads();
-    if (ml.trace && b == ml.trace_block)
-        for (int e = tid; e < 12 * 16 * 5; e += NT) ml.trace[e] = trc[e];
-#endif
 }
 
 // -----------------------------------------------------------------------------------------
@@ -627,7 +545,7 @@ static int launch_ml_k(const OmniGlobalArgs<float> &g, const OmniTab &tab, const
 {
     typedef MlGeom<K> M;
     const size_t lds = ((size_t)M::NSLOT * M::SLOT + 2 * M::RES + (size_t)(KMAX / 2) * M::NCAR) * sizeof(float) +
-                       33 * sizeof(StreamEntry) + 16 * sizeof(int) + ND_ML_TRC_WORDS * 4 + (ND_ML_PREFETCH > 0 ? 256 : 0);
+                       33 * sizeof(StreamEntry) + 16 * sizeof(int);
     const dim3 grid((unsigned)nblocks), block(M::NT);
     StreamScreen<32> none;
     if (!ss) memset(&none, 0, sizeof(none));
@@ -664,23 +582,11 @@ int launch_ml_pass_a(const OmniGlobalArgs<float> &g, const OmniTab &tab, const O
     a.tmax = (int)ceil_div(p.nx, 64) + 2;
     a.x4 = ((((uintptr_t)g.c11 | (uintptr_t)g.c12r | (uintptr_t)g.c12i | (uintptr_t)g.c22) & 15) == 0 &&
             (g.sy & 3) == 0 && (g.st & 3) == 0) ? 1 : 0;
-    {
-        const char *e4 = getenv("ND_AMD_ML_X4");          // 0: per-element transfers everywhere (diagnostic)
-        if (e4 && atoi(e4) == 0) a.x4 = 0;
-    }
     a.wt = 1.0 / (double)(p.ml * p.ml);
     a.list = list ? 1 : 0;
     a.spx = a.nstrips = 0;
     a.trace = nullptr;
     a.trace_block = 1000;
-#ifdef ND_ML_TRACE
-    {
-        const char *e = getenv("ND_AMD_ML_TRACE");       // device pointer (hex) of >= 147456 bytes, diagnostic builds
-        a.trace = e ? reinterpret_cast<unsigned long long *>(strtoull(e, nullptr, 16)) : nullptr;
-        const char *eb = getenv("ND_AMD_ML_TRACE_BLOCK");
-        a.trace_block = eb ? atoi(eb) : 1000;
-    }
-#endif
     const int k = g.k;
 #define ND_ML_K(KK)                                                                       \
     do {                                                                                  \

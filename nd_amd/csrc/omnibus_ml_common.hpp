@@ -19,8 +19,8 @@ struct OmniMlArgs {
     double wt;                // 1 / ml^2 (nd/filters.py:297)
     int list;                 // 0: no candidate list (z / P rasters only)
     int spx, nstrips;         // (wave form, tools/experiments: strips per XCD, strips in all)
-    unsigned long long *trace;   // ND_ML_TRACE builds: time stamps of one block (tools/exp_ml_trace.py)
-    int trace_block;
+    unsigned long long *trace;   // (unused: the time stamps of round 5's diagnostic builds.  The two fields stay
+    int trace_block;             //  so that the kernel's argument layout, and with it its code, does not move)
 };
 
 __device__ __forceinline__ int ml_reflect(int cc, const int len)     // scipy 'reflect': d c b a | a b c d | d c b a

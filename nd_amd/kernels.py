@@ -249,7 +249,8 @@ def change_detection_c3_pixel_major(planes, alpha, n=1, stats=False):
             return None
     # the entry point's documented conditions (include/nd_amd.h), checked before anything is allocated: with the
     # reference's default alpha = 0.01 every full-pol (y, x, time) call would otherwise allocate the map and the
-    # workspace only to learn that it is declined
+    # workspace only to learn that it is declined.  (0.75 is the entry point's fixed switch-over to the fused search,
+    # `fused_alpha` in omnibus_c3.hip: no environment variable moves it.)
     ve = 16 // p0.element_size()
     if (not (alpha >= 0.75) or k % ve != 0 or 16 * 9 * k * p0.element_size() > 56 * 1024
             or any(t.data_ptr() % 16 != 0 for t, i in zip(planes, ids) if i == 1)):

@@ -292,3 +292,28 @@ def test_integration_doc_quotes_the_example():
     # the header says what the example does with the optional tile arguments
     hdr = open(os.path.join(ROOT, 'include', 'nd_amd.h')).read()
     assert 'NULL for any of the four' in hdr
+
+
+def test_library_switches_are_the_documented_and_tested_ones():
+    """The environment variables libnd_amd.so reads (every ND_AMD_* name handed to getenv / env_int / env_double under
+    nd_amd/csrc) are exactly the rows of README.md's "Library switches" table, getenv is called nowhere but in the helper,
+    and each switch is set by some test: a switch nothing forces is an experiment that is over and has to go."""
+    csrc = os.path.join(ROOT, 'nd_amd', 'csrc')
+    read, raw = set(), []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith(('.hip', '.hpp')):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        read |= set(re.findall(r'\b(?:getenv|env_int|env_double)\(\s*"(ND_AMD_[A-Z0-9_]+)"', text))
+        raw += [(f, m.group(0)) for m in re.finditer(r'\bgetenv\([^)]*\)', text)]
+    assert raw == [('common.hpp', 'getenv(name)')] * 2, raw           # env_int and env_double, nothing else
+    readme = open(os.path.join(ROOT, 'README.md')).read()
+    section = readme.split('### Library switches', 1)[1].split('\n## ', 1)[0]
+    documented = re.findall(r'^\| `(ND_AMD_[A-Z0-9_]+)` \|', section, flags=re.M)
+    assert len(documented) == len(set(documented))
+    assert read == set(documented), (sorted(read - set(documented)), sorted(set(documented) - read))
+    tests_dir = os.path.join(ROOT, 'tests')
+    used = ''.join(open(os.path.join(tests_dir, f)).read() for f in sorted(os.listdir(tests_dir))
+                   if f.endswith('.py') and f != os.path.basename(__file__))
+    untested = sorted(n for n in read if not re.search(r'\b%s\b' % n, used))
+    assert not untested, untested

@@ -1,6 +1,6 @@
 """ConvolutionFilter with a kernel that extends along time: the tiled kernel's walk over the window's planes
-(round 5) against the generic footprint kernel (ND_AMD_NO_TILED=1, the route until round 4).
-    python tools/bench_conv3d.py ; ND_AMD_NO_TILED=1 python tools/bench_conv3d.py"""
+(round 5; the generic footprint kernel was the route until round 4).
+    python tools/bench_conv3d.py"""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -21,6 +21,6 @@ for name, k in (('boxcar 3x3x3', np.ones((3, 3, 3)) / 27.0), ('random 3x3x3', rn
     by = {}
     for n_, ms in _lib.timing_collect(): by.setdefault(n_, []).append(ms)
     _lib.timing_enable(0)
-    print(json.dumps({'kernel': name, 'route': 'generic' if os.environ.get('ND_AMD_NO_TILED') else 'tiled', 'ms': round(dt * 1e3, 3),
+    print(json.dumps({'kernel': name, 'ms': round(dt * 1e3, 3),
                       'kernels_ms': {n_: round(sum(v) / len(v), 3) for n_, v in by.items()},
                       'M_px_t_per_s': round(x.numel() / dt / 1e6, 1)}), flush=True)

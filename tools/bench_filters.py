@@ -40,8 +40,7 @@ def main():
         n = x.numel()
         print(json.dumps({'workload': '%s %dx%d on %dt x %d x %d f32' % (a.what, a.w, a.w, a.k, a.ny, a.nx),
                           'ms': dt * 1e3, 'Mpx_t_per_s': n / dt / 1e6, 'GBps_algorithmic': 8 * n / dt / 1e9,
-                          'frac_hbm_peak': 8 * n / dt / 8e12, 'kernels_ms': km,
-                          'tiled': os.environ.get('ND_AMD_NO_TILED') is None}))
+                          'frac_hbm_peak': 8 * n / dt / 8e12, 'kernels_ms': km}))
     elif a.what == 'gaussian':
         x = torch.rand((a.k, a.ny, a.nx), generator=g, device=dev) + 0.5
         out = torch.empty_like(x)

@@ -63,8 +63,6 @@ VARIANTS = {
     # pass A: each XCD (block index mod 8) / each of 32 groups walks its own contiguous part of the raster
     'a_xcd8': [('omnibus_c2_retain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)\n{\n    const int tid = threadIdx.x;\n    const int lane = tid & 63;\n    const int64_t b = blockIdx.x;', 'omnibus_c2_retain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)\n{\n    const int tid = threadIdx.x;\n    const int lane = tid & 63;\n    const int64_t nb_ = gridDim.x, per_ = nb_ >> 3;\n    const int64_t b = (nb_ & 7) ? (int64_t)blockIdx.x : ((int64_t)(blockIdx.x & 7) * per_ + (blockIdx.x >> 3));')],
     'a_grp32': [('omnibus_c2_retain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)\n{\n    const int tid = threadIdx.x;\n    const int lane = tid & 63;\n    const int64_t b = blockIdx.x;', 'omnibus_c2_retain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)\n{\n    const int tid = threadIdx.x;\n    const int lane = tid & 63;\n    const int64_t nb_ = gridDim.x, per_ = nb_ >> 5;\n    const int64_t b = (nb_ & 31) ? (int64_t)blockIdx.x : ((int64_t)(blockIdx.x & 31) * per_ + (blockIdx.x >> 5));')],
-    # pass A block size
-    't128': [("#define ND_RETAIN_THREADS 256", "#define ND_RETAIN_THREADS 128")],
 }
 
 # name -> extra hipcc flags

@@ -1,7 +1,8 @@
 """patch_mode 1 with a search extent along time (the tutorial's window, signed patch distances): the tiled kernel of
-round 6 (nlmeans_patch3_kernel) against the per-pixel kernel (ND_AMD_NLM_NOPATCH3=1), 4 variables, 6 x 1024 x 2048.
-    python tools/exp_nlm_patch3.py            # both forms, one child process each"""
-import json, os, subprocess, sys, time
+round 6 (nlmeans_patch3_kernel), 4 variables, 6 x 1024 x 2048.  (The comparison with the per-pixel kernel it replaced:
+DESIGN-EXPERIMENTS.md, round 6.)
+    python tools/exp_nlm_patch3.py"""
+import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 
 
@@ -34,11 +35,4 @@ def child(tag):
 
 
 if __name__ == '__main__':
-    if len(sys.argv) > 2 and sys.argv[1] == 'child':
-        child(sys.argv[2])
-    else:
-        for tag, env in (('tiled (nlmeans_patch3_kernel)', {}), ('per-pixel kernel', {'ND_AMD_NLM_NOPATCH3': '1'})):
-            e = dict(os.environ); e.update(env)
-            rc = subprocess.call([sys.executable, os.path.abspath(__file__), 'child', tag], env=e)
-            if rc:
-                sys.exit(rc)
+    child('tiled (nlmeans_patch3_kernel)')

@@ -1,4 +1,4 @@
-"""Tuning experiment (GPU box): pass-A bandwidth under layout / build variants + raw read probes."""
+"""Tuning experiment (GPU box): pass-A bandwidth under layout variants + raw read probes."""
 import ctypes as C, os, subprocess, sys, json, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -68,11 +68,9 @@ if __name__ == '__main__':
         sys.exit(0)
     probes()
     from nd_amd import build
-    variants = {'base': [], 'tch2': ['-DND_TIME_CHUNK=2'], 'tch8': ['-DND_TIME_CHUNK=8']}
-    for name, flags in variants.items():
-        so = os.path.join(OUT, 'libnd_amd_%s.so' % name)
-        build.build(extra_flags=flags, out=so)
-        for pad in ((0, 64, 1024) if name == 'base' else (0,)):
-            env = dict(os.environ, ND_AMD_LIB=so)
-            r = subprocess.run([sys.executable, __file__, 'child', str(pad)], env=env, capture_output=True, text=True)
-            print(name, r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-500:])
+    so = os.path.join(OUT, 'libnd_amd_base.so')
+    build.build(out=so)
+    for pad in (0, 64, 1024):
+        env = dict(os.environ, ND_AMD_LIB=so)
+        r = subprocess.run([sys.executable, __file__, 'child', str(pad)], env=env, capture_output=True, text=True)
+        print('base', r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-500:])

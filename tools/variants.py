@@ -18,7 +18,7 @@ VARIANTS = {
     # pm_temporal (C11 / C22 pieces with plain instead of non-temporal loads): adopted, 1.86 -> 1.49 ms
     # pm_direct_c12 (C12 straight into registers, no LDS image): 1.49 against 1.45 ms -- no gain, code removed
     # mlw_* (wave-private form of the fused multilooking kernel): 2.30 - 2.69 ms against 2.04 ms -- lost, code removed
-    # ml_pf* (L2 prefetch by the idle waves, -DND_ML_PREFETCH=n): 2.14 / 3.27 ms against 2.03 / 3.13 -- lost
+    # ml_pf* (L2 prefetch by the idle waves, n steps ahead): 2.14 / 3.27 ms against 2.03 / 3.13 -- lost
     # ---- round 6: the time-split pass A of the full-pol test (omnibus_c3_retain_kernel) ----
     # timing only, NOT a correct screen: no per-date PSD check, no exponent tracking -- what the checks cost
     'c3_nocheck': ('omnibus_c3.hip', [
