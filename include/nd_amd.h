@@ -74,6 +74,8 @@ extern "C" {
 #define ND_AMD_KERNEL_CLASSIFY_KMEANS 18  /* nd_amd_classify_kmeans */
 #define ND_AMD_KERNEL_CLASSIFY_GATHER 19  /* nd_amd_classify_select (mask + scan) and nd_amd_classify_gather */
 #define ND_AMD_KERNEL_CLASS_MEAN      20  /* nd_amd_class_stats and nd_amd_class_fill */
+#define ND_AMD_KERNEL_CLASSIFY_KNN    21  /* nd_amd_classify_knn */
+#define ND_AMD_KERNEL_CLASSIFY_LINEAR 22  /* nd_amd_classify_linear */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -82,6 +84,17 @@ extern "C" {
 /* rows per block of nd_amd_classify_select / _gather: block_offsets has one entry per that many rows */
 #define ND_AMD_CLASSIFY_BLOCK_ROWS 1024
 #define ND_AMD_CLASSIFY_MAX_FEATURES 1024
+/* nd_amd_classify_knn: neighbours and features it serves, and the training samples of one tile */
+#define ND_AMD_CLASSIFY_KNN_MAX_K 32
+#define ND_AMD_CLASSIFY_KNN_MAX_FEATURES 128
+#define ND_AMD_CLASSIFY_KNN_TILE 8
+/* nd_amd_classify_linear: link (what predict_proba applies to the decision values) and output */
+#define ND_AMD_LINK_NONE    0
+#define ND_AMD_LINK_SOFTMAX 1   /* exp(s_c - max s) / sum, in class order */
+#define ND_AMD_LINK_OVR     2   /* expit(s_c), divided by their sum when there are more than two classes */
+#define ND_AMD_LINEAR_LABELS   0
+#define ND_AMD_LINEAR_DECISION 1
+#define ND_AMD_LINEAR_PROBA    2
 
 #define ND_AMD_COREG_MAX_UPSAMPLING 128
 #define ND_AMD_COREG_MAX_VARS       16
@@ -529,7 +542,7 @@ int nd_amd_rgb_compose(const void *const *num, const void *const *den, int nchan
                        const uint8_t *mask, uint8_t *out, void *hip_stream);
 
 /* ------------------------------------------------------------------------
- * Pixel classification (nd/classify.py).  Common to the four nd_amd_classify_*
+ * Pixel classification (nd/classify.py).  Common to the nd_amd_classify_*
  * entries: the FEATURE TABLE.  The reference stacks every variable into a host
  * matrix X of (rows, nfeat) (_build_X, nd/classify.py:47-59); here X is never
  * formed.  feat: host array of nfeat (1 .. ND_AMD_CLASSIFY_MAX_FEATURES) device
@@ -591,6 +604,51 @@ int nd_amd_classify_forest(const void *const *feat, int nfeat, int dtype, const 
 int nd_amd_classify_kmeans(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
                            const int64_t *strides, const double *centers, int k, const double *mean,
                            const double *scale, double *labels, void *workspace, size_t workspace_bytes,
+                           void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * k nearest neighbours.  Replaces  KNeighborsClassifier.predict(X) / .predict_proba(X)
+ * (nd/classify.py:232) for uniform weights and the Euclidean metric.
+ * train: device, (ntrain, nfeat) doubles, the fitted samples (_fit_X).  target:
+ * device, ntrain int32, each sample's index into classes (_y).  classes: device,
+ * nclasses doubles.  1 <= k <= min(ND_AMD_CLASSIFY_KNN_MAX_K, ntrain) and
+ * nfeat <= ND_AMD_CLASSIFY_KNN_MAX_FEATURES, else ND_AMD_EUNSUPPORTED.
+ * Per row, with x_f the (scaled) feature in type T:
+ *   d_j = sum over f, in feature order and in float64, of (double(x_f) - train[j, f])^2
+ * (the product and the sum are two roundings).  The neighbours are the k samples
+ * smallest by (d_j, j): of two samples at the same distance the one with the
+ * lower index is nearer.  proba[r, c] = (neighbours of class c) / k in float64;
+ * labels[r] = classes[first c with the largest count].  A row with a NaN feature
+ * gives NaN in labels and in every proba.  labels: device, rows doubles, or NULL.
+ * proba: device, (rows, nclasses) doubles, or NULL.  Not both NULL.  The caller
+ * guarantees 0 <= target[j] < nclasses and finite train.
+ * ---------------------------------------------------------------------- */
+int nd_amd_classify_knn(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                        const int64_t *strides, const double *train, const int32_t *target, int ntrain,
+                        int k, const double *classes, int nclasses, const double *mean, const double *scale,
+                        double *labels, double *proba, void *workspace, size_t workspace_bytes,
+                        void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Linear classifiers.  Replaces  decision_function / predict / predict_proba of
+ * scikit-learn's linear models (LinearClassifierMixin, LogisticRegression).
+ * coef: device, (ncoef, nfeat) doubles; intercept: device, ncoef doubles.  A
+ * binary model has ncoef = 1 and two classes, any other ncoef classes.  classes:
+ * device doubles.  Per row, with x_f the (scaled) feature in type T:
+ *   s_c = intercept[c] + sum over f, in feature order and in float64, of double(x_f) * coef[c, f]
+ * (the product and the sum are two roundings).  out: device doubles,
+ *   ND_AMD_LINEAR_LABELS    (rows): classes[s > 0] for a binary model, else classes[first c with the largest s_c]
+ *   ND_AMD_LINEAR_DECISION  (rows, ncoef): s
+ *   ND_AMD_LINEAR_PROBA     (rows, classes): by `link`.  ND_AMD_LINK_SOFTMAX: e_c = exp(s_c - max s),
+ *       p_c = e_c / sum e in class order; a binary model takes the softmax of (-s, s).
+ *       ND_AMD_LINK_OVR: p_c = expit(s_c), divided by their sum in class order; a binary model gives
+ *       (1 - p, p).  ND_AMD_LINK_NONE with this output is refused.
+ * A row with a NaN feature gives NaN in every output.
+ * ---------------------------------------------------------------------- */
+int nd_amd_classify_linear(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                           const int64_t *strides, const double *coef, const double *intercept, int ncoef,
+                           const double *classes, int link, int output, const double *mean,
+                           const double *scale, double *out, void *workspace, size_t workspace_bytes,
                            void *hip_stream);
 
 /* ------------------------------------------------------------------------

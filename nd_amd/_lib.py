@@ -19,7 +19,8 @@ KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 4: 'nlmeans', 5: 'boxcar_tiled', 6: 'nlmeans_tiled', 7: 'correlate1d',
                 8: 'relayout', 9: 'omnibus_c2_dense', 10: 'omnibus_c2_fused', 11: 'omnibus_c2_sample', 12: 'omnibus_c2_exact',
                 13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose',
-                17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean'}
+                17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean',
+                21: 'classify_knn', 22: 'classify_linear'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 
 # every symbol include/nd_amd.h declares
@@ -37,8 +38,12 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_warp_translate_workspace_bytes', 'nd_amd_warp_translate',
            'nd_amd_rgb_limits_workspace_bytes', 'nd_amd_rgb_limits', 'nd_amd_rgb_compose',
            'nd_amd_classify_workspace_bytes', 'nd_amd_classify_forest', 'nd_amd_classify_kmeans',
-           'nd_amd_classify_select', 'nd_amd_classify_gather', 'nd_amd_class_stats', 'nd_amd_class_fill')
+           'nd_amd_classify_select', 'nd_amd_classify_gather', 'nd_amd_class_stats', 'nd_amd_class_fill',
+           'nd_amd_classify_knn', 'nd_amd_classify_linear')
 CLASSIFY_BLOCK_ROWS, CLASSIFY_MAX_FEATURES = 1024, 1024
+CLASSIFY_KNN_MAX_K, CLASSIFY_KNN_MAX_FEATURES, CLASSIFY_KNN_TILE = 32, 128, 8
+LINKS = {'none': 0, 'softmax': 1, 'ovr': 2}
+LINEAR_OUTPUTS = {'predict': 0, 'decision_function': 1, 'predict_proba': 2}
 
 _lib = None
 
@@ -146,6 +151,10 @@ def lib():
     L.nd_amd_classify_forest.argtypes = table + [vp, i64, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, C.c_size_t, vp]
     L.nd_amd_classify_kmeans.restype = i32
     L.nd_amd_classify_kmeans.argtypes = table + [vp, i32, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_classify_knn.restype = i32
+    L.nd_amd_classify_knn.argtypes = table + [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_classify_linear.restype = i32
+    L.nd_amd_classify_linear.argtypes = table + [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]
     L.nd_amd_classify_select.restype = i32
     L.nd_amd_classify_select.argtypes = table + [vp, pi64, vp, vp, vp, vp, C.c_size_t, vp]
     L.nd_amd_classify_gather.restype = i32

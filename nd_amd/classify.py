@@ -3,7 +3,8 @@ nd_amd/classify.py -- pixel classification (nd/classify.py) with prediction on t
 
   Classifier      nd.classify.Classifier: make_Xy, fit, predict, fit_predict, score
   class_mean      nd.classify.class_mean
-  ForestModel, KMeansModel, predict_forest, predict_kmeans
+  ForestModel, KMeansModel, KNNModel, LinearModel,
+  predict_forest, predict_kmeans, predict_knn, predict_linear
                   the device path for callers that hold a fitted model as plain arrays
 
 Training is scikit-learn's and runs on the host: it sees only the labelled pixels and is not a hot path.
@@ -18,6 +19,18 @@ Supported for `predict` (anything else raises NotImplementedError; there is no C
   scikit-learn 1.7.2 at n_jobs=1 (with n_jobs > 1 scikit-learn adds the trees in thread order and does
   not reproduce its own last bit); labels are equal everywhere, ties included.
   KMeans, MiniBatchKMeans: func='predict', the first nearest centre in float64.
+  KNeighborsClassifier with uniform weights, the Euclidean metric, dense training data, one output, numeric
+  classes_ and n_neighbors <= 32, on up to 128 features: func='predict' and func='predict_proba'.  With
+  d_j = sum_f (x_f - t_jf)^2 in float64, summed in feature order, the neighbours are the k training samples
+  smallest by (d_j, j) -- a tie in distance goes to the lower training index --, predict_proba is count_c / k
+  and predict the first class with the largest count.  This does not depend on scikit-learn's search
+  structure; scikit-learn agrees wherever the k-th and (k+1)-th distances are not within rounding.
+  LogisticRegression: func='predict' and func='predict_proba'; LinearSVC, RidgeClassifier, SGDClassifier,
+  Perceptron, PassiveAggressiveClassifier: func='predict'; one output, dense coef_, numeric classes_.
+  s_c = b_c + sum_f x_f w_cf in float64, summed in feature order; predict is s > 0 for a binary model, else the
+  first maximum; predict_proba applies the link LogisticRegression.predict_proba applies: softmax with the
+  row maximum subtracted where the model is multinomial, expit normalised over the classes where it is
+  one-vs-rest, [1 - p, p] for a binary model.
 
 Row order and feature order are the reference's (_build_X, _get_data_dims): rows run over the data
 dimensions in the order of the dataset's dimension coordinates (for an xr_lite object without coordinates:
@@ -31,14 +44,22 @@ import numpy as np
 
 from . import _adapter, _device, xr_lite
 
-__all__ = ['Classifier', 'class_mean', 'ForestModel', 'KMeansModel', 'predict_forest', 'predict_kmeans',
-           'pack_forest']
+__all__ = ['Classifier', 'class_mean', 'ForestModel', 'KMeansModel', 'KNNModel', 'LinearModel', 'predict_forest',
+           'predict_kmeans', 'predict_knn', 'predict_linear', 'pack_forest']
 
 FORESTS = ('DecisionTreeClassifier', 'ExtraTreeClassifier', 'RandomForestClassifier', 'ExtraTreesClassifier')
 KMEANS = ('KMeans', 'MiniBatchKMeans')
+KNN = ('KNeighborsClassifier',)
+LINEAR_PROBA = ('LogisticRegression',)
+LINEAR_PREDICT = ('LinearSVC', 'RidgeClassifier', 'SGDClassifier', 'Perceptron', 'PassiveAggressiveClassifier')
+KNN_MAX_K, KNN_MAX_FEATURES = 32, 128
 _SUPPORTED = ('nd_amd.classify predicts on the device with %s (func "predict" or "predict_proba"; one output, '
-              'numeric classes_) and %s (func "predict"); there is no CPU fallback.  '
-              % (', '.join(FORESTS), ', '.join(KMEANS)))
+              'numeric classes_), %s (func "predict"), %s (func "predict" or "predict_proba"; uniform weights, '
+              'Euclidean metric, dense training data, n_neighbors <= %d, up to %d features, one output, numeric '
+              'classes_), %s (func "predict" or "predict_proba") and %s (func "predict"; linear models with one '
+              'output, dense coef_ and numeric classes_); there is no CPU fallback.  '
+              % (', '.join(FORESTS), ', '.join(KMEANS), ', '.join(KNN), KNN_MAX_K, KNN_MAX_FEATURES,
+                 ', '.join(LINEAR_PROBA), ', '.join(LINEAR_PREDICT)))
 
 
 # ---------------------------------------------------------------------------
@@ -185,15 +206,155 @@ class KMeansModel:
         return self._device[dev]
 
 
+def _numeric_classes(classes):
+    classes = np.asarray(classes)
+    if classes.dtype.kind not in 'iufb':
+        raise NotImplementedError(_SUPPORTED + 'classes_ of type %s are not numeric.' % classes.dtype)
+    return np.ascontiguousarray(classes, np.float64)
+
+
+def _is_sparse(a):
+    return hasattr(a, 'toarray') and not isinstance(a, np.ndarray)
+
+
+class KNNModel:
+    """A fitted k-nearest-neighbours classifier as arrays (uniform weights, Euclidean metric).
+    train : (n_train, n_features) the fitted samples, held as float64
+    target : (n_train,) each sample's index into `classes`
+    classes : (n_classes,) numeric classes_
+    n_neighbors : 1 .. min(32, n_train)"""
+
+    def __init__(self, train, target, classes, n_neighbors):
+        if _is_sparse(train):
+            raise NotImplementedError(_SUPPORTED + 'Got sparse training data.')
+        self.train = np.ascontiguousarray(train, np.float64)
+        self.target = np.ascontiguousarray(target, np.int64)
+        self.classes = _numeric_classes(classes)
+        if self.train.ndim != 2 or self.train.shape[0] < 1 or self.train.shape[1] < 1:
+            raise ValueError('KNNModel: train must be (n_train, n_features)')
+        if self.target.ndim == 2 and self.train.shape[0] == self.target.shape[0]:
+            raise NotImplementedError(_SUPPORTED + 'Got a multi-output target.')
+        if self.target.shape != (self.train.shape[0],) or self.classes.ndim != 1 or self.classes.size < 1:
+            raise ValueError('KNNModel: target must be (n_train,) and classes (n_classes,)')
+        if self.target.min() < 0 or self.target.max() >= self.classes.size:
+            raise ValueError('KNNModel: a target lies outside classes')
+        if not np.isfinite(self.train).all():
+            raise ValueError('KNNModel: a training sample is not finite')
+        if self.train.shape[0] >= 2 ** 31:
+            raise ValueError('KNNModel: too many training samples')
+        k = int(n_neighbors)
+        if k != n_neighbors or not 1 <= k <= self.train.shape[0]:
+            raise ValueError('KNNModel: n_neighbors = %r for %d training samples' % (n_neighbors, self.train.shape[0]))
+        if k > KNN_MAX_K:
+            raise NotImplementedError(_SUPPORTED + 'Got n_neighbors=%d.' % k)
+        self.n_neighbors = k
+        self.n_features = self.train.shape[1]
+        self._device = {}
+
+    n_train = property(lambda self: self.train.shape[0])
+    n_classes = property(lambda self: self.classes.size)
+
+    @classmethod
+    def from_sklearn(cls, clf):
+        names = {c.__name__ for c in type(clf).__mro__}
+        if not names & set(KNN):
+            raise NotImplementedError(_SUPPORTED + 'Got %s.' % type(clf).__name__)
+        from sklearn.utils.validation import check_is_fitted
+        check_is_fitted(clf)
+        if clf.weights not in (None, 'uniform'):
+            raise NotImplementedError(_SUPPORTED + 'Got weights=%r.' % (clf.weights,))
+        metric, params = clf.effective_metric_, getattr(clf, 'effective_metric_params_', None) or {}
+        if not (metric == 'euclidean' or (metric == 'minkowski' and params.get('p', 2) == 2
+                                          and params.get('w') is None)):
+            raise NotImplementedError(_SUPPORTED + 'Got metric=%r %r.' % (metric, params))
+        if getattr(clf, 'outputs_2d_', False) or np.ndim(clf._y) != 1:
+            raise NotImplementedError(_SUPPORTED + 'Got a multi-output %s.' % type(clf).__name__)
+        if _is_sparse(clf._fit_X):
+            raise NotImplementedError(_SUPPORTED + 'Got sparse training data.')
+        return cls(clf._fit_X, clf._y, clf.classes_, clf.n_neighbors)
+
+    def _on(self, dev):
+        import torch
+        if dev not in self._device:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            self._device[dev] = (up(self.train), up(self.target.astype(np.int32)), up(self.classes))
+        return self._device[dev]
+
+
+class LinearModel:
+    """A fitted linear classifier as arrays.
+    coef : (n_rows, n_features) float64; a binary model has one row
+    intercept : (n_rows,) float64 (a scalar is repeated)
+    classes : numeric classes_: 2 for one row, else n_rows
+    link : what predict_proba applies to the decision values: 'none' (no predict_proba), 'softmax' or
+        'ovr' (expit, normalised over the classes when there are more than two)"""
+
+    def __init__(self, coef, intercept, classes, link='none'):
+        if _is_sparse(coef):
+            raise NotImplementedError(_SUPPORTED + 'Got a sparse coef_.')
+        self.coef = np.array(coef, np.float64, order='C')         # a copy: partial_fit changes coef_ in place
+        self.classes = _numeric_classes(classes)
+        if self.coef.ndim != 2 or self.coef.shape[0] < 1 or self.coef.shape[1] < 1:
+            raise ValueError('LinearModel: coef must be (n_rows, n_features)')
+        n = self.coef.shape[0]
+        self.intercept = np.ascontiguousarray(np.broadcast_to(np.asarray(intercept, np.float64).reshape(-1), (n,)))
+        if self.classes.shape != ((2,) if n == 1 else (n,)):
+            raise ValueError('LinearModel: %d rows of coefficients need %d classes, got %s'
+                             % (n, 2 if n == 1 else n, self.classes.shape))
+        if link not in ('none', 'softmax', 'ovr'):
+            raise ValueError("LinearModel: link must be 'none', 'softmax' or 'ovr'")
+        self.link = link
+        self.n_features = self.coef.shape[1]
+        self._device = {}
+
+    n_classes = property(lambda self: self.classes.size)
+
+    @classmethod
+    def from_sklearn(cls, clf):
+        names = {c.__name__ for c in type(clf).__mro__}
+        if not names & set(LINEAR_PROBA + LINEAR_PREDICT):
+            raise NotImplementedError(_SUPPORTED + 'Got %s.' % type(clf).__name__)
+        from sklearn.utils.validation import check_is_fitted
+        check_is_fitted(clf)
+        if _is_sparse(clf.coef_):
+            raise NotImplementedError(_SUPPORTED + 'Got a sparse coef_.')
+        classes = clf.classes_
+        if isinstance(classes, list) or np.ndim(classes) != 1 or np.ndim(clf.coef_) != 2:
+            raise NotImplementedError(_SUPPORTED + 'Got a multi-output %s.' % type(clf).__name__)
+        n = 1 if len(classes) <= 2 else len(classes)
+        if clf.coef_.shape[0] != n:      # RidgeClassifier on a label indicator matrix: one row per output
+            raise NotImplementedError(_SUPPORTED + 'Got a multi-output %s.' % type(clf).__name__)
+        link = 'none'
+        if names & set(LINEAR_PROBA):
+            # LogisticRegression.predict_proba (scikit-learn 1.7.2)
+            multi_class = getattr(clf, 'multi_class', 'deprecated')
+            ovr = multi_class in ('ovr', 'warn') or (multi_class in ('auto', 'deprecated') and
+                                                      (len(classes) <= 2 or clf.solver == 'liblinear'))
+            link = 'ovr' if ovr else 'softmax'
+        return cls(clf.coef_, clf.intercept_, classes, link)
+
+    def _on(self, dev):
+        import torch
+        if dev not in self._device:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            self._device[dev] = (up(self.coef), up(self.intercept), up(self.classes))
+        return self._device[dev]
+
+
 def _fitted_state(clf):
-    """what a model was built from: ('trees', the tree_ objects in estimator order) or ('centres', a copy
-    of cluster_centers_); None for an estimator that holds neither (unfitted)"""
+    """what a model was built from: ('trees', the tree_ objects in estimator order), ('centres', a copy of
+    cluster_centers_), ('knn', the fitted samples and targets themselves, and n_neighbors) or ('linear',
+    copies of coef_ and intercept_); None for an estimator that holds none of them (unfitted)"""
     if hasattr(clf, 'estimators_'):
         return 'trees', [getattr(e, 'tree_', None) for e in clf.estimators_]
     if getattr(clf, 'tree_', None) is not None:
         return 'trees', [clf.tree_]
     if getattr(clf, 'cluster_centers_', None) is not None:
         return 'centres', np.array(clf.cluster_centers_, copy=True)
+    if getattr(clf, '_fit_X', None) is not None:
+        return 'knn', (clf._fit_X, getattr(clf, '_y', None), getattr(clf, 'n_neighbors', None))
+    if getattr(clf, 'coef_', None) is not None and not _is_sparse(clf.coef_):
+        return 'linear', (np.array(clf.coef_, copy=True), np.array(getattr(clf, 'intercept_', 0.0), copy=True))
     return None
 
 
@@ -202,6 +363,11 @@ def _same_state(a, b):
         return False
     if a[0] == 'trees':
         return len(a[1]) == len(b[1]) and all(x is y and x is not None for x, y in zip(a[1], b[1]))
+    if a[0] == 'knn':
+        return a[1][0] is b[1][0] and a[1][1] is b[1][1] and a[1][1] is not None and a[1][2] == b[1][2]
+    if a[0] == 'linear':
+        return all(x.shape == y.shape and x.dtype == y.dtype and bool(np.array_equal(x, y))
+                   for x, y in zip(a[1], b[1]))
     return a[1].shape == b[1].shape and a[1].dtype == b[1].dtype and bool(np.array_equal(a[1], b[1]))
 
 
@@ -216,6 +382,15 @@ def _model_for(clf, func, build=True):
         if func != 'predict':
             raise NotImplementedError(_SUPPORTED + 'Got func=%r for %s.' % (func, type(clf).__name__))
         return KMeansModel.from_sklearn(clf) if build else None
+    if names & set(KNN):
+        if func not in ('predict', 'predict_proba'):
+            raise NotImplementedError(_SUPPORTED + 'Got func=%r for %s.' % (func, type(clf).__name__))
+        return KNNModel.from_sklearn(clf) if build else None
+    if names & set(LINEAR_PROBA + LINEAR_PREDICT):
+        served = ('predict', 'predict_proba') if names & set(LINEAR_PROBA) else ('predict',)
+        if func not in served:
+            raise NotImplementedError(_SUPPORTED + 'Got func=%r for %s.' % (func, type(clf).__name__))
+        return LinearModel.from_sklearn(clf) if build else None
     raise NotImplementedError(_SUPPORTED + 'Got %s.' % type(clf).__name__)
 
 
@@ -397,6 +572,45 @@ def predict_kmeans(ds, model, feature_dims=(), scaler=None):
     return layout.wrap(labels)
 
 
+def predict_knn(ds, model, feature_dims=(), func='predict', scaler=None):
+    """`model` (a KNNModel) applied to every pixel of `ds` on the device.  func: 'predict' or 'predict_proba'.
+    The neighbours of a pixel are the n_neighbors training samples smallest by (squared distance in float64,
+    summed in feature order; training index): predict_proba is count_c / n_neighbors, predict the first class
+    with the largest count.  Returns a float64 DataArray over the data dimensions (with a trailing `label`
+    dimension for predict_proba), NaN where any feature of the pixel is NaN."""
+    from . import kernels
+    if func not in ('predict', 'predict_proba'):
+        raise NotImplementedError(_SUPPORTED + 'Got func=%r.' % func)
+    layout = _Layout(ds, feature_dims)
+    _check_features(layout, model)
+    if layout.n_features > KNN_MAX_FEATURES:
+        raise NotImplementedError(_SUPPORTED + 'Got %d features.' % layout.n_features)
+    mean, scale = _scaler_arrays(scaler)
+    train, target, classes = model._on(layout.device)
+    proba = func == 'predict_proba'
+    labels, p = kernels.classify_knn(layout.features, layout.shape, layout.strides, train, target, classes,
+                                     model.n_neighbors, mean, scale, want_labels=not proba, want_proba=proba)
+    return layout.wrap(p, 'label') if proba else layout.wrap(labels)
+
+
+def predict_linear(ds, model, feature_dims=(), func='predict', scaler=None):
+    """`model` (a LinearModel) applied to every pixel of `ds` on the device.  func: 'predict',
+    'predict_proba' (a model with a link) or 'decision_function' (s_c = b_c + sum_f x_f w_cf in float64,
+    summed in feature order, with a trailing `label` dimension of one entry per row of coefficients).
+    Returns a float64 DataArray over the data dimensions, NaN where any feature of the pixel is NaN."""
+    from . import kernels
+    if func not in ('predict', 'predict_proba', 'decision_function') or (func == 'predict_proba'
+                                                                          and model.link == 'none'):
+        raise NotImplementedError(_SUPPORTED + 'Got func=%r.' % func)
+    layout = _Layout(ds, feature_dims)
+    _check_features(layout, model)
+    mean, scale = _scaler_arrays(scaler)
+    coef, intercept, classes = model._on(layout.device)
+    out = kernels.classify_linear(layout.features, layout.shape, layout.strides, coef, intercept, classes,
+                                  model.link, func, mean, scale)
+    return layout.wrap(out) if func == 'predict' else layout.wrap(out, 'label')
+
+
 # ---------------------------------------------------------------------------
 # nd.classify.Classifier
 # ---------------------------------------------------------------------------
@@ -465,13 +679,18 @@ class Classifier:
             scaler = self._scaler
         if isinstance(model, ForestModel):
             return predict_forest(ds, model, self.feature_dims, func, scaler)
+        if isinstance(model, KNNModel):
+            return predict_knn(ds, model, self.feature_dims, func, scaler)
+        if isinstance(model, LinearModel):
+            return predict_linear(ds, model, self.feature_dims, func, scaler)
         return predict_kmeans(ds, model, self.feature_dims, scaler)
 
     def _cached_model(self, func):
         """The arrays of the fitted estimator, packed and uploaded once while the fitted state stays what it
         was.  The state is compared by content where scikit-learn may change it in place: the tree objects
-        of every estimator, one by one (warm_start extends estimators_ in place), and a copy of the k-means
-        centres (partial_fit updates cluster_centers_ in place)."""
+        of every estimator, one by one (warm_start extends estimators_ in place), a copy of the k-means
+        centres and of a linear model's coef_ and intercept_ (partial_fit updates them in place).  A k-NN fit
+        replaces _fit_X and _y, so they are compared by identity, with n_neighbors beside them."""
         clf = self.clf
         _model_for(clf, func, build=False)
         state = _fitted_state(clf)

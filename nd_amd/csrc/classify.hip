@@ -1,6 +1,8 @@
 // nd_amd/csrc/classify.hip -- pixel classification (nd/classify.py) on the device:
 //   nd_amd_classify_forest   decision-forest predict / predict_proba, scikit-learn's arithmetic
 //   nd_amd_classify_kmeans   nearest centre in float64
+//   nd_amd_classify_knn      k nearest training samples in float64, votes and labels
+//   nd_amd_classify_linear   decision values of a linear model, labels and probabilities
 //   nd_amd_classify_select / _gather   the training rows, compacted in row order
 //   nd_amd_class_stats / _fill         per-class statistics and the fill of class_mean
 // No (rows, features) matrix is ever formed: a row's feature f is read from feat[f] + row offset.
@@ -434,6 +436,243 @@ __global__ __launch_bounds__(BLOCK) void class_fill_kernel(
     }
 }
 
+// ---- k nearest neighbours ---------------------------------------------------------------------
+// One lane per row.  Every lane of a wave meets training sample j at the same time, so a sample's
+// features are wave-uniform loads (scalar registers feed the float64 subtraction directly) and the
+// kernel needs no barrier.  The samples are walked in tiles of KNN_TILE: the tile's distances are formed
+// first (their loads issue together), then each is offered to the row's best list.
+// The k best (distance, index) pairs are CAP registers kept sorted by an unrolled compare-and-shift
+// chain; no element is ever addressed by a run-time index.  `kth` is the distance at position k - 1,
+// refreshed after every insertion, so a candidate costs one comparison unless it enters.  Samples
+// arrive in index order: a candidate that ties with a held one is the farther of the two.
+// NF > 0: the row's NF features are registers.  NF == 0: the block's rows lie in LDS, feature-major
+// (xs[f * blockDim.x + lane]: a wave reads consecutive addresses, and a lane only its own column).
+constexpr int KNN_TILE = ND_AMD_CLASSIFY_KNN_TILE;
+constexpr int KNN_LDS_BYTES = 65536;
+
+template <int CAP>
+struct KnnBest {
+    double d[CAP];
+    int i[CAP];
+    double kth;
+};
+
+template <int CAP>
+__device__ __forceinline__ void knn_offer(KnnBest<CAP> &b, double d, int j, int k)
+{
+    if (d < b.kth) {
+#pragma unroll
+        for (int s = CAP - 1; s > 0; s--) {
+            const bool up = d < b.d[s - 1];
+            const bool here = !up && d < b.d[s];
+            b.i[s] = up ? b.i[s - 1] : (here ? j : b.i[s]);
+            b.d[s] = up ? b.d[s - 1] : (here ? d : b.d[s]);
+        }
+        if (d < b.d[0]) {
+            b.d[0] = d;
+            b.i[0] = j;
+        }
+        double kth = b.d[0];
+#pragma unroll
+        for (int s = 1; s < CAP; s++) kth = (s == k - 1) ? b.d[s] : kth;
+        b.kth = kth;
+    }
+}
+
+template <int NF, int TJ, typename T>
+__device__ __forceinline__ void knn_distances(double (&d)[TJ], const double (&x)[NF > 0 ? NF : 1], const T *xs,
+                                              int xstride, const double *__restrict__ train, int nfeat, int j)
+{
+#pragma unroll
+    for (int t = 0; t < TJ; t++) d[t] = 0.0;
+    if (NF > 0) {
+#pragma unroll
+        for (int t = 0; t < TJ; t++) {
+            const double *s = train + (int64_t)(j + t) * NF;
+#pragma unroll
+            for (int f = 0; f < NF; f++) {
+                const double e = x[f] - s[f];
+                d[t] += e * e;
+            }
+        }
+    } else {
+        const double *s = train + (int64_t)j * nfeat;
+        for (int f = 0; f < nfeat; f++) {
+            const double xv = (double)xs[f * xstride];
+#pragma unroll
+            for (int t = 0; t < TJ; t++) {
+                const double e = xv - s[(int64_t)t * nfeat + f];
+                d[t] += e * e;
+            }
+        }
+    }
+}
+
+template <typename T, int NF, int CAP>
+__global__ __launch_bounds__(BLOCK) void classify_knn_kernel(
+    const void *const *tab, int nfeat, RowDims R, int64_t rows, const double *__restrict__ train,
+    const int32_t *__restrict__ target, int ntrain, int k, const double *__restrict__ classes, int nclasses,
+    const double *__restrict__ mean, const double *__restrict__ scale, double *__restrict__ labels,
+    double *__restrict__ proba)
+{
+    extern __shared__ double knn_lds[];
+    const int bdim = blockDim.x;
+    const T *xs = reinterpret_cast<const T *>(knn_lds) + threadIdx.x;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    for (int64_t row = (int64_t)blockIdx.x * bdim + threadIdx.x; row < rows; row += (int64_t)gridDim.x * bdim) {
+        int64_t off, loff;
+        row_offsets(R, row, off, loff);
+        double x[NF > 0 ? NF : 1];
+        bool masked = false;
+        if (NF > 0) {
+#pragma unroll
+            for (int f = 0; f < NF; f++) {
+                const T v = static_cast<const T *>(tab[f])[off];
+                masked |= (v != v);
+                x[f] = (double)scaled<T>(v, mean, scale, f);
+            }
+        } else {
+            x[0] = 0.0;
+            T *w = reinterpret_cast<T *>(knn_lds) + threadIdx.x;
+            for (int f = 0; f < nfeat; f++) {
+                const T v = static_cast<const T *>(tab[f])[off];
+                masked |= (v != v);
+                w[f * bdim] = scaled<T>(v, mean, scale, f);
+            }
+        }
+        if (masked) {
+            if (labels) labels[row] = nan;
+            if (proba)
+                for (int c = 0; c < nclasses; c++) proba[row * nclasses + c] = nan;
+            continue;
+        }
+        KnnBest<CAP> b;
+#pragma unroll
+        for (int s = 0; s < CAP; s++) {
+            b.d[s] = INFINITY;
+            b.i[s] = 0;
+        }
+        b.kth = INFINITY;
+        int j = 0;
+        for (; j + KNN_TILE <= ntrain; j += KNN_TILE) {
+            double d[KNN_TILE];
+            knn_distances<NF, KNN_TILE, T>(d, x, xs, bdim, train, nfeat, j);
+#pragma unroll
+            for (int t = 0; t < KNN_TILE; t++) knn_offer<CAP>(b, d[t], j + t, k);
+        }
+        for (; j < ntrain; j++) {
+            double d[1];
+            knn_distances<NF, 1, T>(d, x, xs, bdim, train, nfeat, j);
+            knn_offer<CAP>(b, d[0], j, k);
+        }
+        // the neighbours' classes; positions k .. CAP-1 of the list are no neighbours
+        int tc[CAP];
+#pragma unroll
+        for (int s = 0; s < CAP; s++) tc[s] = (s < k) ? target[b.i[s]] : -1;
+        int bestn = -1, besti = 0;
+        for (int c = 0; c < nclasses; c++) {
+            int n = 0;
+#pragma unroll
+            for (int s = 0; s < CAP; s++) n += (tc[s] == c) ? 1 : 0;
+            if (proba) proba[row * nclasses + c] = (double)n / (double)k;
+            if (n > bestn) {
+                bestn = n;
+                besti = c;
+            }
+        }
+        if (labels) labels[row] = classes[besti];
+    }
+}
+
+// ---- linear classifiers -----------------------------------------------------------------------
+// One lane per row; a coefficient is the same for every lane: wave-uniform loads.  NC decision values
+// in registers; a model with more rows of coefficients is served in passes of NC that re-read the
+// features and keep a running maximum.  Probabilities are finished in the output itself: the decision
+// values are written there, then every lane re-reads its own row, so the sums run in class order for
+// any number of classes.
+__device__ __forceinline__ double expit(double s)
+{
+    if (s < 0.0) {
+        const double e = exp(s);
+        return e / (1.0 + e);
+    }
+    return 1.0 / (1.0 + exp(-s));
+}
+
+template <typename T, int NC>
+__global__ __launch_bounds__(BLOCK) void classify_linear_kernel(
+    const void *const *tab, int nfeat, RowDims R, int64_t rows, const double *__restrict__ coef,
+    const double *__restrict__ intercept, int ncoef, const double *__restrict__ classes, int link, int output,
+    const double *__restrict__ mean, const double *__restrict__ scale, double *__restrict__ out)
+{
+    __shared__ const void *sbase[MAX_LDS_FEATURES];
+    stage_table<0>(sbase, tab, nfeat);
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const int nclasses = ncoef == 1 ? 2 : ncoef;
+    const int width = output == ND_AMD_LINEAR_LABELS ? 1 : (output == ND_AMD_LINEAR_DECISION ? ncoef : nclasses);
+    for (int64_t row = (int64_t)blockIdx.x * BLOCK + threadIdx.x; row < rows; row += (int64_t)gridDim.x * BLOCK) {
+        int64_t off, loff;
+        row_offsets(R, row, off, loff);
+        double *o = out + row * width;
+        bool masked = false;
+        double best = -INFINITY;
+        int besti = 0;
+        for (int c0 = 0; c0 < ncoef && !masked; c0 += NC) {
+            double acc[NC];
+#pragma unroll
+            for (int c = 0; c < NC; c++) acc[c] = (c0 + c < ncoef) ? intercept[c0 + c] : 0.0;
+            for (int f = 0; f < nfeat; f++) {
+                const T v = static_cast<const T *>(sbase[f])[off];
+                masked |= (v != v);
+                const double xv = (double)scaled<T>(v, mean, scale, f);
+#pragma unroll
+                for (int c = 0; c < NC; c++)
+                    if (c0 + c < ncoef) acc[c] += xv * coef[(int64_t)(c0 + c) * nfeat + f];
+            }
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                if (c0 + c < ncoef) {
+                    if (output != ND_AMD_LINEAR_LABELS && ncoef > 1 && !masked) o[c0 + c] = acc[c];
+                    if (acc[c] > best) {
+                        best = acc[c];
+                        besti = c0 + c;
+                    }
+                }
+            }
+            if (ncoef == 1) best = acc[0];
+        }
+        if (masked) {
+            for (int c = 0; c < width; c++) o[c] = nan;
+            continue;
+        }
+        if (output == ND_AMD_LINEAR_LABELS) {
+            o[0] = ncoef == 1 ? classes[best > 0.0 ? 1 : 0] : classes[besti];
+        } else if (output == ND_AMD_LINEAR_DECISION) {
+            if (ncoef == 1) o[0] = best;
+        } else if (ncoef == 1) {
+            if (link == ND_AMD_LINK_SOFTMAX) {
+                const double m = fabs(best);
+                const double e0 = exp(-best - m), e1 = exp(best - m);
+                const double sum = e0 + e1;
+                o[0] = e0 / sum;
+                o[1] = e1 / sum;
+            } else {
+                const double p = expit(best);
+                o[0] = 1.0 - p;
+                o[1] = p;
+            }
+        } else {
+            double sum = 0.0;
+            for (int c = 0; c < ncoef; c++) {
+                const double p = link == ND_AMD_LINK_SOFTMAX ? exp(o[c] - best) : expit(o[c]);
+                o[c] = p;
+                sum += p;
+            }
+            for (int c = 0; c < ncoef; c++) o[c] = o[c] / sum;
+        }
+    }
+}
+
 // ---- host -------------------------------------------------------------------------------------
 // validate, drop dimensions of size 1, merge neighbours that are contiguous in both stride sets
 static int make_dims(const char *who, const int64_t *sizes, const int64_t *strides, const int64_t *lstrides,
@@ -802,6 +1041,162 @@ extern "C" int nd_amd_class_fill(const void *var, void *out, int dtype, const in
         else
             hipLaunchKernelGGL(class_fill_kernel<double>, dim3(grid), dim3(BLOCK), 0, st, (const double *)var,
                                (double *)out, R, rows, labels, nclasses, (const double *)fill);
+    }
+    ND_HIP_CHECK(hipGetLastError());
+    return ND_AMD_OK;
+}
+
+// rows of a block of the LDS form: the most of 256, 128, 64 whose image fits in KNN_LDS_BYTES
+static int knn_block_rows(int nfeat, size_t elem)
+{
+    int r = BLOCK;
+    while (r > 64 && (size_t)r * nfeat * elem > (size_t)KNN_LDS_BYTES) r >>= 1;
+    return r;
+}
+
+template <typename T, int NF>
+static void launch_knn(int cap, int grid, int block, size_t lds, hipStream_t st, const void *const *tab, int nfeat,
+                       const RowDims &R, int64_t rows, const double *train, const int32_t *target, int ntrain, int k,
+                       const double *classes, int nclasses, const double *mean, const double *scale, double *labels,
+                       double *proba)
+{
+#define ND_KNN(CAP)                                                                                              \
+    hipLaunchKernelGGL((classify_knn_kernel<T, NF, CAP>), dim3(grid), dim3(block), lds, st, tab, nfeat, R, rows, \
+                       train, target, ntrain, k, classes, nclasses, mean, scale, labels, proba)
+    if (cap <= 1) ND_KNN(1);
+    else if (cap <= 2) ND_KNN(2);
+    else if (cap <= 4) ND_KNN(4);
+    else if (cap <= 8) ND_KNN(8);
+    else if (cap <= 16) ND_KNN(16);
+    else ND_KNN(32);
+#undef ND_KNN
+}
+
+template <typename T>
+static void launch_knn_features(int nfeat, int cap, int64_t rows, hipStream_t st, const void *const *tab,
+                                const RowDims &R, const double *train, const int32_t *target, int ntrain, int k,
+                                const double *classes, int nclasses, const double *mean, const double *scale,
+                                double *labels, double *proba)
+{
+#define ND_ARGS st, tab, nfeat, R, rows, train, target, ntrain, k, classes, nclasses, mean, scale, labels, proba
+    const int grid = grid_for(rows);
+    switch (nfeat) {
+    case 1: launch_knn<T, 1>(cap, grid, BLOCK, 0, ND_ARGS); break;
+    case 2: launch_knn<T, 2>(cap, grid, BLOCK, 0, ND_ARGS); break;
+    case 3: launch_knn<T, 3>(cap, grid, BLOCK, 0, ND_ARGS); break;
+    case 4: launch_knn<T, 4>(cap, grid, BLOCK, 0, ND_ARGS); break;
+    case 5: launch_knn<T, 5>(cap, grid, BLOCK, 0, ND_ARGS); break;
+    case 6: launch_knn<T, 6>(cap, grid, BLOCK, 0, ND_ARGS); break;
+    case 7: launch_knn<T, 7>(cap, grid, BLOCK, 0, ND_ARGS); break;
+    case 8: launch_knn<T, 8>(cap, grid, BLOCK, 0, ND_ARGS); break;
+    default: {
+        const int block = knn_block_rows(nfeat, sizeof(T));
+        const int64_t b = ceil_div(rows, block);
+        launch_knn<T, 0>(cap, (int)(b < 8192 ? b : 8192), block, (size_t)block * nfeat * sizeof(T), ND_ARGS);
+    }
+    }
+#undef ND_ARGS
+}
+
+extern "C" int nd_amd_classify_knn(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                                   const int64_t *strides, const double *train, const int32_t *target, int ntrain,
+                                   int k, const double *classes, int nclasses, const double *mean,
+                                   const double *scale, double *labels, double *proba, void *workspace,
+                                   size_t workspace_bytes, void *hip_stream)
+{
+    const char *who = "nd_amd_classify_knn";
+    int rc = check_table(who, feat, nfeat, dtype, workspace, workspace_bytes);
+    if (rc != ND_AMD_OK) return rc;
+    RowDims R;
+    int64_t rows;
+    rc = make_dims(who, sizes, strides, nullptr, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (!train || !target || !classes || ntrain < 1 || nclasses < 1 || k < 1 || k > ntrain) {
+        set_error("%s: bad model (%d training samples, %d classes, k = %d)", who, ntrain, nclasses, k);
+        return ND_AMD_EINVAL;
+    }
+    if (k > ND_AMD_CLASSIFY_KNN_MAX_K || nfeat > ND_AMD_CLASSIFY_KNN_MAX_FEATURES) {
+        set_error("%s: serves k <= %d and up to %d features (k = %d, %d features)", who, ND_AMD_CLASSIFY_KNN_MAX_K,
+                  ND_AMD_CLASSIFY_KNN_MAX_FEATURES, k, nfeat);
+        return ND_AMD_EUNSUPPORTED;
+    }
+    if ((mean == nullptr) != (scale == nullptr)) {
+        set_error("%s: scaler needs both mean and scale", who);
+        return ND_AMD_EINVAL;
+    }
+    if (!labels && !proba) {
+        set_error("%s: no output: labels and proba are both NULL", who);
+        return ND_AMD_EINVAL;
+    }
+    if (rows == 0) return ND_AMD_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    ND_HIP_CHECK(hipMemcpyAsync(workspace, feat, (size_t)nfeat * sizeof(void *), hipMemcpyHostToDevice, st));
+    const void *const *tab = (const void *const *)workspace;
+    {
+        KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_KNN, st);
+        if (dtype == ND_AMD_F32)
+            launch_knn_features<float>(nfeat, k, rows, st, tab, R, train, target, ntrain, k, classes, nclasses, mean,
+                                       scale, labels, proba);
+        else
+            launch_knn_features<double>(nfeat, k, rows, st, tab, R, train, target, ntrain, k, classes, nclasses, mean,
+                                        scale, labels, proba);
+    }
+    ND_HIP_CHECK(hipGetLastError());
+    return ND_AMD_OK;
+}
+
+extern "C" int nd_amd_classify_linear(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                                      const int64_t *strides, const double *coef, const double *intercept, int ncoef,
+                                      const double *classes, int link, int output, const double *mean,
+                                      const double *scale, double *out, void *workspace, size_t workspace_bytes,
+                                      void *hip_stream)
+{
+    const char *who = "nd_amd_classify_linear";
+    int rc = check_table(who, feat, nfeat, dtype, workspace, workspace_bytes);
+    if (rc != ND_AMD_OK) return rc;
+    RowDims R;
+    int64_t rows;
+    rc = make_dims(who, sizes, strides, nullptr, R, rows);
+    if (rc != ND_AMD_OK) return rc;
+    if (!coef || !intercept || !classes || ncoef < 1) {
+        set_error("%s: bad model (%d rows of coefficients)", who, ncoef);
+        return ND_AMD_EINVAL;
+    }
+    if (link < ND_AMD_LINK_NONE || link > ND_AMD_LINK_OVR || output < ND_AMD_LINEAR_LABELS ||
+        output > ND_AMD_LINEAR_PROBA || (output == ND_AMD_LINEAR_PROBA && link == ND_AMD_LINK_NONE)) {
+        set_error("%s: bad link %d for output %d", who, link, output);
+        return ND_AMD_EINVAL;
+    }
+    if ((mean == nullptr) != (scale == nullptr)) {
+        set_error("%s: scaler needs both mean and scale", who);
+        return ND_AMD_EINVAL;
+    }
+    if (!out) {
+        set_error("%s: no output: out is NULL", who);
+        return ND_AMD_EINVAL;
+    }
+    if (rows == 0) return ND_AMD_OK;
+    hipStream_t st = (hipStream_t)hip_stream;
+    ND_HIP_CHECK(hipMemcpyAsync(workspace, feat, (size_t)nfeat * sizeof(void *), hipMemcpyHostToDevice, st));
+    const void *const *tab = (const void *const *)workspace;
+    const int grid = grid_for(rows);
+    {
+        KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_LINEAR, st);
+#define ND_LINEAR(T, NC)                                                                                        \
+    hipLaunchKernelGGL((classify_linear_kernel<T, NC>), dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, coef, \
+                       intercept, ncoef, classes, link, output, mean, scale, out)
+        if (dtype == ND_AMD_F32) {
+            if (ncoef <= 1) ND_LINEAR(float, 1);
+            else if (ncoef <= 2) ND_LINEAR(float, 2);
+            else if (ncoef <= 4) ND_LINEAR(float, 4);
+            else ND_LINEAR(float, 8);
+        } else {
+            if (ncoef <= 1) ND_LINEAR(double, 1);
+            else if (ncoef <= 2) ND_LINEAR(double, 2);
+            else if (ncoef <= 4) ND_LINEAR(double, 4);
+            else ND_LINEAR(double, 8);
+        }
+#undef ND_LINEAR
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;

@@ -1037,6 +1037,83 @@ def classify_kmeans(features, sizes, strides, centers, mean=None, scale=None):
     return labels
 
 
+def classify_knn(features, sizes, strides, train, target, classes, k, mean=None, scale=None,
+                 want_labels=True, want_proba=False):
+    """KNeighborsClassifier.predict / predict_proba (uniform weights, Euclidean) over unstacked rows: the k
+    training samples smallest by (float64 squared distance, index) vote (nd_amd_classify_knn).  train: float64
+    (n_train, features), target: int32 (n_train,) indices into classes, classes: float64, all on the features'
+    device.  -> (labels float64 sizes | None, proba float64 sizes + (classes,) | None); NaN for masked rows."""
+    name = 'classify_knn'
+    ptrs, sz, st, ws = _feature_table(features, sizes, strides, name)
+    dev = features[0].device
+    for t, dt, nm in ((train, torch.float64, 'train'), (target, torch.int32, 'target'),
+                      (classes, torch.float64, 'classes')):
+        if not (torch.is_tensor(t) and t.device == dev and t.dtype == dt and t.is_contiguous()):
+            raise ValueError('%s: %s must be a contiguous %s tensor on %s' % (name, nm, dt, dev))
+    if train.dim() != 2 or train.shape[1] != len(features) or train.shape[0] < 1 \
+            or target.shape != (train.shape[0],) or classes.dim() != 1 or classes.numel() < 1:
+        raise ValueError('%s: train must be (n_train, %d), target (n_train,) and classes (n_classes,)'
+                         % (name, len(features)))
+    k, ntrain, ncls = int(k), int(train.shape[0]), int(classes.numel())
+    if not 1 <= k <= ntrain:
+        raise ValueError('%s: k = %d neighbours of %d training samples' % (name, k, ntrain))
+    if k > _lib.CLASSIFY_KNN_MAX_K or len(features) > _lib.CLASSIFY_KNN_MAX_FEATURES:
+        raise NotImplementedError('%s: serves k <= %d and up to %d features, got k = %d and %d features'
+                                  % (name, _lib.CLASSIFY_KNN_MAX_K, _lib.CLASSIFY_KNN_MAX_FEATURES, k,
+                                     len(features)))
+    if ntrain >= 2 ** 31:
+        raise ValueError('%s: too many training samples' % name)
+    if not (want_labels or want_proba):
+        raise ValueError('%s: nothing to compute' % name)
+    shape = tuple(int(n) for n in sizes)
+    with torch.cuda.device(dev):
+        mean, scale = _scaler_args(mean, scale, len(features), dev, name)
+        labels = torch.empty(shape, dtype=torch.float64, device=dev) if want_labels else None
+        proba = torch.empty(shape + (ncls,), dtype=torch.float64, device=dev) if want_proba else None
+        _lib.check(_lib.lib().nd_amd_classify_knn(
+            ptrs, len(features), _DT[features[0].dtype], sz, st, _ptr(train), _ptr(target), ntrain, k, _ptr(classes),
+            ncls, _ptr(mean), _ptr(scale), _ptr(labels), _ptr(proba), _ptr(ws), ws.numel(), _stream_ptr(dev)))
+        _record(list(features) + [train, target, classes, mean, scale, ws], dev)
+    return labels, proba
+
+
+def classify_linear(features, sizes, strides, coef, intercept, classes, link='none', func='predict', mean=None,
+                    scale=None):
+    """decision_function / predict / predict_proba of a linear classifier over unstacked rows
+    (nd_amd_classify_linear).  coef: float64 (n_rows, features), intercept: float64 (n_rows,), classes:
+    float64 (2 for one row of coefficients, else n_rows), on the features' device.  link: 'none', 'softmax'
+    or 'ovr'.  -> float64 of shape sizes ('predict'), sizes + (n_rows,) ('decision_function') or sizes +
+    (classes,) ('predict_proba'); NaN for masked rows."""
+    name = 'classify_linear'
+    ptrs, sz, st, ws = _feature_table(features, sizes, strides, name)
+    dev = features[0].device
+    for t, nm in ((coef, 'coef'), (intercept, 'intercept'), (classes, 'classes')):
+        if not (torch.is_tensor(t) and t.device == dev and t.dtype == torch.float64 and t.is_contiguous()):
+            raise ValueError('%s: %s must be a contiguous float64 tensor on %s' % (name, nm, dev))
+    if coef.dim() != 2 or coef.shape[1] != len(features) or coef.shape[0] < 1 \
+            or intercept.shape != (coef.shape[0],):
+        raise ValueError('%s: coef must be (n_rows, %d) and intercept (n_rows,)' % (name, len(features)))
+    ncoef = int(coef.shape[0])
+    ncls = 2 if ncoef == 1 else ncoef
+    if classes.shape != (ncls,):
+        raise ValueError('%s: %d rows of coefficients need %d classes' % (name, ncoef, ncls))
+    if link not in _lib.LINKS or func not in _lib.LINEAR_OUTPUTS:
+        raise ValueError('%s: link %r / func %r' % (name, link, func))
+    if func == 'predict_proba' and link == 'none':
+        raise ValueError('%s: predict_proba needs a link' % name)
+    shape = tuple(int(n) for n in sizes)
+    width = {'predict': (), 'decision_function': (ncoef,), 'predict_proba': (ncls,)}[func]
+    with torch.cuda.device(dev):
+        mean, scale = _scaler_args(mean, scale, len(features), dev, name)
+        out = torch.empty(shape + width, dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().nd_amd_classify_linear(
+            ptrs, len(features), _DT[features[0].dtype], sz, st, _ptr(coef), _ptr(intercept), ncoef, _ptr(classes),
+            _lib.LINKS[link], _lib.LINEAR_OUTPUTS[func], _ptr(mean), _ptr(scale), _ptr(out), _ptr(ws), ws.numel(),
+            _stream_ptr(dev)))
+        _record(list(features) + [coef, intercept, classes, mean, scale, ws], dev)
+    return out
+
+
 def _label_args(labels, label_strides, sizes, dev, name):
     nd = len(sizes)
     if labels is None:

@@ -1,12 +1,17 @@
 """Classification timing on the headline stack (k x n x n, four variables from nd_amd.synth, device resident):
 
-    python tools/bench_classify.py [--k 24] [--n 4096] [--reps 5] [--trees 20] [--json out.json]
+    python tools/bench_classify.py [--k 24] [--n 4096] [--reps 5] [--trees 20] [--knn-n N] [--json out.json]
 
   forest      Classifier(RandomForestClassifier(trees)).predict, fitted by scikit-learn on 10 % of a
               256 x 256 crop (labels: terciles of the crop's C11), at feature_dims=[] (k n^2 rows x 4 features)
               and feature_dims=['time'] (n^2 rows x 4 k features); node count and depth are recorded
   kmeans      Classifier(KMeans(3)).predict at feature_dims=[]
   class_mean  class_mean of the stack under the forest's (y, x) labels
+  knn         Classifier(KNeighborsClassifier(3)).predict fitted on 1 000 and on 10 000 labelled pixels of the crop
+              at feature_dims=[], and on 1 000 at feature_dims=['time'] (n^2 rows x 4 k features); the line also
+              gives the kernel's float64 operations per second (3 per row, sample and feature: subtract,
+              multiply, add) as a fraction of --fp64-peak
+  logistic    Classifier(LogisticRegression()).predict, three classes, at feature_dims=[]
 
 Every case: device events around whole calls, one warm-up, min and median of --reps; the kernels' own time from
 the library's event timers (KernelTimer).  Yardstick, measured in the same run: the reference path on the host,
@@ -64,6 +69,8 @@ def main():
     import torch
     from sklearn.cluster import KMeans
     from sklearn.ensemble import RandomForestClassifier
+    from sklearn.linear_model import LogisticRegression
+    from sklearn.neighbors import KNeighborsClassifier
     from nd_amd import classify, synth, xr_lite
     ap = argparse.ArgumentParser()
     ap.add_argument('--k', type=int, default=24)
@@ -72,6 +79,14 @@ def main():
     ap.add_argument('--trees', type=int, default=20)
     ap.add_argument('--crop', type=int, default=256)
     ap.add_argument('--host-rows', type=int, default=2000000)
+    ap.add_argument('--knn-host-rows', type=int, default=200000)
+    ap.add_argument('--knn-n', type=int, default=None,
+                    help='the k-NN lines predict on the leading knn-n x knn-n pixels of the stack (default: all '
+                         'of it; the 10 000-sample line is 5e16 float64 operations there)')
+    ap.add_argument('--knn-reps', type=int, default=1)
+    ap.add_argument('--fp64-peak', type=float, default=78.6e12,
+                    help='float64 vector operations per second the k-NN rate is set against (MI355X: 78.6e12)')
+    ap.add_argument('--skip-knn', action='store_true')
     ap.add_argument('--json', default=None)
     a = ap.parse_args()
     dev = torch.device('cuda:0')
@@ -126,6 +141,38 @@ def main():
     ms = timed(lambda: classify.class_mean(ds, lab), a.reps)
     record('class_mean 3 classes', len(VARS) * k * n * n, 1, ms, kernel_ms(lambda: classify.class_mean(ds, lab), 'class_mean'),
            None)
+
+    def labelled(count):
+        """the crop's truth on `count` of its pixel columns (every date of one at feature_dims=[]), 0 elsewhere"""
+        pick = np.zeros(truth.size, bool)
+        pick[rng.choice(truth.size, count, replace=False)] = True
+        return np.where(pick.reshape(truth.shape), truth, 0)
+
+    kn = min(a.knn_n or n, n)
+    part = xr_lite.Dataset()
+    for i, v in enumerate(VARS):
+        part[v] = (dims, stack[i][:, :kn, :kn])
+    for ntrain, fdims in (() if a.skip_knn else ((1000, []), (10000, []), (1000, ['time']))):
+        c = classify.Classifier(KNeighborsClassifier(3, n_jobs=16), feature_dims=fdims)
+        c.fit(small, labelled(ntrain if fdims else -(-ntrain // k)))
+        model = classify.KNNModel.from_sklearn(c.clf)
+        Xh = c.make_Xy(small)[0]
+        Xh = np.concatenate([Xh] * max(1, a.knn_host_rows // Xh.shape[0]))[:a.knn_host_rows]
+        host = host_rate(c.clf.predict, Xh, reps=1)
+        ms = timed(lambda: c.predict(part), a.knn_reps)
+        kms = kernel_ms(lambda: c.predict(part), 'classify_knn')
+        nrows = kn * kn * (1 if fdims else k)
+        flops = 3.0 * nrows * model.n_train * model.n_features / (kms * 1e-3)
+        record('knn k=3 feature_dims=%s' % fdims, nrows, model.n_features, ms, kms, host,
+               dict(n_train=model.n_train, fp64_ops_per_s=flops, fraction_of_fp64_peak=flops / a.fp64_peak))
+    c = classify.Classifier(LogisticRegression(max_iter=300))
+    c.fit(small, train)
+    Xh = c.make_Xy(small)[0]
+    Xh = np.concatenate([Xh] * max(1, a.host_rows // Xh.shape[0]))[:a.host_rows]
+    host = host_rate(c.clf.predict, Xh)
+    ms = timed(lambda: c.predict(ds), a.reps)
+    record('logistic 3 classes feature_dims=[]', k * n * n, len(VARS), ms,
+           kernel_ms(lambda: c.predict(ds), 'classify_linear'), host)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         json.dump(dict(k=k, n=n, threads=int(os.environ.get('OMP_NUM_THREADS', '0') or 0), rows=rows),
