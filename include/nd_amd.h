@@ -76,6 +76,9 @@ extern "C" {
 #define ND_AMD_KERNEL_CLASS_MEAN      20  /* nd_amd_class_stats and nd_amd_class_fill */
 #define ND_AMD_KERNEL_CLASSIFY_KNN    21  /* nd_amd_classify_knn */
 #define ND_AMD_KERNEL_CLASSIFY_LINEAR 22  /* nd_amd_classify_linear */
+#define ND_AMD_KERNEL_KMEANS_STEP     23  /* nd_amd_kmeans_step: the pass over the rows and the fold of its partials */
+#define ND_AMD_KERNEL_FEATURE_MOMENTS 24  /* nd_amd_feature_moments, the whole call (both passes) */
+#define ND_AMD_KERNEL_GATHER_ROWS     25  /* nd_amd_gather_rows */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -88,6 +91,8 @@ extern "C" {
 #define ND_AMD_CLASSIFY_KNN_MAX_K 32
 #define ND_AMD_CLASSIFY_KNN_MAX_FEATURES 128
 #define ND_AMD_CLASSIFY_KNN_TILE 8
+/* nd_amd_kmeans_step: k * (nfeat + 1) float64 / int64 accumulators per block, 32 KiB of LDS */
+#define ND_AMD_KMEANS_FIT_MAX_ACC 4096
 /* nd_amd_classify_linear: link (what predict_proba applies to the decision values) and output */
 #define ND_AMD_LINK_NONE    0
 #define ND_AMD_LINK_SOFTMAX 1   /* exp(s_c - max s) / sum, in class order */
@@ -697,6 +702,63 @@ int nd_amd_class_stats(const void *var, int dtype, const int64_t *sizes, const i
 int nd_amd_class_fill(const void *var, void *out, int dtype, const int64_t *sizes, const int64_t *strides,
                       const double *labels, const int64_t *label_strides, int nclasses, const void *fill,
                       void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Training k-means on every row (scikit-learn's lloyd loop; the caller drives the
+ * iterations).  The feature table, the scaler and the pointer-table part of the
+ * workspace are those of the nd_amd_classify_* entries; a row with a NaN feature
+ * is not VALID and takes no part in any sum, as make_Xy drops it
+ * (nd/classify.py:164-178).  x_f below is the (scaled) feature in type T.
+ *
+ * All three reducing passes are DETERMINISTIC: every floating-point sum is formed
+ * in an order fixed by (rows, k, nfeat) -- a fixed tree over the 64 rows of a
+ * batch, batches in order inside a block, blocks in order -- with no
+ * floating-point atomics, so a call repeats its results bit for bit.
+ *
+ * workspace: >= nd_amd_kmeans_fit_workspace_bytes(nfeat, k, rows) device bytes,
+ * 256-byte aligned (the pointer table and the per-block partial sums; k = 1 for
+ * nd_amd_feature_moments).  The query returns 0 for a request the calls refuse.
+ * Served: k * (nfeat + 1) <= ND_AMD_KMEANS_FIT_MAX_ACC, else ND_AMD_EUNSUPPORTED.
+ *
+ * nd_amd_kmeans_step: one Lloyd iteration in one pass.  centers: device, (k, nfeat)
+ * doubles.  Every valid row is assigned to the first j with the smallest
+ *   d_j = sum over f, in feature order and in float64, of (double(x_f) - centers[j, f])^2
+ * (the rule of nd_amd_classify_kmeans).  labels: device, rows int32, read and
+ * written: labels[r] = j, or -1 for a row that is not valid; *changed = the number
+ * of valid rows whose label differs from the value found there (fill with -1
+ * before the first iteration: every valid row then counts).  sums: device, (k,
+ * nfeat) doubles, sums[j, f] = sum of double(x_f) over the rows of cluster j;
+ * counts: device, k int64; *inertia = sum of the smallest d_j over the valid rows
+ * (device double); *changed: device int64.  Every output is overwritten.
+ *
+ * nd_amd_feature_moments: *count = the valid rows (device int64), fmean[f] = sum of
+ * double(x_f) / count, fvar[f] = sum of (double(x_f) - fmean[f])^2 / count in a second
+ * pass (the population variance); device, nfeat doubles each, NaN where no row is
+ * valid.  Serves StandardScaler (mean_, var_) and the tol * mean(var) threshold.
+ *
+ * nd_amd_gather_rows: X[i, f] = x_f of row index[i] (device, (m, nfeat) of type T),
+ * valid[i] = 1 where that row has no NaN feature (device, m bytes).  index: device,
+ * m int64 row numbers, counted row-major over sizes, in any order, repeats
+ * allowed; an index outside 0 .. rows-1 is not followed: its row of X is NaN and
+ * valid[i] = 0.  workspace as for the nd_amd_classify_* entries.
+ * ---------------------------------------------------------------------- */
+size_t nd_amd_kmeans_fit_workspace_bytes(int nfeat, int k, int64_t rows);
+
+int nd_amd_kmeans_step(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                       const int64_t *strides, const double *centers, int k, const double *mean,
+                       const double *scale, int32_t *labels, double *sums, int64_t *counts,
+                       double *inertia, int64_t *changed, void *workspace, size_t workspace_bytes,
+                       void *hip_stream);
+
+int nd_amd_feature_moments(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                           const int64_t *strides, const double *mean, const double *scale,
+                           int64_t *count, double *fmean, double *fvar, void *workspace,
+                           size_t workspace_bytes, void *hip_stream);
+
+int nd_amd_gather_rows(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
+                       const int64_t *strides, const int64_t *index, int64_t m, const double *mean,
+                       const double *scale, void *X, uint8_t *valid, void *workspace,
+                       size_t workspace_bytes, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,8 @@ KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 8: 'relayout', 9: 'omnibus_c2_dense', 10: 'omnibus_c2_fused', 11: 'omnibus_c2_sample', 12: 'omnibus_c2_exact',
                 13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose',
                 17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean',
-                21: 'classify_knn', 22: 'classify_linear'}
+                21: 'classify_knn', 22: 'classify_linear', 23: 'kmeans_step', 24: 'feature_moments',
+                25: 'gather_rows'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 
 # every symbol include/nd_amd.h declares
@@ -39,9 +40,12 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_rgb_limits_workspace_bytes', 'nd_amd_rgb_limits', 'nd_amd_rgb_compose',
            'nd_amd_classify_workspace_bytes', 'nd_amd_classify_forest', 'nd_amd_classify_kmeans',
            'nd_amd_classify_select', 'nd_amd_classify_gather', 'nd_amd_class_stats', 'nd_amd_class_fill',
-           'nd_amd_classify_knn', 'nd_amd_classify_linear')
+           'nd_amd_classify_knn', 'nd_amd_classify_linear',
+           'nd_amd_kmeans_fit_workspace_bytes', 'nd_amd_kmeans_step', 'nd_amd_feature_moments',
+           'nd_amd_gather_rows')
 CLASSIFY_BLOCK_ROWS, CLASSIFY_MAX_FEATURES = 1024, 1024
 CLASSIFY_KNN_MAX_K, CLASSIFY_KNN_MAX_FEATURES, CLASSIFY_KNN_TILE = 32, 128, 8
+KMEANS_FIT_MAX_ACC = 4096
 LINKS = {'none': 0, 'softmax': 1, 'ovr': 2}
 LINEAR_OUTPUTS = {'predict': 0, 'decision_function': 1, 'predict_proba': 2}
 
@@ -163,6 +167,14 @@ def lib():
     L.nd_amd_class_stats.argtypes = [vp, i32, pi64, pi64, vp, pi64, i32, vp, vp, vp, vp]
     L.nd_amd_class_fill.restype = i32
     L.nd_amd_class_fill.argtypes = [vp, vp, i32, pi64, pi64, vp, pi64, i32, vp, vp]
+    L.nd_amd_kmeans_fit_workspace_bytes.restype = C.c_size_t
+    L.nd_amd_kmeans_fit_workspace_bytes.argtypes = [i32, i32, i64]
+    L.nd_amd_kmeans_step.restype = i32
+    L.nd_amd_kmeans_step.argtypes = table + [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_feature_moments.restype = i32
+    L.nd_amd_feature_moments.argtypes = table + [vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.nd_amd_gather_rows.restype = i32
+    L.nd_amd_gather_rows.argtypes = table + [vp, i64, vp, vp, vp, vp, vp, C.c_size_t, vp]
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

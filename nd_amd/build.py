@@ -52,7 +52,9 @@ PER_FILE = {'nlmeans.hip': ['-fno-slp-vectorize'],
 # rgb.hip: the histogram passes and the composite are streaming kernels; none of its kernels may spill
 # classify.hip: the forest kernel picks a row's feature by a select chain so that its register copies are
 # never indexed at run time; a spill would mean that form was lost
-NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_', 'classify.hip': 'class'}
+# kmeans_fit.hip: the step kernel keeps a row's features in registers by static index, as the predict kernels do
+NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_', 'classify.hip': 'class',
+              'kmeans_fit.hip': '_kernel'}
 # bytes per lane by the kernel's template arguments <K, KMAX, STATS, CHAIN>, keyed (STATS, CHAIN)
 SCRATCH_BUDGET = {(False, False): 0, (False, True): 96, (True, False): 256, (True, True): 384}
 

@@ -2,12 +2,16 @@
 nd_amd/classify.py -- pixel classification (nd/classify.py) with prediction on the GPU.
 
   Classifier      nd.classify.Classifier: make_Xy, fit, predict, fit_predict, score
+  fit_kmeans, DeviceKMeans
+                  k-means trained on the device over every pixel: scikit-learn's Lloyd loop, no host matrix
   class_mean      nd.classify.class_mean
   ForestModel, KMeansModel, KNNModel, LinearModel,
   predict_forest, predict_kmeans, predict_knn, predict_linear
                   the device path for callers that hold a fitted model as plain arrays
 
 Training is scikit-learn's and runs on the host: it sees only the labelled pixels and is not a hot path.
+The exception is k-means, which trains on every pixel: Classifier(DeviceKMeans(k)) and fit_kmeans run the
+Lloyd iterations on the device (one pass over the data each) and bring only the (k, n_features) sums back.
 What the device does for it is the selection of those pixels -- label > 0 and not NaN, no NaN feature --
 and their gather into a dense (n, n_features) matrix, in the reference's row order, straight from the
 variables.  Prediction sees every pixel and runs on the device without ever forming the reference's
@@ -45,7 +49,7 @@ import numpy as np
 from . import _adapter, _device, xr_lite
 
 __all__ = ['Classifier', 'class_mean', 'ForestModel', 'KMeansModel', 'KNNModel', 'LinearModel', 'predict_forest',
-           'predict_kmeans', 'predict_knn', 'predict_linear', 'pack_forest']
+           'predict_kmeans', 'predict_knn', 'predict_linear', 'pack_forest', 'fit_kmeans', 'DeviceKMeans']
 
 FORESTS = ('DecisionTreeClassifier', 'ExtraTreeClassifier', 'RandomForestClassifier', 'ExtraTreesClassifier')
 KMEANS = ('KMeans', 'MiniBatchKMeans')
@@ -374,6 +378,10 @@ def _same_state(a, b):
 def _model_for(clf, func, build=True):
     """the model of a fitted estimator for `func`; build=False only checks that the pair is served"""
     names = {c.__name__ for c in type(clf).__mro__}
+    if isinstance(clf, DeviceKMeans):
+        if func != 'predict':
+            raise NotImplementedError(_SUPPORTED + 'Got func=%r for %s.' % (func, type(clf).__name__))
+        return clf._model() if build else None
     if names & set(FORESTS):
         if func not in ('predict', 'predict_proba'):
             raise NotImplementedError(_SUPPORTED + 'Got func=%r.' % func)
@@ -612,6 +620,209 @@ def predict_linear(ds, model, feature_dims=(), func='predict', scaler=None):
 
 
 # ---------------------------------------------------------------------------
+# k-means trained on the device
+# ---------------------------------------------------------------------------
+KMEANS_FIT_MAX_ACC = 4096
+
+
+def _moments(layout, mean=None, scale=None):
+    """-> (valid rows, mean, var) of the layout's features as host values (kernels.feature_moments)"""
+    from . import kernels
+    count, fmean, fvar = kernels.feature_moments(layout.features, layout.shape, layout.strides, mean, scale)
+    return int(count.item()), fmean.cpu().numpy(), fvar.cpu().numpy()
+
+
+def _device_scaler(layout):
+    """a StandardScaler as StandardScaler().fit(X) leaves it, from the device's moments of every valid row"""
+    from sklearn import preprocessing
+    n, mean, var = _moments(layout)
+    if n < 1:
+        raise ValueError('no row without NaN to fit the scaler on')
+    sc = preprocessing.StandardScaler()
+    sc.mean_, sc.var_ = mean, var
+    scale = np.sqrt(var)
+    scale[scale == 0.0] = 1.0            # a constant feature is left as it is, as scikit-learn leaves it
+    sc.scale_ = scale
+    sc.n_samples_seen_ = n
+    sc.n_features_in_ = layout.n_features
+    return sc
+
+
+def _valid_rows(layout, index, mean, scale):
+    """the rows at `index` (host int64) without NaN -> (X as float64 on the host, their indices)"""
+    import torch
+    from . import kernels
+    idx = torch.from_numpy(np.ascontiguousarray(index, np.int64)).to(layout.device)
+    X, valid = kernels.gather_rows(layout.features, layout.shape, layout.strides, idx, mean, scale)
+    keep = valid.cpu().numpy().astype(bool)
+    return X.cpu().numpy().astype(np.float64)[keep], np.asarray(index)[keep]
+
+
+def _initial_centres(layout, k, init, rng, init_size, mean, scale):
+    rows = int(np.prod(layout.shape, dtype=np.int64))
+    if init == 'random':
+        need, chosen = k, np.empty((0, layout.n_features))
+        seen = set()
+        for _ in range(8):                          # rows with NaN are drawn again
+            draw = rng.choice(rows, size=min(rows, 2 * need + 64), replace=False)
+            draw = np.array([i for i in draw if i not in seen], np.int64)
+            seen.update(draw.tolist())
+            X, _ = _valid_rows(layout, draw, mean, scale)
+            chosen = np.concatenate([chosen, X[:need]])
+            need = k - chosen.shape[0]
+            if need == 0 or len(seen) >= rows:
+                break
+        if need:
+            raise ValueError('fit_kmeans: fewer than %d rows without NaN to draw the centres from' % k)
+        return chosen
+    if init == 'k-means++':
+        size = min(rows, max(3 * k, 65536) if init_size is None else int(init_size))
+        draw = np.arange(rows) if size >= rows else rng.choice(rows, size=size, replace=False)
+        X, _ = _valid_rows(layout, draw, mean, scale)
+        if X.shape[0] < k:
+            raise ValueError('fit_kmeans: the sample of %d rows has %d without NaN, fewer than n_clusters=%d'
+                             % (size, X.shape[0], k))
+        from sklearn.cluster import kmeans_plusplus
+        return kmeans_plusplus(X, k, random_state=int(rng.integers(2 ** 31 - 1)))[0]
+    raise ValueError("fit_kmeans: init must be 'k-means++', 'random' or a (k, n_features) array, got %r" % (init,))
+
+
+def _lloyd(layout, centres, max_iter, threshold, mean, scale):
+    """scikit-learn 1.7.2's _kmeans_single_lloyd in float64, the pass over the rows on the device.
+    -> (centres, n_iter, inertia, counts)"""
+    import torch
+    from . import kernels
+    dev = layout.device
+    k, nfeat = centres.shape
+    labels = torch.full(layout.shape, -1, dtype=torch.int32, device=dev)
+
+    def step(c):
+        sums, counts, inertia, changed = kernels.kmeans_step(layout.features, layout.shape, layout.strides,
+                                                             torch.from_numpy(c).to(dev), labels, mean, scale)
+        # the one read of an iteration: k * n_features + k + 2 numbers (a count is exact in float64 below 2^53)
+        got = torch.cat([sums.reshape(-1), inertia.reshape(1), counts.double(), changed.double().reshape(1)])
+        got = got.cpu().numpy()
+        return (got[:k * nfeat].reshape(k, nfeat), got[k * nfeat + 1:-1].astype(np.int64), float(got[k * nfeat]),
+                int(got[-1]))
+
+    strict, n_iter = False, 0
+    counts, inertia = np.zeros(k, np.int64), 0.0
+    for n_iter in range(1, max_iter + 1):
+        sums, counts, inertia, changed = step(centres)
+        new = centres.copy()
+        full = counts > 0                      # an empty cluster keeps its centre (scikit-learn relocates it)
+        new[full] = sums[full] / counts[full, None]
+        shift = float(((new - centres) ** 2).sum())
+        centres = new
+        if changed == 0:
+            strict = True
+            break
+        if shift <= threshold:
+            break
+    if not strict:                             # labels, counts and inertia of the final centres
+        _, counts, inertia, _ = step(centres)
+    return centres, n_iter, inertia, counts
+
+
+def _fit_kmeans(layout, n_clusters, init, n_init, max_iter, tol, random_state, scaler, init_size):
+    k = int(n_clusters)
+    if k != n_clusters or k < 1:
+        raise ValueError('fit_kmeans: n_clusters = %r' % (n_clusters,))
+    if int(max_iter) < 1 or int(n_init) < 1:
+        raise ValueError('fit_kmeans: max_iter and n_init must be at least 1')
+    if k * (layout.n_features + 1) > KMEANS_FIT_MAX_ACC:
+        raise NotImplementedError('nd_amd.classify fits k-means on the device for n_clusters * (n_features + 1) <= %d; '
+                                  'got n_clusters=%d and %d features.  There is no CPU fallback.'
+                                  % (KMEANS_FIT_MAX_ACC, k, layout.n_features))
+    import torch
+    mean, scale = _scaler_arrays(scaler)
+    if mean is not None:                       # uploaded once for every pass
+        mean, scale = (torch.from_numpy(np.ascontiguousarray(v)).to(layout.device) for v in (mean, scale))
+    n, _, var = _moments(layout, mean, scale)
+    if n < k:
+        raise ValueError('fit_kmeans: %d rows without NaN for n_clusters=%d' % (n, k))
+    threshold = float(tol) * float(np.mean(var))
+    if not isinstance(init, str):
+        init = np.array(init, np.float64, order='C')
+        if init.shape != (k, layout.n_features):
+            raise ValueError('fit_kmeans: init must be (%d, %d), got %s' % (k, layout.n_features, init.shape))
+        n_init = 1
+    rng = random_state if isinstance(random_state, np.random.Generator) else np.random.default_rng(random_state)
+    best = None
+    for _ in range(int(n_init)):
+        start = init if not isinstance(init, str) else np.ascontiguousarray(
+            _initial_centres(layout, k, init, rng, init_size, mean, scale), np.float64)
+        run = _lloyd(layout, start, int(max_iter), threshold, mean, scale)
+        if best is None or run[2] < best[2]:
+            best = run
+    model = KMeansModel(best[0])
+    model.n_iter, model.inertia, model.counts = best[1], best[2], best[3]
+    model.empty = np.flatnonzero(best[3] == 0)
+    return model
+
+
+def fit_kmeans(ds, n_clusters, feature_dims=(), init='k-means++', n_init=1, max_iter=300, tol=1e-4,
+               random_state=None, scaler=None, init_size=None):
+    """K-means over every pixel of `ds` without a NaN feature, trained on the device: scikit-learn 1.7.2's Lloyd
+    loop restated in float64.  Per iteration one pass assigns every row to its first nearest centre (the rule of
+    predict_kmeans) and sums the rows of every cluster in a fixed order; the new centre is sums / counts.  It
+    stops when no label changed ("strict convergence"), when sum((new - old)^2) <= tol * mean(var), var the
+    population variances of the features, or after max_iter iterations; unless the stop was strict one more
+    pass gives the counts and the inertia of the final centres.  Nothing of the size of the data leaves the
+    device, and the same inputs give the same bits.
+    init: a (n_clusters, n_features) array (forces n_init = 1), 'random' (distinct rows drawn with
+    random_state) or 'k-means++' (sklearn.cluster.kmeans_plusplus on a drawn sample of init_size rows, default
+    max(3 * n_clusters, 65536)).  With n_init > 1 the run of the lowest inertia wins.
+    scaler: None, or an object with mean_ and scale_; the centres are then those of the scaled features.
+    Unlike scikit-learn, a cluster that loses all its rows keeps its centre; such clusters are listed in `.empty`.
+    -> a KMeansModel with .centers, .n_iter, .inertia, .counts and .empty.
+    Serves n_clusters * (n_features + 1) <= 4096; more raises NotImplementedError (there is no CPU fallback)."""
+    return _fit_kmeans(_Layout(ds, feature_dims), n_clusters, init, n_init, max_iter, tol, random_state, scaler,
+                       init_size)
+
+
+class DeviceKMeans:
+    """The estimator Classifier trains on the device: Classifier(DeviceKMeans(8)).fit_predict(ds) clusters every
+    pixel of `ds` through fit_kmeans, without the (n_pixels, n_features) matrix.  Parameters as
+    sklearn.cluster.KMeans; see fit_kmeans for `init` and for the one difference (empty clusters)."""
+
+    def __init__(self, n_clusters=8, init='k-means++', n_init=1, max_iter=300, tol=1e-4, random_state=None):
+        self.n_clusters, self.init, self.n_init = n_clusters, init, n_init
+        self.max_iter, self.tol, self.random_state = max_iter, tol, random_state
+        self.cluster_centers_ = self.n_iter_ = self.inertia_ = None
+
+    def get_params(self, deep=True):
+        return {p: getattr(self, p) for p in ('n_clusters', 'init', 'n_init', 'max_iter', 'tol', 'random_state')}
+
+    def _fit_layout(self, layout, scaler):
+        model = _fit_kmeans(layout, self.n_clusters, self.init, self.n_init, self.max_iter, self.tol,
+                            self.random_state, scaler, None)
+        self.cluster_centers_, self.n_iter_, self.inertia_ = model.centers, model.n_iter, model.inertia
+
+    def _model(self):
+        if self.cluster_centers_ is None:
+            raise AttributeError('DeviceKMeans is not fitted: call Classifier.fit first')
+        return KMeansModel(self.cluster_centers_)
+
+    def predict(self, X):
+        """the first nearest centre of every row of the matrix X (n, n_features), on the device; NaN for a row
+        with a NaN feature"""
+        import torch
+        from . import kernels
+        model = self._model()
+        X = np.asarray(X)
+        X = np.ascontiguousarray(X, np.float32 if X.dtype == np.float32 else np.float64)
+        if X.ndim != 2 or X.shape[1] != model.n_features:
+            raise ValueError('DeviceKMeans.predict: X must be (n, %d)' % model.n_features)
+        dev = _device.device_of(X)
+        with torch.cuda.device(dev):
+            t = torch.from_numpy(X).to(dev)
+            labels = kernels.classify_kmeans([t[:, f] for f in range(X.shape[1])], (X.shape[0],), (X.shape[1],),
+                                             model._on(dev))
+        return labels.cpu().numpy()
+
+
+# ---------------------------------------------------------------------------
 # nd.classify.Classifier
 # ---------------------------------------------------------------------------
 class Classifier:
@@ -629,6 +840,8 @@ class Classifier:
 
     Fitting (``clf.fit``, ``StandardScaler().fit``) is scikit-learn's, on the host, on the labelled pixels
     only: it is not a hot path.  Selecting and gathering those pixels, and ``predict``, run on the device.
+    With a ``DeviceKMeans`` as `clf`, ``fit(ds)`` trains on every pixel on the device (``fit_kmeans``), the
+    scaler included, and forms no matrix.
     """
 
     def __init__(self, clf, feature_dims=[], scale=False):
@@ -660,6 +873,14 @@ class Classifier:
     def fit(self, ds, labels=None):
         """Train the classifier with scikit-learn on the pixels make_Xy selects (labels may be omitted for
         an unsupervised estimator such as KMeans)."""
+        if isinstance(self.clf, DeviceKMeans):
+            if labels is not None:
+                raise TypeError('Classifier: DeviceKMeans is unsupervised and takes no labels')
+            layout = _Layout(ds, self.feature_dims)
+            self._scaler = _device_scaler(layout) if self.scale else None
+            self._model = None
+            self.clf._fit_layout(layout, self._scaler)
+            return self
         X, y = self.make_Xy(ds, labels=labels)
         self._model = None
         self.clf.fit(X, y)

@@ -1206,3 +1206,99 @@ def class_fill(var, labels, label_strides, fill):
                                                 int(fill.numel()) - 1, _ptr(fill), _stream_ptr(dev)))
         _record([var, lab, fill], dev)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Training k-means on the device (include/nd_amd.h, nd_amd_kmeans_step and its neighbours)
+# ---------------------------------------------------------------------------
+def _rows_of(sizes):
+    rows = 1
+    for n in sizes:
+        rows *= int(n)
+    return rows
+
+
+def _fit_workspace(nfeat, k, rows, dev, name):
+    """the pointer table and the per-block partial sums of the reducing passes"""
+    if k < 1:
+        raise ValueError('%s: needs k >= 1 centres, got %d' % (name, k))
+    if k * (nfeat + 1) > _lib.KMEANS_FIT_MAX_ACC:
+        raise NotImplementedError('%s: serves k * (features + 1) <= %d, got k = %d and %d features'
+                                  % (name, _lib.KMEANS_FIT_MAX_ACC, k, nfeat))
+    nbytes = _lib.lib().nd_amd_kmeans_fit_workspace_bytes(nfeat, k, rows)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def kmeans_step(features, sizes, strides, centers, labels, mean=None, scale=None):
+    """One Lloyd iteration over unstacked rows (nd_amd_kmeans_step): every row without a NaN feature goes to its
+    first nearest centre in float64.  centers: float64 (k, features) device tensor.  labels: int32 device tensor of
+    `sizes`, read and overwritten (-1 for rows with a NaN feature; fill it with -1 before the first iteration).
+    -> (sums float64 (k, features), counts int64 (k,), inertia float64 (), changed int64 ()), device tensors;
+    changed counts the rows whose label differs from the one found in `labels`.  The sums are formed in a fixed
+    order: the same inputs give the same bits."""
+    name = 'kmeans_step'
+    ptrs, sz, st, _ = _feature_table(features, sizes, strides, name)
+    dev = features[0].device
+    nfeat, rows = len(features), _rows_of(sizes)
+    if not (torch.is_tensor(centers) and centers.device == dev and centers.dtype == torch.float64
+            and centers.dim() == 2 and centers.shape[1] == nfeat and centers.shape[0] >= 1):
+        raise ValueError('%s: centers must be a float64 (k, %d) tensor on %s' % (name, nfeat, dev))
+    if not (torch.is_tensor(labels) and labels.device == dev and labels.dtype == torch.int32
+            and labels.is_contiguous() and labels.numel() == rows):
+        raise ValueError('%s: labels must be a contiguous int32 tensor of %d rows on %s' % (name, rows, dev))
+    centers = centers.contiguous()
+    k = int(centers.shape[0])
+    with torch.cuda.device(dev):
+        ws = _fit_workspace(nfeat, k, rows, dev, name)
+        mean, scale = _scaler_args(mean, scale, nfeat, dev, name)
+        fbuf = torch.empty(k * nfeat + 1, dtype=torch.float64, device=dev)
+        ibuf = torch.empty(k + 1, dtype=torch.int64, device=dev)
+        sums, inertia, counts, changed = fbuf[:k * nfeat].view(k, nfeat), fbuf[k * nfeat], ibuf[:k], ibuf[k]
+        _lib.check(_lib.lib().nd_amd_kmeans_step(
+            ptrs, nfeat, _DT[features[0].dtype], sz, st, _ptr(centers), k, _ptr(mean), _ptr(scale), _ptr(labels),
+            _ptr(sums), _ptr(counts), _ptr(inertia), _ptr(changed), _ptr(ws), ws.numel(), _stream_ptr(dev)))
+        _record(list(features) + [centers, labels, mean, scale, ws], dev)
+    return sums, counts, inertia, changed
+
+
+def feature_moments(features, sizes, strides, mean=None, scale=None):
+    """Over the rows without a NaN feature (nd_amd_feature_moments): -> (count int64 (), mean float64 (features,),
+    var float64 (features,)), device tensors; var is the population variance, sum (x - mean)^2 / count in a
+    second pass.  With mean / scale given the moments are those of the scaled values.  Deterministic."""
+    name = 'feature_moments'
+    ptrs, sz, st, _ = _feature_table(features, sizes, strides, name)
+    dev = features[0].device
+    nfeat, rows = len(features), _rows_of(sizes)
+    with torch.cuda.device(dev):
+        ws = _fit_workspace(nfeat, 1, rows, dev, name)
+        mean, scale = _scaler_args(mean, scale, nfeat, dev, name)
+        count = torch.empty((), dtype=torch.int64, device=dev)
+        fmean = torch.empty(nfeat, dtype=torch.float64, device=dev)
+        fvar = torch.empty(nfeat, dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().nd_amd_feature_moments(
+            ptrs, nfeat, _DT[features[0].dtype], sz, st, _ptr(mean), _ptr(scale), _ptr(count), _ptr(fmean), _ptr(fvar),
+            _ptr(ws), ws.numel(), _stream_ptr(dev)))
+        _record(list(features) + [mean, scale, ws], dev)
+    return count, fmean, fvar
+
+
+def gather_rows(features, sizes, strides, index, mean=None, scale=None):
+    """The rows at `index` (int64 device tensor of row numbers, row-major over `sizes`, repeats allowed) as a dense
+    matrix (nd_amd_gather_rows): -> (X (m, features) of the data type, scaled where mean / scale are given, valid
+    uint8 (m,): 1 where the row has no NaN feature).  An index outside the rows gives a NaN row and valid 0."""
+    name = 'gather_rows'
+    ptrs, sz, st, ws = _feature_table(features, sizes, strides, name)
+    dev = features[0].device
+    if not (torch.is_tensor(index) and index.device == dev and index.dtype == torch.int64 and index.dim() == 1):
+        raise ValueError('%s: index must be a 1-D int64 tensor on %s' % (name, dev))
+    index = index.contiguous()
+    m, nfeat = int(index.numel()), len(features)
+    with torch.cuda.device(dev):
+        mean, scale = _scaler_args(mean, scale, nfeat, dev, name)
+        X = torch.empty((m, nfeat), dtype=features[0].dtype, device=dev)
+        valid = torch.empty(m, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().nd_amd_gather_rows(
+            ptrs, nfeat, _DT[features[0].dtype], sz, st, _ptr(index), m, _ptr(mean), _ptr(scale), _ptr(X), _ptr(valid),
+            _ptr(ws), ws.numel(), _stream_ptr(dev)))
+        _record(list(features) + [index, mean, scale, ws], dev)
+    return X, valid
