@@ -57,20 +57,12 @@ omnibus_c2_global_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)
         for (int j = tid; j <= k; j += kGlobalThreads) g.tab_dev[j] = tab.e[j];
     }
 
-    // ---- zero-fill this block's slice of the change map (np.zeros at nd/_change.pyx:275) ----
+    // ---- zero-fill this block's slice of the change map ----
     {
         int64_t npx = g.nx - bpx0;
         if (npx > kGlobalThreads * PPT) npx = kGlobalThreads * PPT;
-        uint8_t *ob = g.change + (row * g.nx + bpx0) * (int64_t)k;
-        const int64_t nb = npx * (int64_t)k;
-        int64_t head = (int64_t)((16 - ((uintptr_t)ob & 15)) & 15);
-        if (head > nb) head = nb;
-        if (tid < head) ob[tid] = 0;
-        const int64_t nvec = (nb - head) >> 4;
-        uint4 *v = reinterpret_cast<uint4 *>(ob + head);
-        for (int64_t i = tid; i < nvec; i += kGlobalThreads) store_zero16_nt(v + i);
-        const int64_t tail0 = head + (nvec << 4);
-        if (tail0 + tid < nb) ob[tail0 + tid] = 0;
+        // (the byte count stays the 64-bit value it has always been here)
+        zero_fill_span<kGlobalThreads, int64_t>(g.change + (row * g.nx + bpx0) * (int64_t)k, npx * (int64_t)k, tid);
     }
 
     // ---- stream the series ----
@@ -267,16 +259,8 @@ omnibus_c2_retain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)
 
     bool flag;
     if (STATS) {
-        const T z = z_stat<T>(A, k, g.nlooks, g.e);
-        double zd[1] = {(double)z}, P1[1], P2[1];
-        chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
-        const T P = combine_P<T>(P1[0], P2[0], g.e.omega2);
-        flag = in && ((double)P > g.alpha);
-        if (in) {
-            const int64_t pix = row * g.nx + x0;
-            if (g.z_out) g.z_out[pix] = z;
-            if (g.p_out) g.p_out[pix] = P;
-        }
+        flag = global_flag_stats<T>(z_stat<T>(A, k, g.nlooks, g.e), 4 * (k - 1), g.e, g.alpha, in, g.z_out, g.p_out,
+                                    row * g.nx + x0);
     } else {
         flag = in && (z_approx<T>(A, k, g.nlooks, g.e) >= g.e.zlo_a);
     }
@@ -294,47 +278,21 @@ omnibus_c2_retain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)
                 g.dense_idx[(size_t)shard * g.segd + slot] = (uint32_t)(row * g.nx + bpx0 + (tid & ~63));
             }
         } else {
-            unsigned base = 0;
-            if (lane == 0)
-                base = atomicAdd(g.flag_count + shard * kCounterStride, (unsigned)__popcll(m));
-            base = __shfl(base, 0);
+            const unsigned slot = wave_claim(flag, g.flag_count + shard * kCounterStride, lane);
             if (flag) {
-                const unsigned slot = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
                 g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
-                if (slot < g.dump_cap) {
-                    T *d = g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k);
-#pragma unroll
-                    for (int t = 0; t < KMAX; ++t) {
-                        if (EXACT || t < k) {
-                            Pack<T, 4> q;
-                            q.v[0] = v[t][0];
-                            q.v[1] = v[t][1];
-                            q.v[2] = v[t][2];
-                            q.v[3] = v[t][3];
-                            *reinterpret_cast<Pack<T, 4> *>(d + 4 * t) = q;
-                        }
-                    }
-                }
+                if (slot < g.dump_cap)
+                    dump_series<T, KMAX, EXACT>(g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k), v, k);
             }
         }
     }
 
-    // ---- zero-fill this block's slice of the change map (np.zeros at nd/_change.pyx:275).
-    // Issued last so that no wait on the loads or on the atomic above also has to wait for
-    // these stores (vmcnt retires in order). ----
+    // ---- zero-fill this block's slice of the change map.  Issued last so that no wait on the
+    // loads or on the atomic above also has to wait for these stores (vmcnt retires in order). ----
     {
         const int64_t left = g.nx - bpx0;
         const int npx = left > kRetainThreads ? kRetainThreads : (int)left;
-        uint8_t *ob = g.change + (row * g.nx + bpx0) * (int64_t)k;
-        const int nb = npx * k;                              // <= 256 * k bytes
-        int head = (int)((16 - ((uintptr_t)ob & 15)) & 15);
-        if (head > nb) head = nb;
-        if (tid < head) ob[tid] = 0;
-        const int nvec = (nb - head) >> 4;
-        uint4 *vz = reinterpret_cast<uint4 *>(ob + head);
-        for (int i = tid; i < nvec; i += kRetainThreads) store_zero16_nt(vz + i);
-        const int tail0 = head + (nvec << 4);
-        if (tail0 + tid < nb) ob[tail0 + tid] = 0;
+        zero_fill_span<kRetainThreads>(g.change + (row * g.nx + bpx0) * (int64_t)k, npx * k, tid);   // <= 256 * k bytes
     }
 }
 
@@ -415,6 +373,7 @@ omnibus_c2_split_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const floa
     }
 
     // zero-fill this wave's share of the group's slice of the change map (np.zeros, nd/_change.pyx:275)
+    // (spelled out, not zero_fill_span<64 * NS>: through the helper two float32 forms take one vector register more)
     {
         const int64_t left = g.nx - gpx0;
         const int npx = left > 64 ? 64 : (int)left;
@@ -506,6 +465,7 @@ omnibus_c2_split_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const floa
         const double za = g.e.m2rho * logQ;
         const double mz = (fabs(g.e.m2rho) * g.nlooks * (double)k * 1.02) * (double)rel;
         const bool flag = in && !isdead && (isbad || (za + mz >= g.e.zlo_a));
+        // (not wave_claim: the other waves of the group need the wave's base, which it does not return)
         const unsigned long long m = __ballot(flag);
         unsigned base = 0;
         if (m != 0ull) {
@@ -576,6 +536,7 @@ omnibus_c2_split_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const floa
     // (behind the dump: the series is dead here, the chi-square series have the registers to themselves)
     if (STATS && last_slice) {
         __builtin_amdgcn_sched_barrier(0);
+        // (spelled out, not global_P: through the helper two float32 forms take one vector register more)
         const T z = z_stat<T>(W, k, g.nlooks, g.e);
         double zd[1] = {(double)z}, P1[1], P2[1];
         chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
@@ -746,8 +707,6 @@ omnibus_c2_retain_pm_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const 
             v[t][1] = img[own + t];
             v[t][2] = img[imgsz + own + t];
         }
-    constexpr bool EXACT = false;
-    (void)EXACT;
 
     if (g.write_tab && b == 0) {
         for (int j = tid; j <= k; j += kRetainThreads) g.tab_dev[j] = tab.e[j];
@@ -762,16 +721,8 @@ omnibus_c2_retain_pm_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const 
 
     bool flag;
     if (STATS) {
-        const T z = z_stat<T>(A, k, g.nlooks, g.e);
-        double zd[1] = {(double)z}, P1[1], P2[1];
-        chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
-        const T P = combine_P<T>(P1[0], P2[0], g.e.omega2);
-        flag = in && ((double)P > g.alpha);
-        if (in) {
-            const int64_t pix = row * g.nx + x0;
-            if (g.z_out) g.z_out[pix] = z;
-            if (g.p_out) g.p_out[pix] = P;
-        }
+        flag = global_flag_stats<T>(z_stat<T>(A, k, g.nlooks, g.e), 4 * (k - 1), g.e, g.alpha, in, g.z_out, g.p_out,
+                                    row * g.nx + x0);
     } else {
         flag = in && (z_approx<T>(A, k, g.nlooks, g.e) >= g.e.zlo_a);
     }
@@ -789,47 +740,21 @@ omnibus_c2_retain_pm_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const 
                 g.dense_idx[(size_t)shard * g.segd + slot] = (uint32_t)(row * g.nx + bpx0 + (tid & ~63));
             }
         } else {
-            unsigned base = 0;
-            if (lane == 0)
-                base = atomicAdd(g.flag_count + shard * kCounterStride, (unsigned)__popcll(m));
-            base = __shfl(base, 0);
+            const unsigned slot = wave_claim(flag, g.flag_count + shard * kCounterStride, lane);
             if (flag) {
-                const unsigned slot = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
                 g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
-                if (slot < g.dump_cap) {
-                    T *d = g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k);
-#pragma unroll
-                    for (int t = 0; t < KMAX; ++t) {
-                        if (t < k) {
-                            Pack<T, 4> q;
-                            q.v[0] = v[t][0];
-                            q.v[1] = v[t][1];
-                            q.v[2] = v[t][2];
-                            q.v[3] = v[t][3];
-                            *reinterpret_cast<Pack<T, 4> *>(d + 4 * t) = q;
-                        }
-                    }
-                }
+                if (slot < g.dump_cap)
+                    dump_series<T, KMAX, false>(g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k), v, k);
             }
         }
     }
 
-    // ---- zero-fill this block's slice of the change map (np.zeros at nd/_change.pyx:275).
-    // Issued last so that no wait on the loads or on the atomic above also has to wait for
-    // these stores (vmcnt retires in order). ----
+    // ---- zero-fill this block's slice of the change map.  Issued last so that no wait on the
+    // loads or on the atomic above also has to wait for these stores (vmcnt retires in order). ----
     {
         const int64_t left = g.nx - bpx0;
         const int npx = left > kRetainThreads ? kRetainThreads : (int)left;
-        uint8_t *ob = g.change + (row * g.nx + bpx0) * (int64_t)k;
-        const int nb = npx * k;                              // <= 256 * k bytes
-        int head = (int)((16 - ((uintptr_t)ob & 15)) & 15);
-        if (head > nb) head = nb;
-        if (tid < head) ob[tid] = 0;
-        const int nvec = (nb - head) >> 4;
-        uint4 *vz = reinterpret_cast<uint4 *>(ob + head);
-        for (int i = tid; i < nvec; i += kRetainThreads) store_zero16_nt(vz + i);
-        const int tail0 = head + (nvec << 4);
-        if (tail0 + tid < nb) ob[tail0 + tid] = 0;
+        zero_fill_span<kRetainThreads>(g.change + (row * g.nx + bpx0) * (int64_t)k, npx * k, tid);   // <= 256 * k bytes
     }
 }
 
@@ -1026,18 +951,15 @@ omnibus_c2_pm_dma_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
         asm volatile("" : "+s"(ks));
         dense_chain<T, KMAX, 32>(v, ks, in, ss, tab_lds, mask, handoff, cand);
         dense = true;                 // the search is done: its result serves every pixel of the wave
-        flag = cand;
-        if (dense) {
-            if (handoff) mask = 0u;                           // pass B writes that pixel's changes
-            uint8_t *wob = g.change + px0 * (int64_t)k;
-            if (change_rows_wave_ok(wob, k, np)) {
-                store_change_rows_wave(wob, out_img, k, mask, lane);
-            } else if (in) {
-                uint8_t *res = wob + (int64_t)lane * k;
-                for (int t = 0; t < k; ++t) res[t] = (uint8_t)((mask >> t) & 1u);
-            }
-            flag = handoff;
+        if (handoff) mask = 0u;                               // pass B writes that pixel's changes
+        uint8_t *wob = g.change + px0 * (int64_t)k;
+        if (change_rows_wave_ok(wob, k, np)) {
+            store_change_rows_wave(wob, out_img, k, mask, lane);
+        } else if (in) {
+            uint8_t *res = wob + (int64_t)lane * k;
+            for (int t = 0; t < k; ++t) res[t] = (uint8_t)((mask >> t) & 1u);
         }
+        flag = handoff;
     } else {
     // ---- fold in time order ----
     Accum<T> A;
@@ -1047,47 +969,23 @@ omnibus_c2_pm_dma_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
         if (t < k) A.step(v[t][0], v[t][1], v[t][2], v[t][3]);
 
     if (STATS) {
-        const T z = z_stat<T>(A, k, g.nlooks, g.e);
-        double zd[1] = {(double)z}, P1[1], P2[1];
-        chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
-        const T P = combine_P<T>(P1[0], P2[0], g.e.omega2);
-        flag = in && ((double)P > g.alpha);
-        if (in) {
-            if (g.z_out) g.z_out[x0] = z;
-            if (g.p_out) g.p_out[x0] = P;
-        }
+        flag = global_flag_stats<T>(z_stat<T>(A, k, g.nlooks, g.e), 4 * (k - 1), g.e, g.alpha, in, g.z_out, g.p_out, x0);
     } else {
         flag = in && (z_approx<T>(A, k, g.nlooks, g.e) >= g.e.zlo_a);
     }
     }
 
     // ---- list + dump ----
-    const unsigned long long m = __ballot(flag);
-    if (m != 0ull) {
-        const unsigned shard = (unsigned)(b % kShards);
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(g.flag_count + shard * kCounterStride, (unsigned)__popcll(m));
-        base = __shfl(base, 0);
+    const unsigned shard = (unsigned)(b % kShards);
+    if (__any(flag)) {
+        const unsigned slot = wave_claim(flag, g.flag_count + shard * kCounterStride, lane);
         if (flag) {
-            const unsigned slot = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
             g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)x0;
-            if (slot < g.dump_cap) {
-                T *d = g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k);
-#pragma unroll
-                for (int t = 0; t < KMAX; ++t) {
-                    if (t < k) {
-                        Pack<T, 4> q;
-                        q.v[0] = v[t][0];
-                        q.v[1] = v[t][1];
-                        q.v[2] = v[t][2];
-                        q.v[3] = v[t][3];
-                        *reinterpret_cast<Pack<T, 4> *>(d + 4 * t) = q;
-                    }
-                }
-            }
+            if (slot < g.dump_cap)
+                dump_series<T, KMAX, false>(g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k), v, k);
         }
     }
-    // ---- zero-fill this wave's slice of the change map (np.zeros at nd/_change.pyx:275) ----
+    // ---- zero-fill this wave's slice of the change map ----
     if (!dense) zero_fill_span(g.change + px0 * (int64_t)k, np * k, lane);
 }
 
@@ -1172,29 +1070,18 @@ __global__ void __launch_bounds__(64) omnibus_c2_pm_long_kernel(const OmniGlobal
 
     bool flag;
     if (STATS) {
-        const T z = z_stat<T>(A, k, g.nlooks, g.e);
-        double zd[1] = {(double)z}, P1[1], P2[1];
-        chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
-        const T P = combine_P<T>(P1[0], P2[0], g.e.omega2);
-        flag = in && ((double)P > g.alpha);
-        if (in) {
-            if (g.z_out) g.z_out[x0] = z;
-            if (g.p_out) g.p_out[x0] = P;
-        }
+        flag = global_flag_stats<T>(z_stat<T>(A, k, g.nlooks, g.e), 4 * (k - 1), g.e, g.alpha, in, g.z_out, g.p_out, x0);
     } else {
         flag = in && (z_approx<T>(A, k, g.nlooks, g.e) >= g.e.zlo_a);
     }
 
     // ---- list (no dump: the series of a listed pixel is contiguous in the variables themselves) ----
-    const unsigned long long m = __ballot(flag);
-    if (m != 0ull) {
-        const unsigned shard = (unsigned)(b % kShards);
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(g.flag_count + shard * kCounterStride, (unsigned)__popcll(m));
-        base = __shfl(base, 0);
-        if (flag) g.flag_idx[(size_t)shard * g.seg + base + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)x0;
+    const unsigned shard = (unsigned)(b % kShards);
+    if (__any(flag)) {
+        const unsigned slot = wave_claim(flag, g.flag_count + shard * kCounterStride, lane);
+        if (flag) g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)x0;
     }
-    // ---- zero-fill this wave's slice of the change map (np.zeros at nd/_change.pyx:275) ----
+    // ---- zero-fill this wave's slice of the change map ----
     zero_fill_span(g.change + px0 * (int64_t)k, np * k, lane);
 }
 
@@ -1307,26 +1194,11 @@ __global__ void __launch_bounds__(64, 2) omnibus_c2_dense_kernel(const OmniDense
         dense_chain<T, KMAX, 32>(v, k, active, ss, tab_lds, mask, handoff, cand);
         if (active && !handoff && mask != 0u) store_change_row(s.change + pix * (int64_t)k, k, mask);
         if (__any(handoff)) {
-            const unsigned long long m = __ballot(handoff);
-            unsigned base = 0;
-            if (lane == 0) base = atomicAdd(s.flag_count + shard * kCounterStride, (unsigned)__popcll(m));
-            base = __shfl(base, 0);
+            const unsigned slot = wave_claim(handoff, s.flag_count + shard * kCounterStride, lane);
             if (handoff) {
-                const unsigned slot = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
                 s.flag_idx[(size_t)shard * s.seg + slot] = (uint32_t)pix;
-                if (slot < s.dump_cap) {
-                    T *d = s.dump + ((int64_t)shard * s.dump_cap + slot) * (int64_t)(4 * k);
-#pragma unroll
-                    for (int t = 0; t < KMAX; ++t)
-                        if (t < k) {
-                            Pack<T, 4> q;
-                            q.v[0] = v[t][0];
-                            q.v[1] = v[t][1];
-                            q.v[2] = v[t][2];
-                            q.v[3] = v[t][3];
-                            *reinterpret_cast<Pack<T, 4> *>(d + 4 * t) = q;
-                        }
-                }
+                if (slot < s.dump_cap)
+                    dump_series<T, KMAX, false>(s.dump + ((int64_t)shard * s.dump_cap + slot) * (int64_t)(4 * k), v, k);
             }
         }
     }
@@ -1464,31 +1336,14 @@ omnibus_c2_chain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Stre
         listed = handoff;
     }
     if (__any(listed)) {
-        const unsigned long long lm_ = __ballot(listed);
-        unsigned base = 0;
-        if (lane == 0)
-            base = atomicAdd(g.flag_count + shard * kCounterStride, (unsigned)__popcll(lm_));
-        base = __shfl(base, 0);
+        const unsigned slot = wave_claim(listed, g.flag_count + shard * kCounterStride, lane);
         if (listed) {
-            const unsigned slot = base + (unsigned)__popcll(lm_ & ((1ull << lane) - 1ull));
             g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
-            if (slot < g.dump_cap) {
-                T *d = g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k);
-#pragma unroll
-                for (int t = 0; t < KMAX; ++t) {
-                    if (EXACT || t < k) {
-                        Pack<T, 4> q;
-                        q.v[0] = v[t][0];
-                        q.v[1] = v[t][1];
-                        q.v[2] = v[t][2];
-                        q.v[3] = v[t][3];
-                        *reinterpret_cast<Pack<T, 4> *>(d + 4 * t) = q;
-                    }
-                }
-            }
+            if (slot < g.dump_cap)
+                dump_series<T, KMAX, EXACT>(g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k), v, k);
         }
     }
-    // ---- a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275)
+    // ---- a sparse wave zero-fills its own slice of the change map
     if (!dense && wnp > 0) zero_fill_span(wob, wnp * k, lane);
     // (behind the search, where only the series itself is still alive: in front of it the fold's and the
     // chi-square series' registers pushed the 24-date form over the cap of three waves per SIMD)
@@ -1501,9 +1356,7 @@ omnibus_c2_chain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Stre
         Aw.s22 = stat_s[3][tid];
         Aw.prod = stat_p[tid];
         const T z = z_stat<T>(Aw, k, g.nlooks, g.e);
-        double zd[1] = {(double)z}, P1[1], P2[1];
-        chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
-        const T P = combine_P<T>(P1[0], P2[0], g.e.omega2);
+        const T P = global_P<T>(z, 4 * (k - 1), g.e);
         if (in) {
             const int64_t pix = row * g.nx + x0;
             if (g.z_out) g.z_out[pix] = z;
@@ -2159,13 +2012,8 @@ omnibus_c2_stream_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
         listed = handoff;
     }
     if (__any(listed)) {
-        const unsigned long long lm_ = __ballot(listed);
-        unsigned base = 0;
-        if (lane == 0)
-            base = atomicAdd(g.flag_count + shard * kCounterStride, (unsigned)__popcll(lm_));
-        base = __shfl(base, 0);
+        const unsigned slot = wave_claim(listed, g.flag_count + shard * kCounterStride, lane);
         if (listed) {
-            const unsigned slot = base + (unsigned)__popcll(lm_ & ((1ull << lane) - 1ull));
             g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
             if (slot < g.dump_cap) {
                 // the series was streamed, not kept: the (rare) listed pixel is read once more
@@ -2182,7 +2030,7 @@ omnibus_c2_stream_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
             }
         }
     }
-    // ---- a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275)
+    // ---- a sparse wave zero-fills its own slice of the change map
     if (!dense && wnp > 0) zero_fill_span(wob, wnp * k, lane);
 }
 
@@ -2450,9 +2298,7 @@ omnibus_c2_stream_chain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, con
         listed = handoff;
         if (STATS) {
             const T z = z_stat<T>(W, k, g.nlooks, g.e);
-            double zd[1] = {(double)z}, P1[1], P2[1];
-            chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
-            const T P = combine_P<T>(P1[0], P2[0], g.e.omega2);
+            const T P = global_P<T>(z, 4 * (k - 1), g.e);
             if (in) {
                 const int64_t pix = row * g.nx + x0;
                 if (g.z_out) g.z_out[pix] = z;
@@ -2461,13 +2307,8 @@ omnibus_c2_stream_chain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, con
         }
     }
     if (__any(listed)) {
-        const unsigned long long lm_ = __ballot(listed);
-        unsigned base = 0;
-        if (lane == 0)
-            base = atomicAdd(g.flag_count + shard * kCounterStride, (unsigned)__popcll(lm_));
-        base = __shfl(base, 0);
+        const unsigned slot = wave_claim(listed, g.flag_count + shard * kCounterStride, lane);
         if (listed) {
-            const unsigned slot = base + (unsigned)__popcll(lm_ & ((1ull << lane) - 1ull));
             g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
             if (slot < g.dump_cap) {
                 T *d = g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k);
@@ -2724,18 +2565,7 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_kernel(const OmniSearchA
                 if (__any(inband)) {
                     if (inband) {
                         const OmniTabEntry e = tabp[jj];
-                        const T zp = z_stat<T>(A, jj, s.nlooks, e);
-                        const double zd = (double)zp;
-                        // 0 = cannot fire (z < zlo, or NaN), 1 = fires for certain
-                        // (zhi < z < inf), 2 = inside the exact band: needs the chi-square pair
-                        int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
-                        if (verdict == 2) {
-                            double zv[1] = {zd}, P1[1], P2[1];
-                            chisq_pair<1>(zv, 4 * (jj - 1), e.lgam, P1, P2);
-                            const T P = combine_P<T>(P1[0], P2[0], e.omega2);
-                            verdict = ((double)P > s.alpha) ? 1 : 0;
-                        }
-                        fires = (verdict == 1);
+                        fires = exact_verdict<T>(z_stat<T>(A, jj, s.nlooks, e), 4 * (jj - 1), e, s.alpha);
                     }
                 }
                 if (!last) {
@@ -2853,16 +2683,7 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_rounds_kernel(const Omni
                         if (__any(inband)) {
                             if (inband) {
                                 const OmniTabEntry e = tabp[jj];
-                                const T zp = z_stat<T>(A, jj, s.nlooks, e);
-                                const double zd = (double)zp;
-                                int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
-                                if (verdict == 2) {
-                                    double zv[1] = {zd}, P1[1], P2[1];
-                                    chisq_pair<1>(zv, 4 * (jj - 1), e.lgam, P1, P2);
-                                    const T P = combine_P<T>(P1[0], P2[0], e.omega2);
-                                    verdict = ((double)P > s.alpha) ? 1 : 0;
-                                }
-                                f = (verdict == 1);
+                                f = exact_verdict<T>(z_stat<T>(A, jj, s.nlooks, e), 4 * (jj - 1), e, s.alpha);
                             }
                         }
                         if (need) {
@@ -3019,16 +2840,7 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_starts_kernel(const Omni
                 if (__any(inband)) {
                     if (inband) {
                         const OmniTabEntry e = tabp[jj];
-                        const T zp = z_stat<T>(A, jj, s.nlooks, e);
-                        const double zd = (double)zp;
-                        int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
-                        if (verdict == 2) {
-                            double zv[1] = {zd}, P1[1], P2[1];
-                            chisq_pair<1>(zv, 4 * (jj - 1), e.lgam, P1, P2);
-                            const T P = combine_P<T>(P1[0], P2[0], e.omega2);
-                            verdict = ((double)P > s.alpha) ? 1 : 0;
-                        }
-                        fires = (verdict == 1);
+                        fires = exact_verdict<T>(z_stat<T>(A, jj, s.nlooks, e), 4 * (jj - 1), e, s.alpha);
                     }
                 }
                 if (on && fires && fire_at < 0) fire_at = t;

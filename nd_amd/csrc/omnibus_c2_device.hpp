@@ -1,6 +1,6 @@
 // nd_amd/csrc/omnibus_c2_device.hpp -- device-side pieces of the dual-pol omnibus test shared by
 // omnibus.hip and omnibus_ml.hip: the reference's running state (nd/_change.pyx:53-77), pass A's
-// argument block, the wave-level zero-fill of the change map and the two-pass search on a series
+// argument block, the dump of a register-held series and the two-pass search on a series
 // held in registers (dense_chain).  Moved here verbatim from omnibus.hip (round 4) so that the
 // multilooking front end can live in a translation unit of its own.
 #pragma once
@@ -67,13 +67,6 @@ __device__ __forceinline__ double z_approx(const Accum<T> &A, int j, double nloo
 // plain accesses).  Measured on pass A: 1.30 -> 1.14 ms (profiles/r01_probe_bandwidth.txt).
 constexpr int kNtAux = 2;
 
-__device__ __forceinline__ void store_zero16_nt(uint4 *p)
-{
-    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-    const u4 z = {0u, 0u, 0u, 0u};
-    __builtin_nontemporal_store(z, reinterpret_cast<u4 *>(p));
-}
-
 // raw buffer load of one element: descriptor (SGPRs) + lane byte offset + scalar byte offset
 template <typename T>
 __device__ __forceinline__ T buffer_load(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff);
@@ -94,6 +87,24 @@ template <typename T, int N>
 struct alignas(sizeof(T) * N) Pack {
     T v[N];
 };
+
+// A series held in registers goes to its slot d of the dump ([date][4]): one 16-byte store per date.
+// EXACT: k == KMAX.
+template <typename T, int KMAX, bool EXACT>
+__device__ __forceinline__ void dump_series(T *d, const T (&v)[KMAX][4], const int k)
+{
+#pragma unroll
+    for (int t = 0; t < KMAX; ++t) {
+        if (EXACT || t < k) {
+            Pack<T, 4> q;
+            q.v[0] = v[t][0];
+            q.v[1] = v[t][1];
+            q.v[2] = v[t][2];
+            q.v[3] = v[t][3];
+            *reinterpret_cast<Pack<T, 4> *>(d + 4 * t) = q;
+        }
+    }
+}
 
 // =========================================================================================
 // pass A
@@ -151,18 +162,6 @@ constexpr int kShards = 128;
 constexpr int kCounterStride = 32;   // uint32 words between shard counters (128 B)
 constexpr int kTimeChunk = 4;
 
-
-__device__ __forceinline__ void zero_fill_span(uint8_t *ob, const int nb, const int lane)
-{
-    int head = (int)((16 - ((uintptr_t)ob & 15)) & 15);
-    if (head > nb) head = nb;
-    if (lane < head) ob[lane] = 0;
-    const int nvec = (nb - head) >> 4;
-    uint4 *vz = reinterpret_cast<uint4 *>(ob + head);
-    for (int i = lane; i < nvec; i += 64) store_zero16_nt(vz + i);
-    const int tail0 = head + (nvec << 4);
-    if (tail0 + lane < nb) ob[tail0 + lane] = 0;
-}
 
 typedef __attribute__((address_space(3))) unsigned char lds_u8_t;
 typedef __attribute__((address_space(1))) const unsigned char glb_u8_t;

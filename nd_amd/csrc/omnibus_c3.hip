@@ -156,48 +156,23 @@ __global__ void __launch_bounds__(kC3Threads) omnibus_c3_global_kernel(const C3A
 
     bool flag;
     if (STATS) {
-        const T z = z_stat3<T>(A, k, g.nlooks, g.e);
-        double zd[1] = {(double)z}, P1[1], P2[1];
-        chisq_pair<1>(zd, 9 * (k - 1), g.e.lgam, P1, P2);
-        const T P = combine_P<T>(P1[0], P2[0], g.e.omega2);
-        flag = in && ((double)P > g.alpha);
-        if (in) {
-            const int64_t pix = row * g.nx + x0;
-            if (g.z_out) g.z_out[pix] = z;
-            if (g.p_out) g.p_out[pix] = P;
-        }
+        flag = global_flag_stats<T>(z_stat3<T>(A, k, g.nlooks, g.e), 9 * (k - 1), g.e, g.alpha, in, g.z_out, g.p_out,
+                                    row * g.nx + x0);
     } else {
         flag = in && (z_approx3<T>(A, k, g.nlooks, g.e) >= g.e.zlo_a);
     }
 
+    const unsigned shard = (unsigned)(b % kC3Shards);
     if (__any(flag)) {
-        const unsigned long long m = __ballot(flag);
-        const unsigned shard = (unsigned)(b % kC3Shards);
-        unsigned base = 0;
-        if (lane == 0)
-            base = atomicAdd(g.flag_count + shard * kC3CounterStride, (unsigned)__popcll(m));
-        base = __shfl(base, 0);
-        if (flag)
-            g.flag_idx[(size_t)shard * g.seg + base + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] =
-                (uint32_t)(row * g.nx + x0);
+        const unsigned slot = wave_claim(flag, g.flag_count + shard * kC3CounterStride, lane);
+        if (flag) g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
     }
 
     // zero-fill this block's slice of the change map (issued last, never waited on)
     {
         const int64_t left = g.nx - bpx0;
         const int npx = left > kC3Threads ? kC3Threads : (int)left;
-        uint8_t *ob = g.change + (row * g.nx + bpx0) * (int64_t)k;
-        const int nb = npx * k;
-        int head = (int)((16 - ((uintptr_t)ob & 15)) & 15);
-        if (head > nb) head = nb;
-        if (tid < head) ob[tid] = 0;
-        const int nvec = (nb - head) >> 4;
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        u4 *vz = reinterpret_cast<u4 *>(ob + head);
-        const u4 zero = {0u, 0u, 0u, 0u};
-        for (int i = tid; i < nvec; i += kC3Threads) __builtin_nontemporal_store(zero, vz + i);
-        const int tail0 = head + (nvec << 4);
-        if (tail0 + tid < nb) ob[tail0 + tid] = 0;
+        zero_fill_span<kC3Threads>(g.change + (row * g.nx + bpx0) * (int64_t)k, npx * k, tid);
     }
 }
 
@@ -279,18 +254,7 @@ __global__ void __launch_bounds__(64 * kC3Slices) omnibus_c3_retain_kernel(const
     if (gpx0 < g.nx) {
         const int64_t left = g.nx - gpx0;
         const int npx = left > 64 ? 64 : (int)left;
-        uint8_t *ob = g.change + (row * g.nx + gpx0) * (int64_t)k;
-        const int nb = npx * k;
-        int head = (int)((16 - ((uintptr_t)ob & 15)) & 15);
-        if (head > nb) head = nb;
-        if (w == 0 && lane < head) ob[lane] = 0;
-        const int nvec = (nb - head) >> 4;
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        u4 *vz = reinterpret_cast<u4 *>(ob + head);
-        const u4 zero = {0u, 0u, 0u, 0u};
-        for (int i = w * 64 + lane; i < nvec; i += 64 * NW) __builtin_nontemporal_store(zero, vz + i);
-        const int tail0 = head + (nvec << 4);
-        if (w == 0 && tail0 + lane < nb) ob[tail0 + lane] = 0;
+        zero_fill_span<64 * NW>(g.change + (row * g.nx + gpx0) * (int64_t)k, npx * k, w * 64 + lane);
     }
 
     // fold the slice in time order
@@ -366,6 +330,7 @@ __global__ void __launch_bounds__(64 * kC3Slices) omnibus_c3_retain_kernel(const
         const double za = g.e.m2rho * logQ;
         const double mz = (fabs(g.e.m2rho) * g.nlooks * (double)k * 1.02) * (double)rel;
         const bool flag = in && !isdead && (isbad || (za + mz >= g.e.zlo_a));
+        // (not wave_claim: the other waves of the group need the wave's base, which it does not return)
         const unsigned long long m = __ballot(flag);
         unsigned base = 0;
         if (m != 0ull) {
@@ -512,6 +477,8 @@ __global__ void __launch_bounds__(64) omnibus_c3_pm_kernel(const C3Args<T> g, co
 
     bool flag;
     if (STATS) {
+        // (spelled out, not global_flag_stats: through the helper three float32 forms of this kernel take
+        //  64 instead of 63 vector registers)
         const T z = z_stat3<T>(A, k, g.nlooks, g.e);
         double zd[1] = {(double)z}, P1[1], P2[1];
         chisq_pair<1>(zd, 9 * (k - 1), g.e.lgam, P1, P2);
@@ -524,29 +491,13 @@ __global__ void __launch_bounds__(64) omnibus_c3_pm_kernel(const C3Args<T> g, co
     } else {
         flag = in && (z_approx3<T>(A, k, g.nlooks, g.e) >= g.e.zlo_a);
     }
+    const unsigned shard = (unsigned)(b % kC3Shards);
     if (__any(flag)) {
-        const unsigned long long m = __ballot(flag);
-        const unsigned shard = (unsigned)(b % kC3Shards);
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(g.flag_count + shard * kC3CounterStride, (unsigned)__popcll(m));
-        base = __shfl(base, 0);
-        if (flag) g.flag_idx[(size_t)shard * g.seg + base + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)x0;
+        const unsigned slot = wave_claim(flag, g.flag_count + shard * kC3CounterStride, lane);
+        if (flag) g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)x0;
     }
     // zero-fill this wave's slice of the change map
-    {
-        uint8_t *ob = g.change + px0 * (int64_t)k;
-        const int nb = np * k;
-        int head = (int)((16 - ((uintptr_t)ob & 15)) & 15);
-        if (head > nb) head = nb;
-        if (lane < head) ob[lane] = 0;
-        const int nvec = (nb - head) >> 4;
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        u4 *vz = reinterpret_cast<u4 *>(ob + head);
-        const u4 zero = {0u, 0u, 0u, 0u};
-        for (int i = lane; i < nvec; i += 64) __builtin_nontemporal_store(zero, vz + i);
-        const int tail0 = head + (nvec << 4);
-        if (tail0 + lane < nb) ob[tail0 + lane] = 0;
-    }
+    zero_fill_span(g.change + px0 * (int64_t)k, np * k, lane);
 }
 
 // ---- pass A with the search fused in (low thresholds), streaming form ---------------------------
@@ -950,14 +901,8 @@ __global__ void __launch_bounds__(kC3Threads) omnibus_c3_stream_kernel(const C3A
         listed = handoff;
     }
     if (__any(listed)) {
-        const unsigned long long lm_ = __ballot(listed);
-        unsigned base = 0;
-        if (lane == 0)
-            base = atomicAdd(g.flag_count + shard * kC3CounterStride, (unsigned)__popcll(lm_));
-        base = __shfl(base, 0);
-        if (listed)
-            g.flag_idx[(size_t)shard * g.seg + base + (unsigned)__popcll(lm_ & ((1ull << lane) - 1ull))] =
-                (uint32_t)(row * g.nx + x0);
+        const unsigned slot = wave_claim(listed, g.flag_count + shard * kC3CounterStride, lane);
+        if (listed) g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
     }
     // a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275)
     if (!dense && wnp > 0) {
@@ -1213,14 +1158,8 @@ __global__ void __launch_bounds__(kC3Threads) omnibus_c3_stream_chain_kernel(con
         listed = handoff;
     }
     if (__any(listed)) {
-        const unsigned long long lm_ = __ballot(listed);
-        unsigned base = 0;
-        if (lane == 0)
-            base = atomicAdd(g.flag_count + shard * kC3CounterStride, (unsigned)__popcll(lm_));
-        base = __shfl(base, 0);
-        if (listed)
-            g.flag_idx[(size_t)shard * g.seg + base + (unsigned)__popcll(lm_ & ((1ull << lane) - 1ull))] =
-                (uint32_t)(row * g.nx + x0);
+        const unsigned slot = wave_claim(listed, g.flag_count + shard * kC3CounterStride, lane);
+        if (listed) g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
     }
     // a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275)
     if (!dense && wnp > 0) {
@@ -1401,16 +1340,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_kernel(const C3Args<T> s
                 if (__any(inband)) {
                     if (inband) {
                         const OmniTabEntry e = s.tab_dev[jj];
-                        const T zp = z_stat3<T>(A, jj, s.nlooks, e);
-                        const double zd = (double)zp;
-                        int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
-                        if (verdict == 2) {
-                            double zv[1] = {zd}, P1[1], P2[1];
-                            chisq_pair<1>(zv, 9 * (jj - 1), e.lgam, P1, P2);
-                            const T P = combine_P<T>(P1[0], P2[0], e.omega2);
-                            verdict = ((double)P > s.alpha) ? 1 : 0;
-                        }
-                        fires = (verdict == 1);
+                        fires = exact_verdict<T>(z_stat3<T>(A, jj, s.nlooks, e), 9 * (jj - 1), e, s.alpha);
                     }
                 }
                 if (fires && fire_at < 0) fire_at = t;
@@ -1563,16 +1493,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_dump_kernel(const C3Args
                     if (__any(inband)) {
                         if (inband) {
                             const OmniTabEntry e = s.tab_dev[jj];
-                            const T zp = z_stat3<T>(A, jj, s.nlooks, e);
-                            const double zd = (double)zp;
-                            int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
-                            if (verdict == 2) {
-                                double zv[1] = {zd}, P1[1], P2[1];
-                                chisq_pair<1>(zv, 9 * (jj - 1), e.lgam, P1, P2);
-                                const T P = combine_P<T>(P1[0], P2[0], e.omega2);
-                                verdict = ((double)P > s.alpha) ? 1 : 0;
-                            }
-                            fires = (verdict == 1);
+                            fires = exact_verdict<T>(z_stat3<T>(A, jj, s.nlooks, e), 9 * (jj - 1), e, s.alpha);
                         }
                     }
                     if (fires && fire_at < 0) fire_at = t;
@@ -1688,16 +1609,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_rounds_kernel(const C3Ar
                         if (__any(inband)) {
                             if (inband) {
                                 const OmniTabEntry e = s.tab_dev[jj];
-                                const T zp = z_stat3<T>(A, jj, s.nlooks, e);
-                                const double zd = (double)zp;
-                                int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
-                                if (verdict == 2) {
-                                    double zv[1] = {zd}, P1[1], P2[1];
-                                    chisq_pair<1>(zv, 9 * (jj - 1), e.lgam, P1, P2);
-                                    const T P = combine_P<T>(P1[0], P2[0], e.omega2);
-                                    verdict = ((double)P > s.alpha) ? 1 : 0;
-                                }
-                                f = (verdict == 1);
+                                f = exact_verdict<T>(z_stat3<T>(A, jj, s.nlooks, e), 9 * (jj - 1), e, s.alpha);
                             }
                         }
                         if (need) {
@@ -1802,16 +1714,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_starts_kernel(const C3Ar
                 if (__any(inband)) {
                     if (inband) {
                         const OmniTabEntry e = s.tab_dev[jj];
-                        const T zp = z_stat3<T>(A, jj, s.nlooks, e);
-                        const double zd = (double)zp;
-                        int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
-                        if (verdict == 2) {
-                            double zv[1] = {zd}, P1[1], P2[1];
-                            chisq_pair<1>(zv, 9 * (jj - 1), e.lgam, P1, P2);
-                            const T P = combine_P<T>(P1[0], P2[0], e.omega2);
-                            verdict = ((double)P > s.alpha) ? 1 : 0;
-                        }
-                        fires = (verdict == 1);
+                        fires = exact_verdict<T>(z_stat3<T>(A, jj, s.nlooks, e), 9 * (jj - 1), e, s.alpha);
                     }
                 }
                 if (on && fires && fire_at < 0) fire_at = t;

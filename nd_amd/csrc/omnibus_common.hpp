@@ -147,6 +147,88 @@ __device__ __forceinline__ T combine_P(double P1, double P2, double omega2)
     return (T)((double)p1 + (omega2 * (double)d));
 }
 
+// ---- the steps every kernel form repeats (dual pol and full pol alike) -------------------------
+// P of the test whose statistic is z (already rounded to T): the chi-square pair in double and the
+// reference's combination.  a2 = p^2 (j - 1): 4 (j - 1) dual pol, 9 (j - 1) full pol; the statistic
+// itself (z_stat / z_stat3) stays with the caller.
+template <typename T>
+__device__ __forceinline__ T global_P(const T z, const int a2, const OmniTabEntry &e)
+{
+    double zd[1] = {(double)z}, P1[1], P2[1];
+    chisq_pair<1>(zd, a2, e.lgam, P1, P2);
+    return combine_P<T>(P1[0], P2[0], e.omega2);
+}
+
+// The global test with statistics: P for every pixel, the z / P rasters stored where asked for, and
+// the verdict (double)P > alpha of nd/_change.pyx:241-242.  `in`: the lane owns the pixel `pix`.
+template <typename T>
+__device__ __forceinline__ bool global_flag_stats(const T z, const int a2, const OmniTabEntry &e,
+                                                  const double alpha, const bool in, T *z_out,
+                                                  T *p_out, const int64_t pix)
+{
+    const T P = global_P<T>(z, a2, e);
+    const bool flag = in && ((double)P > alpha);
+    if (in) {
+        if (z_out) z_out[pix] = z;
+        if (p_out) p_out[pix] = P;
+    }
+    return flag;
+}
+
+// The exact verdict of one test from its statistic (nd/_change.pyx:235-257 asks it at :241-242 for
+// the global test of a segment and at :252 for a marginal test, whose firing starts the next segment
+// at :255): cannot fire (z < zlo, or NaN), fires for certain
+// (zhi < z < inf), and only inside the band between the two the chi-square pair decides.
+template <typename T>
+__device__ __forceinline__ bool exact_verdict(const T z, const int a2, const OmniTabEntry &e,
+                                              const double alpha)
+{
+    const double zd = (double)z;
+    // 0 = cannot fire, 1 = fires for certain, 2 = inside the exact band: needs the chi-square pair
+    int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
+    if (verdict == 2) verdict = ((double)global_P<T>(z, a2, e) > alpha) ? 1 : 0;
+    return verdict == 1;
+}
+
+// Slots of a shard's list for the flagged lanes of a wave: one ballot, one atomic on the shard's
+// counter word by the wave's first lane, and each flagged lane's rank among them.  The returned
+// slot is valid where `flag` is set.  Called under `if (__any(flag))`: a wave without a flagged
+// lane has nothing to claim and leaves the counter alone.
+__device__ __forceinline__ unsigned wave_claim(const bool flag, uint32_t *counter, const int lane)
+{
+    const unsigned long long m = __ballot(flag);
+    unsigned base = 0;
+    if (lane == 0) base = atomicAdd(counter, (unsigned)__popcll(m));
+    base = __shfl(base, 0);
+    return base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+// The change map is written once: the zeros bypass the cache hierarchy's retention.
+__device__ __forceinline__ void store_zero16_nt(uint4 *p)
+{
+    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+    const u4 z = {0u, 0u, 0u, 0u};
+    __builtin_nontemporal_store(z, reinterpret_cast<u4 *>(p));
+}
+
+// Zero-fill of nb bytes of the change map at ob (np.zeros at nd/_change.pyx:275) by STRIDE threads
+// numbered t = 0 .. STRIDE - 1: head bytes up to the first 16-byte boundary, 16-byte pieces, tail
+// bytes.  A wave calls it with its lane, a block with STRIDE = its thread count and t = tid.
+// N: type of the byte count (int wherever a block's slice is below 2 GB).
+template <int STRIDE = 64, typename N = int>
+__device__ __forceinline__ void zero_fill_span(uint8_t *ob, const N nb, const int t)
+{
+    static_assert(STRIDE >= 16, "head and tail are one byte per thread");
+    N head = (N)((16 - ((uintptr_t)ob & 15)) & 15);
+    if (head > nb) head = nb;
+    if (t < head) ob[t] = 0;
+    const N nvec = (nb - head) >> 4;
+    uint4 *vz = reinterpret_cast<uint4 *>(ob + head);
+    for (N i = t; i < nvec; i += STRIDE) store_zero16_nt(vz + i);
+    const N tail0 = head + (nvec << 4);
+    if (tail0 + t < nb) ob[tail0 + t] = 0;
+}
+
 // =========================================================================================
 // host side
 // =========================================================================================

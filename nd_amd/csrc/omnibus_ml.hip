@@ -440,9 +440,7 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
                 for (int t = 0; t < KMAX; ++t)
                     if (t < k) A.step(v[t][0], v[t][1], v[t][2], v[t][3]);
                 const float z = z_stat<float>(A, k, g.nlooks, g.e);
-                double zd[1] = {(double)z}, P1[1], P2[1];
-                chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
-                const float P = combine_P<float>(P1[0], P2[0], g.e.omega2);
+                const float P = global_P<float>(z, 4 * (k - 1), g.e);
                 if (in) {
                     if (g.z_out) g.z_out[pix] = z;
                     if (g.p_out) g.p_out[pix] = P;
@@ -466,28 +464,18 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
             for (int t = 0; t < KMAX; ++t)
                 if (t < k) A.step(v[t][0], v[t][1], v[t][2], v[t][3]);
             if (STATS) {
-                const float z = z_stat<float>(A, k, g.nlooks, g.e);
-                double zd[1] = {(double)z}, P1[1], P2[1];
-                chisq_pair<1>(zd, 4 * (k - 1), g.e.lgam, P1, P2);
-                const float P = combine_P<float>(P1[0], P2[0], g.e.omega2);
-                flag = in && ((double)P > g.alpha) && ml.list;
-                if (in) {
-                    if (g.z_out) g.z_out[pix] = z;
-                    if (g.p_out) g.p_out[pix] = P;
-                }
+                flag = global_flag_stats<float>(z_stat<float>(A, k, g.nlooks, g.e), 4 * (k - 1), g.e, g.alpha, in, g.z_out,
+                                                g.p_out, pix) &&
+                       ml.list;
             } else {
                 flag = in && (z_approx<float>(A, k, g.nlooks, g.e) >= g.e.zlo_a);
             }
         }
 
         // ---- list + dump (the multilooked series exists nowhere else: the dump holds every listed pixel) ----
-        const unsigned long long m = __ballot(flag);
-        if (m != 0ull) {
-            unsigned base = 0;
-            if (lane == 0) base = atomicAdd(g.flag_count + shard * kCounterStride, (unsigned)__popcll(m));
-            base = __shfl(base, 0);
+        if (__any(flag)) {
+            const unsigned slot = wave_claim(flag, g.flag_count + shard * kCounterStride, lane);
             if (flag) {
-                const unsigned slot = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
                 g.flag_idx[(size_t)shard * g.seg + slot] = pix;
                 float *dd = g.dump + ((int64_t)shard * g.dump_cap + slot) * (int64_t)(4 * k);
 #pragma unroll
@@ -503,7 +491,7 @@ omnibus_c2_ml_kernel(const OmniGlobalArgs<float> g, const OmniTab tab, const Omn
                 }
             }
         }
-        // ---- a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275) ----
+        // ---- a sparse wave zero-fills its own slice of the change map ----
         if (!dense && wnp > 0 && ml.list) zero_fill_span(wob, wnp * k, lane);
     }
 }
