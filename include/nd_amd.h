@@ -239,6 +239,32 @@ int nd_amd_omnibus_c3_pixel_major(const void *const planes[9], int dtype,
                                   void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /* ------------------------------------------------------------------------
+ * OmnibusTest for intensity-only stacks (pol = 'diag') -- EXTENSION.
+ * The block-diagonal case of the omnibus test: nch = q independent 1 x 1
+ * blocks (1 <= q <= 3 real intensity channels, e.g. VV and VH of detected
+ * products, which have no C12).  The reference's algorithm
+ * (nd/_change.pyx:46-77, 133-151, 224-257) with p replaced by q and a date's
+ * determinant by the product of its intensities; f = q (j - 1),
+ * rho = 1 - (j/n - 1/(n j)) / (6 (j - 1)), omega2 = -(q (j - 1) / 4) (1 - 1/rho)^2.
+ * planes[nch] share one set of element strides; n_looks is a double (> 0,
+ * finite: equivalent numbers of looks are not integers).  Every k >= 1 and
+ * every alpha is served; rasters of 2^32 - 1 pixels and more return
+ * ND_AMD_EUNSUPPORTED.  change (ny, nx, k) uint8 is written whole; z_out /
+ * p_out (ny, nx), optional, receive the whole-series statistic and its P.
+ * Workspace: 256-byte aligned, nd_amd_omnibus_diag_workspace_bytes() bytes
+ * (counters, the per-j table, one u32 per pixel; 0 for invalid arguments).
+ * ---------------------------------------------------------------------- */
+size_t nd_amd_omnibus_diag_workspace_bytes(int dtype, int nch, int64_t ny, int64_t nx, int64_t k);
+
+int nd_amd_omnibus_diag(const void *const planes[], int nch, int dtype,
+                        int64_t ny, int64_t nx, int64_t k,
+                        int64_t stride_y, int64_t stride_x, int64_t stride_t,
+                        double n_looks, double alpha,
+                        uint8_t *change, void *z_out, void *p_out,
+                        void *workspace, size_t workspace_bytes,
+                        void *hip_stream);
+
+/* ------------------------------------------------------------------------
  * Kernel convolution / boxcar.
  * Replaces  scipy.ndimage.convolve(arr, nd_kernel, output=output, **kwargs)
  *           as called at nd/filters.py:256-267 (scipy is the reference's

@@ -37,7 +37,9 @@ PER_FILE = {'nlmeans.hip': ['-fno-slp-vectorize'],
             # (omnibus_c3.hip: the pass moved 15 values per date between registers to pair scalar operations
             #  of the 3 x 3 determinants; without it the streaming search needs 133 instead of 155 registers)
             'omnibus_c3.hip': ['-fno-slp-vectorize'],
-            'omnibus_ml.hip': ['-fno-slp-vectorize']}
+            'omnibus_ml.hip': ['-fno-slp-vectorize'],
+            # (omnibus_diag.hip: the channel products and sums of two and three intensities get paired the same way)
+            'omnibus_diag.hip': ['-fno-slp-vectorize']}
 
 
 # Scratch guard.  omnibus_c2_ml_kernel waits for its LDS-DMA transfers by COUNT (s_waitcnt vmcnt(4 | 16),
@@ -53,8 +55,10 @@ PER_FILE = {'nlmeans.hip': ['-fno-slp-vectorize'],
 # classify.hip: the forest kernel picks a row's feature by a select chain so that its register copies are
 # never indexed at run time; a spill would mean that form was lost
 # kmeans_fit.hip: the step kernel keeps a row's features in registers by static index, as the predict kernels do
+# omnibus_diag.hip: pass A and the one-launch form stream the planes; the per-j table is read from the argument
+# segment by wave-uniform index or from LDS, never through a private copy
 NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_', 'classify.hip': 'class',
-              'kmeans_fit.hip': '_kernel'}
+              'kmeans_fit.hip': '_kernel', 'omnibus_diag.hip': 'omnibus_diag_'}
 # bytes per lane by the kernel's template arguments <K, KMAX, STATS, CHAIN>, keyed (STATS, CHAIN)
 SCRATCH_BUDGET = {(False, False): 0, (False, True): 96, (True, False): 256, (True, True): 384}
 

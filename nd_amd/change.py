@@ -23,6 +23,8 @@ _VARS = ['C11', 'C12__re', 'C12__im', 'C22']      # column order of nd/change.py
 # full-pol extension (no reference counterpart): plane order of nd_amd_omnibus_c3
 _VARS3 = ['C11', 'C22', 'C33', 'C12__re', 'C12__im', 'C13__re', 'C13__im', 'C23__re', 'C23__im']
 _COMPLEX = {'C12', 'C13', 'C23'}
+# intensity-only extension (pol='diag'): the channels taken when none are named
+_DIAG_DEFAULT = ['C11', 'C22', 'C33']
 
 
 class ChangeDetection(Algorithm):
@@ -132,12 +134,59 @@ def _on_device(ds, device, wanted):
     return out
 
 
+def _diag_channels(ds, channels):
+    """The names of the one to three real intensity variables the intensity-only test runs on."""
+    held = list(ds.data_vars)
+    if channels is None:
+        names = [v for v in _DIAG_DEFAULT if v in held]
+        if not names:
+            raise KeyError("OmnibusTest(pol='diag') needs at least one intensity variable: pass channels=[...] "
+                           "(e.g. ['VV', 'VH']) or provide C11 / C22 / C33; the dataset holds %s" % held)
+    else:
+        names = [channels] if isinstance(channels, str) else list(channels)
+        if not names:
+            raise KeyError("OmnibusTest(pol='diag'): channels is empty; the dataset holds %s" % held)
+        if len(names) > 3:
+            raise ValueError("OmnibusTest(pol='diag') takes one to three channels, got %d: %s" % (len(names), names))
+        missing = [v for v in names if v not in held]
+        if missing:
+            raise KeyError("OmnibusTest(pol='diag'): channels %s are missing; the dataset holds %s" % (missing, held))
+    for v in names:
+        da = ds[v]
+        if _device.np_dtype(da.values).kind == 'c':
+            raise TypeError("OmnibusTest(pol='diag'): channel '%s' is complex; the intensity-only test takes real "
+                            "intensities (for C11, C12, C22 use pol='dual')" % v)
+        if set(da.dims) != {'y', 'x', 'time'} or len(da.dims) != 3:
+            raise ValueError("channel %s must have exactly the dimensions y, x, time" % v)
+    return names
+
+
+def _omnibus_diag(ds, names, alpha, ml, n, dev, host, stats):
+    """The intensity-only test on the channels `names`: planes used where they lie when the dataset is
+    time-first on the device, transposed otherwise; ml: BoxcarFilter(w=ml) first, then n = ml ** 2."""
+    ds_m = _on_device(ds, dev, set(names)) if host else ds
+    stack = _planes_in_place(ds_m, dev, names) if ml is None else None
+    if stack is None:
+        stack = _covariance_planes(ds_m, dev, names)
+    if ml is not None:
+        stack, n = _multilook_planes(stack, int(ml)), ml * ml
+    return kernels.change_detection_diag(list(stack), alpha=alpha, n=n, dims=('time', 'y', 'x'), stats=stats)
+
+
 def _omnibus_change_detection(ds, alpha=0.01, ml=None, n=1, njobs=1, device=None, stats=False,
-                              pol='dual'):
-    if pol not in ('dual', 'full'):
-        raise ValueError("pol must be 'dual' (C11, C12, C22: the reference's test) or 'full'")
+                              pol='dual', channels=None):
+    if pol not in ('dual', 'full', 'diag'):
+        raise ValueError("pol must be 'dual' (C11, C12, C22: the reference's test), 'full' or 'diag' "
+                         "(intensities only)")
     ns = _adapter.namespace(ds)
     ds.persist() if hasattr(ds, 'persist') else None
+    if pol == 'diag':
+        names = _diag_channels(ds, channels)
+        host = not any(_device.is_tensor(ds[v].values) for v in names)
+        dev = _device.device_of(*[ds[v].values for v in names], device=device)
+        with torch.cuda.device(dev):
+            res = _omnibus_diag(ds, names, alpha, ml, n, dev, host, stats)
+        return _omnibus_result(ns, ds, res, host, stats)
     full_pol = pol == 'full'               # 3 x 3 covariance: the extension kernel, opt-in
     # like nd/change.py:66 the dual-pol test picks C11 / C12 / C22 and ignores anything else the
     # dataset carries (a C33 next to them changes nothing)
@@ -190,6 +239,11 @@ def _omnibus_change_detection(ds, alpha=0.01, ml=None, n=1, njobs=1, device=None
                 else:
                     res = kernels.change_detection(stack[0], stack[1], stack[2], stack[3], alpha=alpha,
                                                    n=int(n), dims=('time', 'y', 'x'), stats=stats)
+    return _omnibus_result(ns, ds, res, host, stats)
+
+
+def _omnibus_result(ns, ds, res, host, stats):
+    """The kernels' tensors as the reference's DataArrays (nd/change.py:71-78)."""
     change = res[0] if stats else res
     change = change.view(torch.bool)            # 0 / 1 bytes: reinterpreted, not copied
     dims = ['y', 'x', 'time']
@@ -221,7 +275,13 @@ class OmnibusTest(ChangeDetection):
     devices explicit list of ROCm devices to spread the row blocks over
     pol     'dual' (default): the reference's 2 x 2 test on C11, C12, C22, whatever else the
             dataset holds.  'full': the same test with p = 3 on C11, C22, C33, C12, C13, C23 -- an
-            extension without a reference counterpart, hence opt-in.
+            extension without a reference counterpart, hence opt-in.  'diag': the block-diagonal
+            case for intensity-only data (detected products have no C12): q independent 1 x 1
+            blocks, f = q (j - 1) degrees of freedom; `n` may be any positive real (equivalent
+            number of looks).  Also an extension.
+    channels  with pol='diag': the names of one to three real (y, x, time) variables, e.g.
+            ['VV', 'VH']; default: those of C11, C22, C33 the dataset holds.  Anything else in the
+            dataset (a C12 included) is ignored.
 
     `apply(ds)` returns the boolean DataArray 'change' with dimensions ('y', 'x', 'time')."""
 
@@ -230,6 +290,7 @@ class OmnibusTest(ChangeDetection):
         self.device = kwargs.pop('device', None)
         self.devices = kwargs.pop('devices', None)
         self.pol = kwargs.pop('pol', 'dual')
+        self.channels = kwargs.pop('channels', None)
         ChangeDetection.__init__(self, *args, **kwargs)
         self.ml, self.n, self.alpha = ml, n, alpha
 
@@ -240,7 +301,7 @@ class OmnibusTest(ChangeDetection):
         from .algorithm import parallel, resolve_devices
         run = lambda part: _omnibus_change_detection(                      # noqa: E731
             part, alpha=self.alpha, ml=self.ml, n=self.n, njobs=self.njobs, device=self.device,
-            pol=self.pol)
+            pol=self.pol, channels=self.channels)
         devs = resolve_devices(self.devices, self.njobs) if self.device is None else None
         if devs and 'y' in ds.dims:
             halo = self._buffer('y')
@@ -258,11 +319,12 @@ class OmnibusTest(ChangeDetection):
 omnibus = wrap_algorithm(OmnibusTest, 'omnibus')
 
 
-def omnibus_statistics(ds, ml=None, n=1, alpha=0.01, device=None, pol='dual'):
+def omnibus_statistics(ds, ml=None, n=1, alpha=0.01, device=None, pol='dual', channels=None):
     """change map plus the rasters the reference only computes per pixel: the test statistic
     z = -2 rho ln Q and the probability P of the global test over the whole series
     (nd/_change.pyx:46-77, 133-151).  Returns (change, z, P)."""
-    return _omnibus_change_detection(ds, alpha=alpha, ml=ml, n=n, device=device, stats=True, pol=pol)
+    return _omnibus_change_detection(ds, alpha=alpha, ml=ml, n=n, device=device, stats=True, pol=pol,
+                                     channels=channels)
 
 
 def change_count(change):

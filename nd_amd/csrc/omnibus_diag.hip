@@ -1,0 +1,738 @@
+// nd_amd/csrc/omnibus_diag.hip -- OmnibusTest for intensity-only stacks (pol = 'diag') on gfx950.
+//
+// EXTENSION: the block-diagonal case of Conradsen et al.'s omnibus test -- q independent 1 x 1 blocks,
+// q = 1, 2 or 3 real intensity channels (Sentinel-1 GRD: VV, VH; a single-channel stack: one plane).
+// The algorithm is the reference's (nd/_change.pyx:46-77, 133-151, 224-257) with p replaced by q and the
+// determinant of a date by the product of its intensities, in the arithmetic of the generic-p oracle
+// (oracle/nd_oracle_impl.h:150-200), T the data type:
+//   det_i = x_1i * x_2i * ...            left to right in T           (q = 1: x_1i itself)
+//   prod  = prod * (double)det_i          in double, in time order
+//   s_c   = s_c + x_ci                    in T, in time order
+//   dets  = s_1 * s_2 * ...               left to right in T
+//   logQ  = n ((T(q) T(j)) ln j + ln prod - j ln dets)                  in double
+//   z     = T((-2 T(rho)) logQ),  P = T(P1 + omega2 T(T(P2) - T(P1))),  change where P > alpha
+//   f = q (j - 1),  rho = host_rho(1, j, n),  omega2 = q host_omega2(1, j, n, rho) < 0
+// (additivity of Box's expansion over independent blocks).  n is a double: equivalent numbers of looks
+// of detected products are not integers.
+//
+// Regime -> kernel:
+//   alpha <  0.75 and k q sizeof(T) <= 192 B (k >= 2):  omnibus_diag_fused_kernel, ONE launch.  A lane stages
+//       its pixel's series in LDS once (a column of a wave-private image: no barrier, no bank conflict at any
+//       per-lane date) and runs the exact search from there; the wave's rows of the map leave as 16-byte pieces.
+//       192 B per pixel = 48 KB per block of 256 pixels plus the table: three blocks per CU.
+//   everything else:  pass A (omnibus_diag_global_kernel) streams the planes once, decides the whole-series
+//       test per pixel by zlo / zhi or exactly in between, zero-fills the map and lists the pixels that fire;
+//       pass B (omnibus_diag_search_kernel) searches the listed pixels exactly, one lane per pixel, reading
+//       the series from the planes -- any k.
+// Every form evaluates a test the same way (diag_fires): the f32-log2 screen against zlo_a / zhi_a, and in
+// between the exact statistic and, inside [zlo, zhi], the chi-square pair.
+#include <utility>
+
+#include "omnibus_common.hpp"
+
+namespace nd_amd {
+
+constexpr int kDgThreads = 256;
+constexpr int kDgShards = 128;
+constexpr int kDgCounterStride = 32;
+constexpr int kDgChunk = 8;          // dates per load chunk in pass A and in the staging of the fused form
+constexpr int kDgFusedBytes = 192;   // bytes of series per pixel up to which the one-launch form is used
+constexpr double kDgFusedAlpha = 0.75;
+constexpr size_t kDgCounterBytes = (size_t)kDgShards * kDgCounterStride * sizeof(uint32_t);
+
+// ---- running state of one segment: the reference's sums and product --------------------------------
+template <typename T, int Q>
+struct DiagAccum {
+    T s[Q];
+    double prod;
+    __device__ __forceinline__ void reset()
+    {
+#pragma unroll
+        for (int c = 0; c < Q; ++c) s[c] = (T)0;
+        prod = 1.0;
+    }
+    __device__ __forceinline__ void step(const T (&v)[Q])
+    {
+        T det = v[0];
+#pragma unroll
+        for (int c = 1; c < Q; ++c) det = det * v[c];
+        prod = prod * (double)det;
+#pragma unroll
+        for (int c = 0; c < Q; ++c) s[c] = s[c] + v[c];
+    }
+    __device__ __forceinline__ T det_of_sum() const
+    {
+        T d = s[0];
+#pragma unroll
+        for (int c = 1; c < Q; ++c) d = d * s[c];
+        return d;
+    }
+};
+
+template <typename T, int Q>
+__device__ __forceinline__ T diag_z(const DiagAccum<T, Q> &A, int j, double nlooks, double m2rho, double pklogk)
+{
+    const T dets = A.det_of_sum();
+    const double logQ = nlooks * ((pklogk + log(A.prod)) - ((double)j * log((double)dets)));
+    return (T)(m2rho * logQ);
+}
+
+template <typename T, int Q>
+__device__ __forceinline__ double diag_z_approx(const DiagAccum<T, Q> &A, int j, double nlooks, double m2rho,
+                                                double pklogk)
+{
+    const T dets = A.det_of_sum();
+    const double logQ = nlooks * ((pklogk + approx_ln(A.prod)) - ((double)j * approx_ln((double)dets)));
+    return m2rho * logQ;
+}
+
+// P of the test whose statistic is z.  chisq_pair's upper form sums Q(a, x) = t_{a-1} (1 + (a-1)/x + ...) over
+// the factors >= 1 and starts that sum at 1 -- right for every a >= 1, but at a = 1/2 (f = 1: one channel, two
+// dates) Q(1/2, x) is erfc(sqrt x) alone.  The dual- and full-pol tests never meet f = 1 (f = 4 (j - 1),
+// 9 (j - 1)), so the shared routine stays as it is and that one case is finished here.
+template <typename T>
+__device__ __forceinline__ T diag_P(const T z, const int a2, const OmniTabEntry &e)
+{
+    double zd[1] = {(double)z}, P1[1], P2[1];
+    chisq_pair<1>(zd, a2, e.lgam, P1, P2);
+    if (a2 == 1 && zd[0] >= 3.0 && zd[0] < INFINITY) {      // x >= a + 1
+        const double x = 0.5 * zd[0];
+        const double ta = exp(fma(0.5, log(x), -x) - e.lgam);
+        const double qa = erfc(sqrt(x));
+        P1[0] = 1.0 - qa;
+        P2[0] = 1.0 - (qa + ta + ta * (x * inv_half(3)));
+    }
+    return combine_P<T>(P1[0], P2[0], e.omega2);
+}
+
+// exact_verdict (omnibus_common.hpp) with diag_P behind it
+template <typename T>
+__device__ __forceinline__ bool diag_verdict(const T z, const int a2, const OmniTabEntry &e, const double alpha)
+{
+    const double zd = (double)z;
+    int verdict = !(zd >= e.zlo) ? 0 : ((zd > e.zhi && zd < INFINITY) ? 1 : 2);
+    if (verdict == 2) verdict = ((double)diag_P<T>(z, a2, e) > alpha) ? 1 : 0;
+    return verdict == 1;
+}
+
+// ---- the per-j table as the kernels read it ---------------------------------------------------------
+// in global memory, as the host built it
+struct DiagTabGlobal {
+    const OmniTabEntry *p;
+    __device__ __forceinline__ double m2rho(int j) const { return p[j].m2rho; }
+    __device__ __forceinline__ double pklogk(int j) const { return p[j].pklogk; }
+    __device__ __forceinline__ double zlo_a(int j) const { return p[j].zlo_a; }
+    __device__ __forceinline__ double zhi_a(int j) const { return p[j].zhi_a; }
+    __device__ __forceinline__ OmniTabEntry entry(int j) const { return p[j]; }
+};
+// the one entry pass A needs, from the kernel's arguments
+struct DiagTabOne {
+    const OmniTabEntry &e;
+    __device__ __forceinline__ double m2rho(int) const { return e.m2rho; }
+    __device__ __forceinline__ double pklogk(int) const { return e.pklogk; }
+    __device__ __forceinline__ double zlo_a(int) const { return e.zlo_a; }
+    __device__ __forceinline__ double zhi_a(int) const { return e.zhi_a; }
+    __device__ __forceinline__ OmniTabEntry entry(int) const { return e; }
+};
+// in LDS, field by field (lanes at different j read different banks): field f of entry j at p[f * kp + j],
+// f in the order of OmniTabEntry
+struct DiagTabLds {
+    const double *p;
+    int kp;
+    __device__ __forceinline__ double m2rho(int j) const { return p[j]; }
+    __device__ __forceinline__ double pklogk(int j) const { return p[kp + j]; }
+    __device__ __forceinline__ double zlo_a(int j) const { return p[5 * kp + j]; }
+    __device__ __forceinline__ double zhi_a(int j) const { return p[7 * kp + j]; }
+    __device__ __forceinline__ OmniTabEntry entry(int j) const
+    {
+        OmniTabEntry e;
+        e.m2rho = p[j];
+        e.pklogk = p[kp + j];
+        e.omega2 = p[2 * kp + j];
+        e.lgam = p[3 * kp + j];
+        e.zlo = p[4 * kp + j];
+        e.zlo_a = p[5 * kp + j];
+        e.zhi = p[6 * kp + j];
+        e.zhi_a = p[7 * kp + j];
+        return e;
+    }
+};
+
+// Does the test over the jj dates folded into A fire?  The screen first: z_approx is within aerr of the exact
+// double statistic (make_entry_diag), NaN or infinite exactly when that is; only between zlo_a and zhi_a the
+// exact statistic is formed and decided by zlo / zhi or the chi-square pair.
+template <typename T, int Q, typename Tab>
+__device__ __forceinline__ bool diag_fires(const DiagAccum<T, Q> &A, const int jj, const double nlooks,
+                                           const double alpha, const Tab &tab)
+{
+    const double za = diag_z_approx<T, Q>(A, jj, nlooks, tab.m2rho(jj), tab.pklogk(jj));
+    bool fires = (za > tab.zhi_a(jj)) && (za < INFINITY);
+    const bool inband = (za >= tab.zlo_a(jj)) && !fires;
+    if (inband) {
+        const OmniTabEntry e = tab.entry(jj);
+        fires = diag_verdict<T>(diag_z<T, Q>(A, jj, nlooks, e.m2rho, e.pklogk), Q * (jj - 1), e, alpha);
+    }
+    return fires;
+}
+
+// The sequential search of nd/_change.pyx:224-257 for one pixel, one sweep per segment: the dates of ts[l:]
+// are folded once in time order; every prefix of j >= 2 dates is the marginal test over j dates (asked until
+// the first one fires), the whole of it the global test of the segment (:241-242) -- which is also its last
+// marginal test, so r = (k - l) - 1 where no shorter one fires.  fetch(t, v): the pixel's values of date t;
+// fire(t): a change at date t (:252).
+template <typename T, int Q, typename Tab, typename Fetch, typename Fire>
+__device__ __forceinline__ void diag_search(const int k, const bool active, const double nlooks, const double alpha,
+                                            const Tab &tab, Fetch fetch, Fire fire)
+{
+    int l = 0;
+    bool done = !active || k < 2;
+    while (!done) {
+        DiagAccum<T, Q> A;
+        A.reset();
+        int fire_at = -1;
+        bool gfires = false;
+        for (int t0 = l; t0 < k; t0 += 4) {
+            T v[4][Q];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) fetch(t0 + u < k ? t0 + u : k - 1, v[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int t = t0 + u;
+                if (t < k) {
+                    A.step(v[u]);
+                    const int jj = t - l + 1;
+                    const bool last = (t == k - 1);
+                    if (jj >= 2 && (fire_at < 0 || last)) {
+                        const bool f = diag_fires<T, Q>(A, jj, nlooks, alpha, tab);
+                        if (f && fire_at < 0) fire_at = t;
+                        if (last) gfires = f;
+                    }
+                }
+            }
+        }
+        if (gfires) {
+            fire(fire_at);                    // :252
+            l = fire_at;                      // :255
+            if (l >= k - 1) done = true;      // :256
+        } else {
+            done = true;                      // :241-242
+        }
+    }
+}
+
+template <typename T>
+struct DiagArgs {
+    const T *pl[3];
+    int64_t nx, nrows, sy, sx, st, blocks_per_row;
+    int64_t nx_orig;          // pixels per row of the raster (list entries are y * nx_orig + x)
+    int k, write_tab;
+    double nlooks, alpha;
+    OmniTabEntry e;           // the whole-series test's constants
+    uint8_t *change;
+    T *z_out, *p_out;
+    uint32_t *flag_count, *flag_idx;
+    uint32_t seg;
+    OmniTabEntry *tab_dev;
+};
+
+// ---- pass A: the whole-series test, streamed -----------------------------------------------------------
+template <typename T, int Q, bool STATS>
+__global__ void __launch_bounds__(kDgThreads) omnibus_diag_global_kernel(const DiagArgs<T> g, const OmniTab tab)
+{
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t b = blockIdx.x;
+    const int64_t row = b / g.blocks_per_row;
+    const int64_t bx = b - row * g.blocks_per_row;
+    const int64_t bpx0 = bx * (int64_t)kDgThreads;
+    const int64_t x0 = bpx0 + tid;
+    const int k = g.k;
+    const bool in = x0 < g.nx;
+
+    if (g.write_tab && b == 0)
+        for (int j = tid; j <= k; j += kDgThreads) g.tab_dev[j] = tab.e[j];
+
+    DiagAccum<T, Q> A;
+    A.reset();
+    {
+        const int64_t xc = in ? x0 : g.nx - 1;                // idle lanes re-read the last pixel
+        const int64_t off0 = row * g.sy + xc * g.sx;
+        for (int t0 = 0; t0 < k; t0 += kDgChunk) {
+            T v[kDgChunk][Q];
+#pragma unroll
+            for (int tt = 0; tt < kDgChunk; ++tt) {
+                const int t = t0 + tt < k ? t0 + tt : k - 1;
+                const int64_t off = off0 + (int64_t)t * g.st;
+#pragma unroll
+                for (int c = 0; c < Q; ++c) v[tt][c] = __builtin_nontemporal_load(g.pl[c] + off);
+            }
+#pragma unroll
+            for (int tt = 0; tt < kDgChunk; ++tt)
+                if (t0 + tt < k) A.step(v[tt]);
+        }
+    }
+
+    bool flag;
+    if (STATS) {
+        const T z = diag_z<T, Q>(A, k, g.nlooks, g.e.m2rho, g.e.pklogk);
+        const T P = diag_P<T>(z, Q * (k - 1), g.e);
+        flag = in && ((double)P > g.alpha);
+        if (in) {
+            const int64_t pix = row * g.nx + x0;
+            if (g.z_out) g.z_out[pix] = z;
+            if (g.p_out) g.p_out[pix] = P;
+        }
+    } else {
+        const DiagTabOne one{g.e};
+        flag = in && diag_fires<T, Q>(A, k, g.nlooks, g.alpha, one);
+    }
+    flag = flag && k >= 2;                                    // a single date has no change to place
+
+    const unsigned shard = (unsigned)(b % kDgShards);
+    if (__any(flag)) {
+        const unsigned slot = wave_claim(flag, g.flag_count + shard * kDgCounterStride, lane);
+        if (flag) g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
+    }
+
+    // zero-fill this block's slice of the change map (np.zeros, nd/_change.pyx:275; issued last, never waited on)
+    {
+        const int64_t left = g.nx - bpx0;
+        const int npx = left > kDgThreads ? kDgThreads : (int)left;
+        zero_fill_span<kDgThreads, int64_t>(g.change + (row * g.nx + bpx0) * (int64_t)k, (int64_t)npx * k, tid);
+    }
+}
+
+// ---- pass B: the exact search over the listed pixels, any k ----------------------------------------------
+template <typename T, int Q>
+__global__ void __launch_bounds__(64) omnibus_diag_search_kernel(const DiagArgs<T> s)
+{
+    const int lane = threadIdx.x;
+    const int k = s.k;
+    const unsigned shard = blockIdx.x % kDgShards;
+    const unsigned lblock = blockIdx.x / kDgShards, nlblock = gridDim.x / kDgShards;
+    const uint32_t n = s.flag_count[shard * kDgCounterStride];
+    const uint32_t *list = s.flag_idx + (size_t)shard * s.seg;
+    const DiagTabGlobal tab{s.tab_dev};
+    for (uint32_t base = lblock * 64u; base < n; base += nlblock * 64u) {
+        const uint32_t idx = base + (uint32_t)lane;
+        const bool active = idx < n;
+        const int64_t pix = active ? (int64_t)list[idx] : 0;
+        const int64_t row = pix / s.nx_orig, col = pix - row * s.nx_orig;
+        const int64_t off = row * s.sy + col * s.sx;
+        uint8_t *res = s.change + pix * (int64_t)k;           // the row was zero-filled by pass A
+        diag_search<T, Q>(
+            k, active, s.nlooks, s.alpha, tab,
+            [&](const int t, T(&v)[Q]) {
+#pragma unroll
+                for (int c = 0; c < Q; ++c) v[c] = s.pl[c][off + (int64_t)t * s.st];
+            },
+            [&](const int t) { res[t] = 1; });
+    }
+}
+
+// ---- the one-launch form for short series ----------------------------------------------------------------
+// LDS: [table: 8 (k + 1) doubles][per wave: k Q rows of 64 values, value (t, c) of the lane's pixel at
+// ((t Q + c) 64 + lane)].  A lane reads only what it wrote, so the image needs no barrier; the one barrier is
+// for the table.  k <= 48 (float32) / 24 (float64) dates: the changes of a pixel are bits of one 64-bit word.
+template <typename T, int Q, bool STATS>
+__global__ void __launch_bounds__(kDgThreads) omnibus_diag_fused_kernel(const DiagArgs<T> g, const OmniTab tab)
+{
+    extern __shared__ __align__(16) unsigned char nd_smem_diag[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int k = g.k, kp = k + 1;
+    double *tl = reinterpret_cast<double *>(nd_smem_diag);
+    T *ser = reinterpret_cast<T *>(nd_smem_diag + (size_t)kp * sizeof(OmniTabEntry)) + (size_t)(tid >> 6) * (k * Q * 64);
+    const int64_t b = blockIdx.x;
+    const int64_t row = b / g.blocks_per_row;
+    const int64_t bx = b - row * g.blocks_per_row;
+    const int64_t bpx0 = bx * (int64_t)kDgThreads;
+    const int64_t x0 = bpx0 + tid;
+    const bool in = x0 < g.nx;
+
+    // the table into LDS: entry j (wave-uniform: scalar loads from the argument segment) by wave j mod 4, its
+    // eight fields by the wave's first eight lanes
+    {
+        const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll 1
+        for (int j = w; j <= k; j += kDgThreads / 64) {
+            const OmniTabEntry e = tab.e[j];
+            const double f = lane == 0 ? e.m2rho : lane == 1 ? e.pklogk : lane == 2 ? e.omega2 : lane == 3 ? e.lgam
+                           : lane == 4 ? e.zlo : lane == 5 ? e.zlo_a : lane == 6 ? e.zhi : e.zhi_a;
+            if (lane < 8) tl[lane * kp + j] = f;
+        }
+    }
+    {
+        const int64_t xc = in ? x0 : g.nx - 1;                // idle lanes re-read the last pixel
+        const int64_t off0 = row * g.sy + xc * g.sx;
+        for (int t0 = 0; t0 < k; t0 += kDgChunk) {
+            T v[kDgChunk][Q];
+#pragma unroll
+            for (int tt = 0; tt < kDgChunk; ++tt) {
+                const int t = t0 + tt < k ? t0 + tt : k - 1;
+                const int64_t off = off0 + (int64_t)t * g.st;
+#pragma unroll
+                for (int c = 0; c < Q; ++c) v[tt][c] = __builtin_nontemporal_load(g.pl[c] + off);
+            }
+#pragma unroll
+            for (int tt = 0; tt < kDgChunk; ++tt)
+                if (t0 + tt < k) {
+#pragma unroll
+                    for (int c = 0; c < Q; ++c) ser[((t0 + tt) * Q + c) * 64 + lane] = v[tt][c];
+                }
+        }
+    }
+    __syncthreads();
+    const DiagTabLds tv{tl, kp};
+    auto fetch = [&](const int t, T(&v)[Q]) {
+#pragma unroll
+        for (int c = 0; c < Q; ++c) v[c] = ser[(t * Q + c) * 64 + lane];
+    };
+    if (STATS) {
+        DiagAccum<T, Q> A;
+        A.reset();
+        for (int t = 0; t < k; ++t) {
+            T v[Q];
+            fetch(t, v);
+            A.step(v);
+        }
+        const T z = diag_z<T, Q>(A, k, g.nlooks, g.e.m2rho, g.e.pklogk);
+        const T P = diag_P<T>(z, Q * (k - 1), g.e);
+        if (in) {
+            const int64_t pix = row * g.nx + x0;
+            if (g.z_out) g.z_out[pix] = z;
+            if (g.p_out) g.p_out[pix] = P;
+        }
+    }
+    unsigned long long mask = 0ull;
+    diag_search<T, Q>(k, in, g.nlooks, g.alpha, tv, fetch, [&](const int t) { mask |= 1ull << t; });
+
+    // the wave's rows of the map: 64 k contiguous bytes, through the wave's own image (every lane of the wave
+    // is through with its series here: LDS operations of a wave complete in order)
+    const int64_t wpx0 = bpx0 + (tid & ~63);
+    const int64_t wleft = g.nx - wpx0;
+    const int wnp = wleft > 64 ? 64 : (wleft > 0 ? (int)wleft : 0);
+    uint8_t *wob = g.change + (row * g.nx + wpx0) * (int64_t)k;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (change_rows_wave_ok(wob, k, wnp)) {
+        store_change_rows_wave(wob, reinterpret_cast<uint32_t *>(ser), k, mask, lane);
+    } else if (in) {
+        uint8_t *res = wob + (int64_t)lane * k;
+        for (int t = 0; t < k; ++t) res[t] = (uint8_t)((mask >> t) & 1ull);
+    }
+}
+
+// =========================================================================================
+// host side
+// =========================================================================================
+// host twin of diag_P's chi-square pair (host_chisq_pair finished at f = 1)
+static inline void host_chisq_pair_diag(double z, int a2, double lgam_a1, double *P1, double *P2)
+{
+    host_chisq_pair(z, a2, lgam_a1, P1, P2);
+    if (a2 == 1 && z >= 3.0 && z < INFINITY) {
+        const double x = 0.5 * z;
+        const double ta = exp((0.5 * log(x) - x) - lgam_a1);
+        const double qa = erfc(sqrt(x));
+        *P1 = 1.0 - qa;
+        *P2 = 1.0 - (qa + ta + ta * (x / 1.5));
+    }
+}
+
+// Decision bounds with omega2 < 0 (omni_bounds gives up outside 0 <= omega2 <= 1, where P is a mixture of two
+// CDFs).  With w = -omega2 > 0, x = z / 2, a = f / 2 and t_a = x^a e^-x / Gamma(a + 1):
+//   P(a, x) - P(a + 2, x) = t_a + t_{a+1},  so  P = P(a, x) + w (t_a + t_{a+1});
+//   d/dx P(a, x) = t_{a-1},  d/dx t_a = t_{a-1} - t_a,  t_{a+1} = t_{a-1} x^2 / (a (a + 1)),  hence
+//   dP/dx = t_{a-1} (1 + w) - w t_{a+1} = t_{a-1} (1 + w - w x^2 / (a (a + 1))).
+// P rises from 0 up to x* = sqrt(a (a + 1) (1 + 1/w)) and falls beyond it towards its limit 1, so P >= 1 on
+// [x*, inf).  For a target tau < 1 the crossing P = tau is therefore unique, lies below x*, and P < tau before
+// it, P > tau behind it: the bisection of omni_bounds holds with the bracket [0, 2 x*].  That needs
+// alpha + margin < 1; otherwise (and for j < 2, where rho is NaN) every test is evaluated exactly -- with
+// omega2 < 0, P passes 1, so "P <= 1 < alpha: nothing fires" does not hold here either.
+// margin: the kernel's roundings of P1, P2, their difference and P to T, and the series' ~1e-13 (omni_bounds).
+template <typename T>
+static void diag_bounds(int j, int a2, double omega2, double lgam, double alpha, double *zlo, double *zhi)
+{
+    *zlo = -INFINITY;
+    *zhi = INFINITY;
+    if (j < 2 || a2 < 1) return;
+    if (!(omega2 < 0.0) || !(omega2 > -INFINITY) || !(alpha == alpha)) return;
+    const double ulp = sizeof(T) == 4 ? 5.9604644775390625e-08 : 1.1102230246251565e-16;
+    const double w = -omega2;
+    const double a = 0.5 * (double)a2;
+    const double margin = 16.0 * ulp * (1.0 + 2.0 * w) + 1e-11 +
+                          8.0 * a * (1.0 + log(a + 2.0)) * 1.1102230246251565e-16;
+    const double thi = alpha + margin, tlo = alpha - margin;
+    if (!(thi < 1.0 - 1e-9)) return;
+    const double zcap = 4.0 * sqrt(a * (a + 1.0) * (1.0 + 1.0 / w));      // z = 2 x at x = 2 x*
+    if (!(zcap > 0.0) || !(zcap < INFINITY)) return;
+    auto Pz = [&](double z) {
+        double p1, p2;
+        host_chisq_pair_diag(z, a2, lgam, &p1, &p2);
+        return p1 + omega2 * (p2 - p1);
+    };
+    auto quantile = [&](double target, double *lo_out, double *hi_out) -> bool {
+        double lo = 0.0, hi = zcap;
+        if (!(Pz(hi) >= target)) return false;
+        for (int it = 0; it < 200; ++it) {
+            const double mid = 0.5 * (lo + hi);
+            if (Pz(mid) < target)
+                lo = mid;
+            else
+                hi = mid;
+            if (hi - lo <= 1e-15 * hi) break;
+        }
+        *lo_out = lo;
+        *hi_out = hi;
+        return true;
+    };
+    double lo, hi;
+    if (tlo > 0.0 && quantile(tlo, &lo, &hi)) *zlo = lo * (1.0 - 1e-9);
+    if (thi > 0.0 && quantile(thi, &lo, &hi)) *zhi = hi * (1.0 + 1e-9);
+}
+
+// make_entry (omnibus_common.hpp) for q independent 1 x 1 blocks and a real number of looks
+template <typename T>
+static OmniTabEntry make_entry_diag(int j, int q, double n, double alpha)
+{
+    OmniTabEntry e;
+    const double k = (double)j;
+    const double rho = host_rho(1.0, k, n);                   // does not depend on q
+    const T rho_t = (T)rho;
+    e.m2rho = -2.0 * (double)rho_t;
+    const T pk = (T)q * (T)j;
+    e.pklogk = (double)pk * log(k);
+    e.omega2 = (double)q * host_omega2(1.0, k, n, rho);       // -(q (j - 1) / 4) (1 - 1/rho)^2
+    const int a2 = q * (j - 1);                               // f
+    e.lgam = lgamma(0.5 * (double)a2 + 1.0);
+    diag_bounds<T>(j, a2, e.omega2, e.lgam, alpha, &e.zlo, &e.zhi);
+    // bounds for the f32-log2 screen: |z_approx - z| <= |m2rho| n (j + 1) 4.2e-8 before z is rounded to T
+    // (two hardware log2 of <= 6e-8 absolute, times ln 2, the second one j times); aerr is twenty times that,
+    // and the rounding of z to T (which zlo / zhi refer to) is added
+    const double eps = sizeof(T) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16;
+    const double aerr = 1e-6 * fabs(e.m2rho) * n * (k + 1.0);
+    e.zlo_a = (e.zlo > -INFINITY && e.zlo < INFINITY) ? e.zlo - (aerr + (2.0 * eps + 1e-9) * fabs(e.zlo)) : e.zlo;
+    e.zhi_a = (e.zhi < INFINITY) ? e.zhi + (aerr + (2.0 * eps + 1e-9) * fabs(e.zhi)) : INFINITY;
+    if (!(aerr == aerr) || !(aerr < INFINITY)) {              // rho is NaN for j = 1: exact path only
+        e.zlo = e.zlo_a = -INFINITY;
+        e.zhi = e.zhi_a = INFINITY;
+    }
+    return e;
+}
+
+// the table cache of omnibus_common.hpp (TabCacheEntry) with this family's key: q and a real n
+struct DiagTabKey {
+    int k, dtype, q;
+    double n, alpha;
+};
+static std::vector<OmniTabEntry> get_table_diag(int k, double n, double alpha, int dtype, int q)
+{
+    static std::mutex mu;
+    static std::vector<std::pair<DiagTabKey, std::vector<OmniTabEntry>>> cache;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (const auto &c : cache)
+            if (c.first.k == k && c.first.dtype == dtype && c.first.q == q &&
+                memcmp(&c.first.n, &n, sizeof(double)) == 0 && memcmp(&c.first.alpha, &alpha, sizeof(double)) == 0)
+                return c.second;
+    }
+    std::vector<OmniTabEntry> tab((size_t)k + 1);
+    memset(tab.data(), 0, tab.size() * sizeof(OmniTabEntry));
+    for (int j = 1; j <= k; ++j)
+        tab[j] = dtype == ND_AMD_F32 ? make_entry_diag<float>(j, q, n, alpha) : make_entry_diag<double>(j, q, n, alpha);
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (cache.size() >= 32) cache.erase(cache.begin());
+        DiagTabKey key;
+        memset(&key, 0, sizeof(key));
+        key.k = k;
+        key.dtype = dtype;
+        key.q = q;
+        key.n = n;
+        key.alpha = alpha;
+        cache.emplace_back(key, tab);
+    }
+    return tab;
+}
+
+// workspace: [counters][per-j table][pixel lists: kDgShards x seg x u32]
+struct DiagWorkspace {
+    size_t off_count, off_tab, off_idx, total;
+    uint32_t seg;
+};
+static DiagWorkspace diag_layout(int64_t npix, int64_t ny, int64_t k)
+{
+    DiagWorkspace w;
+    // (a row may end inside a block: at most ceil(npix / 256) + ny blocks of <= 256 entries)
+    const int64_t nb = ceil_div(npix, kDgThreads) + ny;
+    w.seg = (uint32_t)((ceil_div(nb, kDgShards) + 1) * kDgThreads);
+    w.off_count = 0;
+    w.off_tab = align256(kDgCounterBytes);
+    w.off_idx = w.off_tab + align256((size_t)(k + 1) * sizeof(OmniTabEntry));
+    w.total = w.off_idx + align256((size_t)w.seg * kDgShards * sizeof(uint32_t));
+    return w;
+}
+
+template <typename T, int Q>
+static int omnibus_diag_impl(const void *const planes[], int64_t ny, int64_t nx, int64_t k, int64_t sy, int64_t sx,
+                             int64_t st, double n_looks, double alpha, uint8_t *change, void *z_out, void *p_out,
+                             void *workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    const int64_t npix = ny * nx;
+    const DiagWorkspace w = diag_layout(npix, ny, k);
+    if (workspace == nullptr || workspace_bytes < w.total) {
+        set_error("nd_amd_omnibus_diag: workspace of %zu bytes needed, %zu given", w.total, workspace_bytes);
+        return ND_AMD_EWORKSPACE;
+    }
+    if (((uintptr_t)workspace & 255) != 0) {
+        set_error("nd_amd_omnibus_diag: workspace must be 256-byte aligned");
+        return ND_AMD_EINVAL;
+    }
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    const std::vector<OmniTabEntry> htab =
+        get_table_diag((int)k, n_looks, alpha, sizeof(T) == 4 ? ND_AMD_F32 : ND_AMD_F64, Q);
+    OmniTab tab;
+    memset(&tab, 0, sizeof(tab));
+    OmniTabEntry *tab_dev = reinterpret_cast<OmniTabEntry *>(ws + w.off_tab);
+    const bool tab_in_args = k <= kTabArgs;
+    if (tab_in_args) {
+        memcpy(tab.e, htab.data(), htab.size() * sizeof(OmniTabEntry));
+    } else {
+        // long series: the table goes through a pageable host copy (synchronises the stream once)
+        hipError_t e = hipMemcpyAsync(tab_dev, htab.data(), htab.size() * sizeof(OmniTabEntry), hipMemcpyHostToDevice,
+                                      stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        ND_HIP_CHECK(e);
+    }
+
+    DiagArgs<T> g;
+    for (int c = 0; c < 3; ++c) g.pl[c] = static_cast<const T *>(planes[c < Q ? c : 0]);
+    const bool flat = (sx == 1) && (sy == nx);
+    g.nx = flat ? npix : nx;
+    g.nrows = flat ? 1 : ny;
+    g.nx_orig = nx;
+    g.sy = sy;
+    g.sx = sx;
+    g.st = st;
+    g.blocks_per_row = ceil_div(g.nx, kDgThreads);
+    g.k = (int)k;
+    g.write_tab = tab_in_args ? 1 : 0;
+    g.nlooks = n_looks;
+    g.alpha = alpha;
+    g.e = htab[(size_t)k];
+    g.change = change;
+    g.z_out = static_cast<T *>(z_out);
+    g.p_out = static_cast<T *>(p_out);
+    g.flag_count = reinterpret_cast<uint32_t *>(ws + w.off_count);
+    g.tab_dev = tab_dev;
+    g.flag_idx = reinterpret_cast<uint32_t *>(ws + w.off_idx);
+    g.seg = w.seg;
+    const int64_t nblocks = g.blocks_per_row * g.nrows;
+    if (nblocks > 0x7fffffffLL) {                             // (only a strided raster of 2^31 rows and more)
+        set_error("nd_amd_omnibus_diag: raster too large for one launch");
+        return ND_AMD_EUNSUPPORTED;
+    }
+    const bool stats = z_out != nullptr || p_out != nullptr;
+    const dim3 grid((unsigned)nblocks), block(kDgThreads);
+
+    // (The launches are timed under the dual-pol test's timer ids -- OMNIBUS_FUSED, _GLOBAL, _SEARCH, reported as
+    //  omnibus_c2_* -- as the full-pol unit does: the ids name the role of a launch in an omnibus call, and one call
+    //  runs one family.)
+    // low thresholds fire on nearly every pixel: the search runs inside the one launch where the series fit
+    const bool fused = k >= 2 && k * Q * (int64_t)sizeof(T) <= kDgFusedBytes && alpha < kDgFusedAlpha;
+    if (fused) {
+        const size_t lds = (size_t)(k + 1) * sizeof(OmniTabEntry) + (size_t)k * Q * kDgThreads * sizeof(T);
+        KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_FUSED, stream);
+        if (stats)
+            hipLaunchKernelGGL((omnibus_diag_fused_kernel<T, Q, true>), grid, block, lds, stream, g, tab);
+        else
+            hipLaunchKernelGGL((omnibus_diag_fused_kernel<T, Q, false>), grid, block, lds, stream, g, tab);
+        ND_HIP_CHECK(hipGetLastError());
+        return ND_AMD_OK;
+    }
+
+    ND_HIP_CHECK(hipMemsetAsync(g.flag_count, 0, kDgCounterBytes, stream));
+    {
+        KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
+        if (stats)
+            hipLaunchKernelGGL((omnibus_diag_global_kernel<T, Q, true>), grid, block, 0, stream, g, tab);
+        else
+            hipLaunchKernelGGL((omnibus_diag_global_kernel<T, Q, false>), grid, block, 0, stream, g, tab);
+        ND_HIP_CHECK(hipGetLastError());
+    }
+    if (k >= 2) {
+        int64_t per_shard = ceil_div(ceil_div(npix, kDgShards), 64);
+        if (per_shard > 64) per_shard = 64;
+        if (per_shard < 1) per_shard = 1;
+        KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_SEARCH, stream);
+        hipLaunchKernelGGL((omnibus_diag_search_kernel<T, Q>), dim3((unsigned)(per_shard * kDgShards)), dim3(64), 0,
+                           stream, g);
+        ND_HIP_CHECK(hipGetLastError());
+    }
+    return ND_AMD_OK;
+}
+
+template <typename T>
+static int omnibus_diag_q(int nch, const void *const planes[], int64_t ny, int64_t nx, int64_t k, int64_t sy,
+                          int64_t sx, int64_t st, double n_looks, double alpha, uint8_t *change, void *z_out,
+                          void *p_out, void *workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    if (nch == 1)
+        return omnibus_diag_impl<T, 1>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out, workspace,
+                                       workspace_bytes, stream);
+    if (nch == 2)
+        return omnibus_diag_impl<T, 2>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out, workspace,
+                                       workspace_bytes, stream);
+    return omnibus_diag_impl<T, 3>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out, workspace,
+                                   workspace_bytes, stream);
+}
+
+}  // namespace nd_amd
+
+using namespace nd_amd;
+
+extern "C" size_t nd_amd_omnibus_diag_workspace_bytes(int dtype, int nch, int64_t ny, int64_t nx, int64_t k)
+{
+    if ((dtype != ND_AMD_F32 && dtype != ND_AMD_F64) || nch < 1 || nch > 3 || ny < 0 || nx < 0 || k < 0) return 0;
+    return diag_layout(ny * nx, ny, k).total;
+}
+
+extern "C" int nd_amd_omnibus_diag(const void *const planes[], int nch, int dtype, int64_t ny, int64_t nx, int64_t k,
+                                   int64_t stride_y, int64_t stride_x, int64_t stride_t, double n_looks, double alpha,
+                                   uint8_t *change, void *z_out, void *p_out, void *workspace, size_t workspace_bytes,
+                                   void *hip_stream)
+{
+    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
+        set_error("nd_amd_omnibus_diag: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", dtype);
+        return ND_AMD_EINVAL;
+    }
+    if (nch < 1 || nch > 3) {
+        set_error("nd_amd_omnibus_diag: one to three intensity channels, got %d", nch);
+        return ND_AMD_EINVAL;
+    }
+    if (ny < 0 || nx < 0 || k < 0) {
+        set_error("nd_amd_omnibus_diag: negative shape");
+        return ND_AMD_EINVAL;
+    }
+    if (!(n_looks > 0.0) || !(n_looks < INFINITY)) {
+        set_error("nd_amd_omnibus_diag: n_looks must be positive and finite, got %g", n_looks);
+        return ND_AMD_EINVAL;
+    }
+    if (ny == 0 || nx == 0 || k == 0) return ND_AMD_OK;
+    if (!planes || !change) {
+        set_error("nd_amd_omnibus_diag: null data pointer");
+        return ND_AMD_EINVAL;
+    }
+    for (int c = 0; c < nch; ++c)
+        if (!planes[c]) {
+            set_error("nd_amd_omnibus_diag: plane %d is null", c);
+            return ND_AMD_EINVAL;
+        }
+    if (ny * nx >= 0xffffffffLL || k > 0x7fffffffLL / 3) {
+        set_error("nd_amd_omnibus_diag: raster exceeds the 32-bit pixel index");
+        return ND_AMD_EUNSUPPORTED;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (dtype == ND_AMD_F32)
+        return omnibus_diag_q<float>(nch, planes, ny, nx, k, stride_y, stride_x, stride_t, n_looks, alpha, change,
+                                     z_out, p_out, workspace, workspace_bytes, stream);
+    return omnibus_diag_q<double>(nch, planes, ny, nx, k, stride_y, stride_x, stride_t, n_looks, alpha, change, z_out,
+                                  p_out, workspace, workspace_bytes, stream);
+}

@@ -6,6 +6,7 @@ stream.  PyTorch is only the device-memory / stream plumbing here.
 Each function names the native call of the reference it stands in for:
 
   change_detection(...)      nd._change.change_detection          nd/_change.pyx:263-287
+  change_detection_diag(...) the same for intensity-only stacks (extension, no reference counterpart)
   correlate_footprint(...)   scipy.ndimage.convolve               nd/filters.py:256-267
   pixelwise_nlmeans_3d(...)  nd._filters._pixelwise_nlmeans_3d    nd/_filters.pyx:320-420
 """
@@ -219,6 +220,48 @@ def change_detection_c3(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=False
             _lib.check(L.nd_amd_omnibus_c3(
                 ptrs, _DT[p0.dtype], ny, nx, k, p0.stride(ay), p0.stride(ax), p0.stride(at),
                 int(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
+                _stream_ptr(dev)))
+            ws.record_stream(torch.cuda.current_stream(dev))
+    if stats:
+        return change, z, P
+    return change
+
+
+def change_detection_diag(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=False):
+    """Omnibus change detection on intensity-only stacks -- an extension: the block-diagonal case of the
+    test, q independent 1 x 1 blocks.  planes: one to three real CUDA tensors (e.g. [VV, VH]) of identical
+    shape/strides/dtype, axes named by `dims`; n: the (equivalent) number of looks, any positive real.
+    Returns uint8 (y, x, time) [, z, P]."""
+    planes = list(planes)
+    if not 1 <= len(planes) <= 3:
+        raise ValueError('the intensity-only test takes one to three channels, got %d' % len(planes))
+    p0 = planes[0]
+    for i, t in enumerate(planes):
+        _require_cuda(t, 'planes[%d]' % i)
+        # strides of length-1 axes address nothing: views of one buffer may carry different ones
+        same_strides = t.dim() == 3 and all(a == b for a, b, n_ in zip(t.stride(), p0.stride(), t.shape)
+                                            if n_ > 1)
+        if (t.dim() != 3 or t.shape != p0.shape or not same_strides
+                or t.dtype != p0.dtype or t.device != p0.device):
+            raise ValueError('the intensity planes must be 3-D and share shape, strides, dtype and device')
+    dims = tuple(dims)
+    if sorted(dims) != ['time', 'x', 'y']:
+        raise ValueError("dims must be a permutation of ('time', 'y', 'x')")
+    ay, ax, at = dims.index('y'), dims.index('x'), dims.index('time')
+    ny, nx, k = p0.shape[ay], p0.shape[ax], p0.shape[at]
+    dev = p0.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        change = torch.empty((ny, nx, k), dtype=torch.uint8, device=dev)
+        z = torch.empty((ny, nx), dtype=p0.dtype, device=dev) if stats else None
+        P = torch.empty((ny, nx), dtype=p0.dtype, device=dev) if stats else None
+        if ny * nx * k > 0:
+            nbytes = L.nd_amd_omnibus_diag_workspace_bytes(_DT[p0.dtype], len(planes), ny, nx, k)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ptrs = (C.c_void_p * len(planes))(*[t.data_ptr() for t in planes])
+            _lib.check(L.nd_amd_omnibus_diag(
+                ptrs, len(planes), _DT[p0.dtype], ny, nx, k, p0.stride(ay), p0.stride(ax), p0.stride(at),
+                float(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
                 _stream_ptr(dev)))
             ws.record_stream(torch.cuda.current_stream(dev))
     if stats:
