@@ -79,6 +79,7 @@ extern "C" {
 #define ND_AMD_KERNEL_KMEANS_STEP     23  /* nd_amd_kmeans_step: the pass over the rows and the fold of its partials */
 #define ND_AMD_KERNEL_FEATURE_MOMENTS 24  /* nd_amd_feature_moments, the whole call (both passes) */
 #define ND_AMD_KERNEL_GATHER_ROWS     25  /* nd_amd_gather_rows */
+#define ND_AMD_KERNEL_CHANGE_SEGMENTS 26  /* nd_amd_change_segments */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -263,6 +264,42 @@ int nd_amd_omnibus_diag(const void *const planes[], int nch, int dtype,
                         uint8_t *change, void *z_out, void *p_out,
                         void *workspace, size_t workspace_bytes,
                         void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Direction of each detected change and the segment means -- EXTENSION.
+ * planes: the real planes an omnibus entry reads, in its order
+ *   ND_AMD_STRUCT_DIAG  1..3 intensities
+ *   ND_AMD_STRUCT_C2    [C11, C12re, C12im, C22]
+ *   ND_AMD_STRUCT_C3    [C11, C22, C33, C12re, C12im, C13re, C13im, C23re, C23im]
+ * change (ny, nx, k) bytes as the omnibus entries write them: non-zero at
+ * date t >= 1 opens a new segment at t (nd/_change.pyx:253); byte 0 of a
+ * pixel is ignored.  Per pixel, in double and in date order: the running
+ * sums s_p and the count m of the open segment; at a change
+ * mean_p = s_p / m, d_p = x_p[t] - mean_p and
+ *   direction[t] = 1  d positive definite   (all d_p > 0 / leading minors > 0)
+ *                  2  d negative definite   (all d_p < 0 / minors -, +, -)
+ *                  3  anything else (indefinite, singular, any NaN)
+ * direction is 0 where no change is declared.  means_p[t] = (T)(s_p / m) of
+ * the segment date t lies in, rounded to nearest: the piecewise-constant
+ * series the sequential search implies.  No value is special-cased.
+ * direction (ny, nx, k) int8 and means (nplanes planes with the strides of
+ * `planes`, not overlapping them) are optional, one of them is required.
+ * Every k >= 1, every stride combination (fast: stride_x == 1), no
+ * workspace.  ND_AMD_EINVAL before any HIP call for a bad dtype, structure,
+ * plane count, negative extent, null pointers or no output; ND_AMD_OK for
+ * an empty raster.
+ * ---------------------------------------------------------------------- */
+#define ND_AMD_STRUCT_DIAG 0   /* nplanes 1..3 */
+#define ND_AMD_STRUCT_C2   1   /* nplanes 4    */
+#define ND_AMD_STRUCT_C3   2   /* nplanes 9    */
+
+int nd_amd_change_segments(const void *const planes[], int nplanes, int structure, int dtype,
+                           int64_t ny, int64_t nx, int64_t k,
+                           int64_t stride_y, int64_t stride_x, int64_t stride_t,
+                           const uint8_t *change,      /* (ny, nx, k) contiguous            */
+                           int8_t *direction,          /* (ny, nx, k) contiguous, optional  */
+                           void *const means[],        /* nplanes planes, optional, strides */
+                           void *hip_stream);          /* of `planes`; must not overlap them */
 
 /* ------------------------------------------------------------------------
  * Kernel convolution / boxcar.

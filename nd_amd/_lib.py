@@ -21,8 +21,9 @@ KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose',
                 17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean',
                 21: 'classify_knn', 22: 'classify_linear', 23: 'kmeans_step', 24: 'feature_moments',
-                25: 'gather_rows'}
+                25: 'gather_rows', 26: 'change_segments'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
+STRUCT_DIAG, STRUCT_C2, STRUCT_C3 = 0, 1, 2
 
 # every symbol include/nd_amd.h declares
 SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
@@ -30,7 +31,7 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_omnibus_c2_pixel_major',
            'nd_amd_omnibus_c2_ml_workspace_bytes', 'nd_amd_omnibus_c2_ml',
            'nd_amd_omnibus_c3_workspace_bytes', 'nd_amd_omnibus_c3', 'nd_amd_omnibus_c3_pixel_major',
-           'nd_amd_omnibus_diag_workspace_bytes', 'nd_amd_omnibus_diag',
+           'nd_amd_omnibus_diag_workspace_bytes', 'nd_amd_omnibus_diag', 'nd_amd_change_segments',
            'nd_amd_correlate', 'nd_amd_correlate1d', 'nd_amd_correlate1d_yx', 'nd_amd_nlmeans3d',
            'nd_amd_relayout_planar', 'nd_amd_relayout_planar_complex',
            'nd_amd_relayout_pixel_major', 'nd_amd_split_complex', 'nd_amd_merge_complex',
@@ -101,6 +102,9 @@ def lib():
     L.nd_amd_omnibus_diag.restype = i32
     L.nd_amd_omnibus_diag.argtypes = ([C.POINTER(vp), i32, i32] + [i64] * 6 + [dbl, dbl]
                                       + [vp, vp, vp, vp, C.c_size_t, vp])
+    L.nd_amd_change_segments.restype = i32
+    L.nd_amd_change_segments.argtypes = ([C.POINTER(vp), i32, i32, i32] + [i64] * 6
+                                         + [vp, vp, C.POINTER(vp), vp])
     L.nd_amd_correlate.restype = i32
     L.nd_amd_correlate.argtypes = [vp, vp, i32, C.POINTER(i64), C.POINTER(i64),
                                    C.POINTER(i64), i64, C.POINTER(i64),

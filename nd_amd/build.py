@@ -57,8 +57,11 @@ PER_FILE = {'nlmeans.hip': ['-fno-slp-vectorize'],
 # kmeans_fit.hip: the step kernel keeps a row's features in registers by static index, as the predict kernels do
 # omnibus_diag.hip: pass A and the one-launch form stream the planes; the per-j table is read from the argument
 # segment by wave-uniform index or from LDS, never through a private copy
+# change_segments.hip: a streaming walk over the dates; the sums, a chunk's loads and the carried means are
+# indexed statically
 NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_', 'classify.hip': 'class',
-              'kmeans_fit.hip': '_kernel', 'omnibus_diag.hip': 'omnibus_diag_'}
+              'kmeans_fit.hip': '_kernel', 'omnibus_diag.hip': 'omnibus_diag_',
+              'change_segments.hip': 'change_segments_kernel'}
 # bytes per lane by the kernel's template arguments <K, KMAX, STATS, CHAIN>, keyed (STATS, CHAIN)
 SCRATCH_BUDGET = {(False, False): 0, (False, True): 96, (True, False): 256, (True, True): 384}
 

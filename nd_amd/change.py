@@ -17,7 +17,7 @@ from .algorithm import Algorithm, wrap_algorithm
 from .io import disassemble_complex
 
 __all__ = ['ChangeDetection', 'OmnibusTest', 'omnibus', 'omnibus_statistics', 'change_count',
-           'first_change']
+           'first_change', 'change_segments', 'change_direction', 'segment_means']
 
 _VARS = ['C11', 'C12__re', 'C12__im', 'C22']      # column order of nd/change.py:66
 # full-pol extension (no reference counterpart): plane order of nd_amd_omnibus_c3
@@ -352,3 +352,106 @@ def first_change(change):
         data = np.where(any_, vals.argmax(axis=ax), -1)
     return ns.DataArray(data, dims=[d for d in change.dims if d != 'time'], attrs=change.attrs,
                         name='first_change')
+
+
+def _change_map_checked(ds, names, change):
+    """The checks on the map of change_segments that need no device: a DataArray over y, x, time, bool or
+    uint8, of the raster and series length of the variables `names` of `ds`."""
+    dims = tuple(getattr(change, 'dims', ()))
+    if set(dims) != {'y', 'x', 'time'} or len(dims) != 3:
+        raise ValueError("change must be a DataArray with exactly the dimensions y, x, time, got %s" % (dims,))
+    dtype = _device.np_dtype(change.values)
+    if dtype not in (np.dtype(np.bool_), np.dtype(np.uint8)):
+        raise TypeError("change must be bool or uint8 (the map OmnibusTest returns), got %s" % dtype)
+    da = ds[names[0]]
+    want = tuple(int(da.values.shape[da.dims.index(d)]) for d in ('y', 'x', 'time'))
+    got = tuple(int(change.values.shape[dims.index(d)]) for d in ('y', 'x', 'time'))
+    if got != want:
+        raise ValueError("change has (y, x, time) = %s, the data have %s" % (got, want))
+
+
+def _means_dataset(ns, ds, src_dims, names, planes, host):
+    """The mean planes (time, y, x) as a dataset: every variable in the dims order of the variable it was
+    read from ((y, x, time) through the transpose kernel), on the host when the input was."""
+    out = ns.Dataset(coords=ds.coords, attrs=ds.attrs)
+    for name, plane in zip(names, planes):
+        dims = tuple(src_dims[name])
+        if dims == ('time', 'y', 'x'):
+            data = plane
+        else:
+            perm = [('time', 'y', 'x').index(d) for d in dims]
+            data = torch.empty([plane.shape[i] for i in perm], dtype=plane.dtype, device=plane.device)
+            if not (dims == ('y', 'x', 'time') and kernels.relayout_pixel_major(plane, data)):
+                data.copy_(plane.permute(*perm))
+        out[name] = (dims, _device.to_host(data) if host else data)
+    return out
+
+
+def change_segments(ds, change, pol='dual', channels=None, device=None, direction=True, means=True):
+    """What the change map of OmnibusTest says about the series it was computed from -- an extension, both
+    outputs from one pass of a HIP kernel over the stack and the map (nd_amd/csrc/change_segments.hip).
+
+    ds        the dataset OmnibusTest took (any container and layout it accepts); `pol` and `channels`
+              select the variables exactly as they do there
+    change    the map: a bool or uint8 DataArray over y, x, time (any order), True where a date opens a new
+              segment; date 0 is ignored.  It need not come from a detector.
+    direction the int8 DataArray 'direction' with dims ('y', 'x', 'time'): 0 where no change is declared, else
+              the Loewner order of (the new date - the mean of the segment before it): 1 positive definite
+              (backscatter went up), 2 negative definite (down), 3 neither.  Coords and attrs of `change`.
+    means     a dataset of the variables the structure reads (C11, C12__re, C12__im, C22, ...; the `channels`
+              for pol='diag'; io.assemble_complex restores a complex C12), every date replaced by the mean of
+              its segment: a temporal speckle filter that never averages across a detected change.  Each
+              variable keeps the dims order of its input; the float type is the one the kernel ran in (the
+              inputs' common float type, float64 for integer data).
+    Sums and means are taken in double, in date order.  Host data in, host results out; device data stay on
+    the device.  Returns (direction, means), or the one that was asked for."""
+    if pol not in ('dual', 'full', 'diag'):
+        raise ValueError("pol must be 'dual' (C11, C12, C22: the reference's test), 'full' or 'diag' "
+                         "(intensities only)")
+    if not (direction or means):
+        raise ValueError('change_segments: neither direction nor means is asked for')
+    ns = _adapter.namespace(ds)
+    ds.persist() if hasattr(ds, 'persist') else None
+    if pol == 'diag':
+        names = _diag_channels(ds, channels)
+        wanted, present = set(names), names
+    else:
+        names = _VARS3 if pol == 'full' else _VARS
+        wanted = (set(_VARS3) | _COMPLEX) if pol == 'full' else (set(_VARS) | {'C12'})
+        present = [v for v in list(ds.data_vars) if v in wanted]
+        missing = [v for v in names if v not in present and v.split('__')[0] not in present]
+        if missing:
+            raise KeyError("change_segments needs the variables C11, C12 (or C12__re/C12__im) and C22 (plus C33, "
+                           "C13, C23 for full-pol data); %s are missing" % missing)
+    _change_map_checked(ds, present, change)
+    host = not any(_device.is_tensor(ds[v].values) for v in present)
+    dev = _device.device_of(*[ds[v].values for v in present], device=device)
+    with torch.cuda.device(dev):
+        ds_m = _on_device(ds, dev, wanted) if host else ds
+        if pol != 'diag':
+            ds_m = disassemble_complex(ds_m)
+        src_dims = {v: ds_m[v].dims for v in names}
+        stack = _planes_in_place(ds_m, dev, names)
+        if stack is None:
+            stack = _covariance_planes(ds_m, dev, names)
+        cmap = _device.to_device(change.transpose('y', 'x', 'time').values, dev).contiguous()
+        res = kernels.change_segments(list(stack), cmap, {'dual': 'c2', 'full': 'c3', 'diag': 'diag'}[pol],
+                                      dims=('time', 'y', 'x'), direction=direction, means=means)
+        out = []
+        if direction:
+            d = res[0] if means else res
+            out.append(ns.DataArray(_device.to_host(d) if host else d, dims=['y', 'x', 'time'],
+                                    coords=change.coords, attrs=change.attrs, name='direction'))
+        if means:
+            out.append(_means_dataset(ns, ds, src_dims, names, res[1] if direction else res, host))
+    return tuple(out) if len(out) == 2 else out[0]
+
+
+def change_direction(ds, change, pol='dual', channels=None, device=None):
+    """change_segments(...) for the direction alone."""
+    return change_segments(ds, change, pol=pol, channels=channels, device=device, direction=True, means=False)
+
+
+def segment_means(ds, change, pol='dual', channels=None, device=None):
+    """change_segments(...) for the segment means alone."""
+    return change_segments(ds, change, pol=pol, channels=channels, device=device, direction=False, means=True)

@@ -269,6 +269,73 @@ def change_detection_diag(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=Fal
     return change
 
 
+_STRUCTURES = {'diag': (_lib.STRUCT_DIAG, (1, 2, 3)), 'c2': (_lib.STRUCT_C2, (4,)), 'c3': (_lib.STRUCT_C3, (9,))}
+
+
+def change_segments(planes, change, structure, dims=('time', 'y', 'x'), direction=True, means=True):
+    """Direction of every declared change and the segment means -- an extension (include/nd_amd.h has the
+    definition).  planes: the real CUDA tensors an omnibus entry reads, in its order -- structure 'diag': one
+    to three intensities, 'c2': [C11, C12re, C12im, C22], 'c3': the nine planes of change_detection_c3 -- of
+    identical shape/strides/dtype, axes named by `dims`.  change: the contiguous uint8 or bool CUDA tensor
+    (y, x, time) an omnibus entry returns.
+    Returns direction, int8 (y, x, time): 0 no change declared, 1 / 2 / 3 the difference between the new date
+    and the mean of the segment before it is positive definite / negative definite / neither; and / or means:
+    a list of planes shaped and strided like `planes`, every date replaced by the mean of its segment."""
+    planes = list(planes)
+    if structure not in _STRUCTURES:
+        raise ValueError("structure must be 'diag', 'c2' or 'c3', got %r" % (structure,))
+    code, counts = _STRUCTURES[structure]
+    if len(planes) not in counts:
+        raise ValueError("structure '%s' takes %s planes, got %d"
+                         % (structure, {'diag': 'one to three', 'c2': 'four', 'c3': 'nine'}[structure], len(planes)))
+    if not (direction or means):
+        raise ValueError('change_segments: neither direction nor means is asked for')
+    p0 = planes[0]
+    for i, t in enumerate(planes):
+        _require_cuda(t, 'planes[%d]' % i)
+        # strides of length-1 axes address nothing: views of one buffer may carry different ones
+        same_strides = t.dim() == 3 and all(a == b for a, b, n_ in zip(t.stride(), p0.stride(), t.shape)
+                                            if n_ > 1)
+        if (t.dim() != 3 or t.shape != p0.shape or not same_strides
+                or t.dtype != p0.dtype or t.device != p0.device):
+            raise ValueError('the planes must be 3-D and share shape, strides, dtype and device')
+    if any(st_ == 0 and n_ > 1 for st_, n_ in zip(p0.stride(), p0.shape)):
+        raise ValueError('expanded planes (stride 0) are not served: the means would overlap')
+    dims = tuple(dims)
+    if sorted(dims) != ['time', 'x', 'y']:
+        raise ValueError("dims must be a permutation of ('time', 'y', 'x')")
+    ay, ax, at = dims.index('y'), dims.index('x'), dims.index('time')
+    ny, nx, k = p0.shape[ay], p0.shape[ax], p0.shape[at]
+    if not isinstance(change, torch.Tensor):
+        raise TypeError('change must be a torch.Tensor, got %r' % type(change))
+    if change.dtype not in (torch.uint8, torch.bool):
+        raise TypeError('change must be uint8 or bool, got %s' % change.dtype)
+    if tuple(change.shape) != (ny, nx, k):
+        raise ValueError('change has shape %s, the planes are (y, x, time) = %s'
+                         % (tuple(change.shape), (ny, nx, k)))
+    if change.device != p0.device:
+        raise ValueError('change lives on %s, the planes on %s' % (change.device, p0.device))
+    if not change.is_contiguous():
+        raise ValueError('change must be contiguous (y, x, time)')
+    dev = p0.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        out_d = torch.empty((ny, nx, k), dtype=torch.int8, device=dev) if direction else None
+        # one allocation per plane with the planes' own strides (empty_strided: nothing is initialised)
+        out_m = [torch.empty_strided(tuple(p0.shape), p0.stride(), dtype=p0.dtype, device=dev)
+                 for _ in planes] if means else None
+        if ny * nx * k > 0:
+            ptrs = (C.c_void_p * len(planes))(*[t.data_ptr() for t in planes])
+            mptrs = (C.c_void_p * len(planes))(*[t.data_ptr() for t in out_m]) if means else None
+            cbytes = change.view(torch.uint8) if change.dtype == torch.bool else change
+            _lib.check(L.nd_amd_change_segments(
+                ptrs, len(planes), code, _DT[p0.dtype], ny, nx, k, p0.stride(ay), p0.stride(ax), p0.stride(at),
+                _ptr(cbytes), _ptr(out_d), mptrs, _stream_ptr(dev)))
+    if direction and means:
+        return out_d, out_m
+    return out_d if direction else out_m
+
+
 def change_detection_c3_pixel_major(planes, alpha, n=1, stats=False):
     """change_detection_c3 for nine device variables in the reference's own layout, (y, x, time) with time
     fastest -- [C11, C22, C33, C12re, C12im, C13re, C13im, C23re, C23im], the off-diagonal pairs either real

@@ -1,0 +1,244 @@
+"""change_segments on the GPU against the numpy restatement (tests/change_segments_ref.py), computed inside the
+tests: direction equal everywhere, means bit for bit with equal NaN positions.  No tolerance, no excluded
+pixel -- the definition is exact and so is the comparison."""
+import numpy as np
+import pytest
+
+from tests import change_segments_cases as cases
+from tests import change_segments_ref as R
+
+pytestmark = pytest.mark.gpu
+
+CORE = cases.core_cases()
+
+
+def _bits(a):
+    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+def assert_bit_equal(got, want, what=''):
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    nan = np.isnan(want)
+    np.testing.assert_array_equal(np.isnan(got), nan, err_msg=what)
+    np.testing.assert_array_equal(_bits(np.where(nan, 0, got)), _bits(np.where(nan, 0, want)), err_msg=what)
+
+
+def _run(device, planes, change, structure, direction=True, means=True, dims=('time', 'y', 'x')):
+    import torch
+    from nd_amd import kernels
+    t = [p if torch.is_tensor(p) else torch.from_numpy(p).to(device) for p in planes]
+    c = change if torch.is_tensor(change) else torch.from_numpy(change).to(device)
+    res = kernels.change_segments(t, c, structure, dims=dims, direction=direction, means=means)
+    d, m = res if (direction and means) else ((res, None) if direction else (None, res))
+    if d is not None:
+        assert d.dtype == torch.int8 and tuple(d.shape) == tuple(c.shape)
+        d = d.cpu().numpy()
+    if m is not None:
+        assert all(a.shape == b.shape and a.stride() == b.stride() for a, b in zip(m, t))
+        m = [a.cpu().numpy() for a in m]
+    return d, m
+
+
+def _check(device, planes, change, structure, **kw):
+    """All three ways to ask -- both outputs, direction only, means only -- against the restatement."""
+    want_d, want_m = R.change_segments(planes, change, structure)
+    for direction, means in ((True, True), (True, False), (False, True)):
+        d, m = _run(device, planes, change, structure, direction, means, **kw)
+        if direction:
+            np.testing.assert_array_equal(d, want_d)
+        if means:
+            for p, (a, b) in enumerate(zip(m, want_m)):
+                assert_bit_equal(a, b, 'plane %d' % p)
+    return want_d, want_m
+
+
+@pytest.mark.parametrize('case', CORE, ids=cases.case_id)
+def test_core(device, case):
+    planes, change = cases.make(*case)
+    _check(device, planes, change, case[0])
+
+
+@pytest.mark.parametrize('structure, nplanes, dtype', [('c2', 4, np.float32), ('diag', 3, np.float64),
+                                                       ('c3', 9, np.float32)])
+def test_special_maps(device, structure, nplanes, dtype):
+    planes, _ = cases.make(structure, nplanes, dtype, 10, 5, 130, 31)
+    none = np.zeros((5, 130, 10), np.uint8)
+    d, m = _check(device, planes, none, structure)
+    assert (d == 0).all()
+    for p, mp in zip(planes, m):
+        total = np.zeros(p.shape[1:])
+        for t in range(10):
+            total = total + p[t].astype(np.float64)
+        whole = (total / 10.0).astype(dtype)
+        assert_bit_equal(mp, np.broadcast_to(whole, mp.shape).copy())
+    d_none = _run(device, planes, none, structure)
+    # every date its own segment: the means are the input, every date but the first carries a code
+    every = np.full((5, 130, 10), 255, np.uint8)
+    d, m = _check(device, planes, every, structure)
+    assert (d[..., 0] == 0).all() and (d[..., 1:] != 0).all()
+    for p, mp in zip(planes, m):
+        assert_bit_equal(mp, p)
+    # a flag at date 0 opens nothing
+    first = np.zeros((5, 130, 10), np.uint8)
+    first[..., 0] = 1
+    d_first = _run(device, planes, first, structure)
+    np.testing.assert_array_equal(d_first[0], d_none[0])
+    for a, b in zip(d_first[1], d_none[1]):
+        assert_bit_equal(a, b)
+
+
+@pytest.mark.parametrize('k', [200, 1000])
+@pytest.mark.parametrize('structure, nplanes, dtype', [('c2', 4, np.float32), ('diag', 2, np.float64)])
+def test_long_series(device, structure, nplanes, dtype, k):
+    planes, change = cases.make(structure, nplanes, dtype, k, 2, 130, 500 + k)
+    d, _ = _check(device, planes, change, structure)
+    assert (d[..., 64:] > 0).any() and all((d == c).any() for c in (1, 2, 3))
+
+
+@pytest.mark.parametrize('structure, nplanes, dtype', [('c2', 4, np.float32), ('diag', 3, np.float64)])
+def test_strides_and_alignment(device, structure, nplanes, dtype):
+    """Time-fastest tensors as they lie, a view with a row pitch, base pointers one element off the 16-byte grid
+    and separate allocations all give the contiguous result."""
+    import torch
+    k, ny, nx = 10, 5, 130
+    planes, change = cases.make(structure, nplanes, dtype, k, ny, nx, 77)
+    want_d, want_m = _check(device, planes, change, structure)           # planes of separate allocations
+
+    def compare(t, dims, perm):
+        c = torch.from_numpy(change).to(device)
+        for direction, means in ((True, True), (False, True), (True, False)):
+            d, m = _run(device, t, c, structure, direction, means, dims=dims)
+            if direction:
+                np.testing.assert_array_equal(d, want_d)
+            if means:
+                for a, b in zip(m, want_m):
+                    assert_bit_equal(np.ascontiguousarray(a.transpose(perm)), b)
+
+    one = torch.from_numpy(np.stack(planes)).to(device)                  # one allocation
+    compare(list(one), ('time', 'y', 'x'), (0, 1, 2))
+    yxt = one.permute(0, 2, 3, 1).contiguous()                           # (y, x, time), time fastest
+    compare(list(yxt), ('y', 'x', 'time'), (2, 0, 1))
+    wide = torch.zeros((nplanes, k, ny, nx + 10), dtype=one.dtype, device=device)
+    wide[..., 3:133] = one
+    view = [w[:, :, 3:133] for w in wide]
+    assert not view[0].is_contiguous()
+    compare(view, ('time', 'y', 'x'), (0, 1, 2))
+    flat = torch.zeros(nplanes * (k * ny * nx + 4) + 1, dtype=one.dtype, device=device)
+    off = []
+    for p in range(nplanes):
+        o = flat[p * (k * ny * nx + 4) + 1:][:k * ny * nx].view(k, ny, nx)
+        o.copy_(one[p])
+        assert o.data_ptr() % 16 == o.element_size()
+        off.append(o)
+    compare(off, ('time', 'y', 'x'), (0, 1, 2))
+
+
+@pytest.mark.parametrize('structure, nplanes, dtype', [('c2', 4, np.float32), ('c3', 9, np.float64)])
+def test_degenerate_values(device, structure, nplanes, dtype):
+    planes, change = cases.make(structure, nplanes, dtype, 10, 5, 130, 11)
+    planes = cases.degenerate(planes, 12)
+    d, m = _check(device, planes, change, structure)
+    assert np.isnan(m[0]).any() and np.isinf(m[0]).any() and (d == 3).any()
+
+
+def _dataset(planes, dims, device=None, split=False, names=('C11', 'C12', 'C22')):
+    import torch
+    from nd_amd import xr_lite
+    ds = xr_lite.Dataset(attrs={'sensor': 'test'})
+    perm = [('time', 'y', 'x').index(d) for d in dims]
+    put = lambda a: (dims, np.ascontiguousarray(a.transpose(perm)) if device is None      # noqa: E731
+                     else torch.from_numpy(np.ascontiguousarray(a.transpose(perm))).to(device))
+    ds['C11'] = put(planes[0])
+    if split:
+        ds['C12__re'], ds['C12__im'] = put(planes[1]), put(planes[2])
+    else:
+        ds['C12'] = put(planes[1] + 1j * planes[2])
+    ds['C22'] = put(planes[3])
+    return ds
+
+
+def test_public_interface_host_pixel_major(device):
+    from nd_amd import xr_lite
+    from nd_amd.change import change_segments
+    from nd_amd.io import assemble_complex
+    planes, change = cases.make('c2', 4, np.float32, 10, 5, 130, 21)
+    want_d, want_m = R.change_segments(planes, change, 'c2')
+    ds = _dataset(planes, ('y', 'x', 'time'))
+    cmap = xr_lite.DataArray(change.astype(bool), dims=('y', 'x', 'time'), attrs={'a': 1}, name='change')
+    direction, means = change_segments(ds, cmap)
+    assert isinstance(direction.values, np.ndarray) and direction.values.dtype == np.int8
+    assert direction.dims == ('y', 'x', 'time') and direction.name == 'direction' and direction.attrs['a'] == 1
+    np.testing.assert_array_equal(direction.values, want_d)
+    assert list(means.data_vars) == ['C11', 'C12__re', 'C12__im', 'C22']
+    for name, w in zip(means.data_vars, want_m):
+        v = means[name]
+        assert v.dims == ('y', 'x', 'time') and isinstance(v.values, np.ndarray) and v.values.dtype == np.float32
+        assert_bit_equal(np.ascontiguousarray(v.values.transpose(2, 0, 1)), w)
+    whole = assemble_complex(means)
+    assert whole['C12'].values.dtype == np.complex64 and 'C12__re' not in whole.data_vars
+
+
+def test_public_interface_device_time_first(device):
+    import torch
+    from nd_amd import xr_lite
+    from nd_amd.change import change_direction, segment_means
+    planes, change = cases.make('c2', 4, np.float64, 10, 5, 130, 22)
+    want_d, want_m = R.change_segments(planes, change, 'c2')
+    ds = _dataset(planes, ('time', 'y', 'x'), device=device, split=True)
+    cmap = xr_lite.DataArray(torch.from_numpy(np.ascontiguousarray(change.transpose(2, 0, 1))).to(device),
+                             dims=('time', 'y', 'x'))                          # uint8, another dims order
+    direction = change_direction(ds, cmap)
+    assert torch.is_tensor(direction.values) and direction.values.is_cuda and direction.values.dtype == torch.int8
+    assert direction.dims == ('y', 'x', 'time')
+    np.testing.assert_array_equal(direction.values.cpu().numpy(), want_d)
+    means = segment_means(ds, cmap)
+    for name, w in zip(('C11', 'C12__re', 'C12__im', 'C22'), want_m):
+        v = means[name]
+        assert v.dims == ('time', 'y', 'x') and v.values.is_cuda and v.values.dtype == torch.float64
+        assert_bit_equal(v.values.cpu().numpy(), w)
+
+
+def test_public_interface_intensities(device):
+    from nd_amd import xr_lite
+    from nd_amd.change import change_segments
+    planes, change = cases.make('diag', 2, np.float32, 10, 5, 130, 23)
+    want_d, want_m = R.change_segments(planes, change, 'diag')
+    ds = xr_lite.Dataset()
+    ds['VH'] = (('y', 'x', 'time'), np.ascontiguousarray(planes[1].transpose(1, 2, 0)))
+    ds['VV'] = (('y', 'x', 'time'), np.ascontiguousarray(planes[0].transpose(1, 2, 0)))
+    ds['C12'] = (('y', 'x', 'time'), np.ones((5, 130, 10), np.complex64))                # ignored
+    cmap = xr_lite.DataArray(change, dims=('y', 'x', 'time'))
+    direction, means = change_segments(ds, cmap, pol='diag', channels=['VV', 'VH'])
+    np.testing.assert_array_equal(direction.values, want_d)
+    assert list(means.data_vars) == ['VV', 'VH']
+    for name, w in zip(('VV', 'VH'), want_m):
+        assert_bit_equal(np.ascontiguousarray(means[name].values.transpose(2, 0, 1)), w)
+
+
+def test_omnibus_map_of_the_step_stack(device):
+    """The detector's own map: one change per pixel at date 5, the power going up -- code 1 there, 0 elsewhere,
+    and two constant segments in the means."""
+    from nd_amd.change import OmnibusTest, change_segments
+    planes = cases.step_stack('up', np.float64)
+    ds = _dataset(planes, ('y', 'x', 'time'))
+    change = OmnibusTest(n=9, alpha=0.9).apply(ds)
+    assert change.values[..., 5].all() and (change.values.sum(axis=-1) == 1).all()
+    direction, means = change_segments(ds, change)
+    assert (direction.values[..., 5] == 1).all() and (np.delete(direction.values, 5, axis=-1) == 0).all()
+    for name in ('C11', 'C12__re', 'C12__im', 'C22'):
+        v = means[name].values
+        assert (v[..., :5] == v[..., :1]).all() and (v[..., 5:] == v[..., 5:6]).all()
+    assert (means['C11'].values[..., 5] > 3 * means['C11'].values[..., 0]).all()
+
+
+def test_kernel_name(device):
+    """One call is one launch, timed under the new kernel's name."""
+    from nd_amd import _lib
+    planes, change = cases.make('c2', 4, np.float32, 10, 5, 130, 5)
+    _lib.timing_enable(16)
+    try:
+        _run(device, planes, change, 'c2')
+        names = [n for n, _ in _lib.timing_collect()]
+    finally:
+        _lib.timing_enable(0)
+    assert names == ['change_segments']
