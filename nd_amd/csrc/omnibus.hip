@@ -2951,37 +2951,6 @@ omnibus_c2_search_chain_kernel(const OmniSearchArgs<T> s, const StreamScreen<32>
 // =========================================================================================
 // host side
 // =========================================================================================
-std::vector<OmniTabEntry> get_table_impl(int k, uint32_t n_looks, double alpha, int dtype, int pol)
-{
-    static std::mutex mu;
-    static std::vector<TabCacheEntry> cache;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (const auto &c : cache)
-            if (c.key.k == k && c.key.dtype == dtype && c.key.pol == pol && c.key.n == n_looks &&
-                memcmp(&c.key.alpha, &alpha, sizeof(double)) == 0)
-                return c.tab;
-    }
-    std::vector<OmniTabEntry> tab((size_t)k + 1);
-    memset(tab.data(), 0, tab.size() * sizeof(OmniTabEntry));
-    for (int j = 1; j <= k; ++j)
-        tab[j] = dtype == ND_AMD_F32 ? make_entry<float>(j, n_looks, alpha, pol)
-                                     : make_entry<double>(j, n_looks, alpha, pol);
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (cache.size() >= 32) cache.erase(cache.begin());
-        TabCacheEntry c;
-        c.key.k = k;
-        c.key.dtype = dtype;
-        c.key.pol = pol;
-        c.key.n = n_looks;
-        c.key.alpha = alpha;
-        c.tab = tab;
-        cache.push_back(c);
-    }
-    return tab;
-}
-
 // workspace: [counters][per-j table][pixel list: npix x u32][dense-wave list][dump: cap x k x 4 x T]
 // `min_total` is what the call needs; everything beyond it is used as dump capacity.  The
 // recommended size holds the series of 1/8 of the pixels (a listed pixel beyond the capacity is
@@ -3168,34 +3137,17 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
     // ptr_v[((y * nx + x) * k + t) * pm_ids[v]]; sy / sx / st then describe the unit-stride case
     const int64_t npix = ny * nx;
     const OmniWorkspace w = omni_layout(npix, ny, k, sizeof(T), mlp ? mlp->seg : 0);
-    if (workspace == nullptr || workspace_bytes < w.min_total) {
-        set_error("nd_amd_omnibus_c2: workspace of at least %zu bytes needed, %zu given",
-                  w.min_total, workspace_bytes);
-        return ND_AMD_EWORKSPACE;
-    }
-    if (((uintptr_t)workspace & 255) != 0) {
-        set_error("nd_amd_omnibus_c2: workspace must be 256-byte aligned");
-        return ND_AMD_EINVAL;
-    }
+    if (const int rc = check_workspace("nd_amd_omnibus_c2", workspace, workspace_bytes, w.min_total, true)) return rc;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     uint32_t *flag_count = reinterpret_cast<uint32_t *>(ws + w.off_count);
     OmniTabEntry *tab_dev = reinterpret_cast<OmniTabEntry *>(ws + w.off_tab);
     uint32_t *flag_idx = reinterpret_cast<uint32_t *>(ws + w.off_idx);
 
     // per-j constants (host, double, same expression order as nd/_change.c:2926-2975)
-    const std::vector<OmniTabEntry> htab = get_table<T>((int)k, n_looks, alpha, 2);
+    const std::vector<OmniTabEntry> htab = get_table((int)k, n_looks, alpha, dtype_of<T>(), OmniFamily{2, 1});
     OmniTab tab;
-    memset(&tab, 0, sizeof(tab));
-    const bool tab_in_args = (k <= kTabArgs);
-    if (tab_in_args) {
-        memcpy(tab.e, htab.data(), htab.size() * sizeof(OmniTabEntry));
-    } else {
-        // large k: the table goes through a pageable host copy (synchronises the stream once)
-        hipError_t e = hipMemcpyAsync(tab_dev, htab.data(), htab.size() * sizeof(OmniTabEntry),
-                                      hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        ND_HIP_CHECK(e);
-    }
+    bool tab_in_args;
+    ND_HIP_CHECK(stage_table(htab, k, &tab, tab_dev, stream, &tab_in_args));
 
     ND_HIP_CHECK(hipMemsetAsync(flag_count, 0, kCounterBytes, stream));
 

@@ -1817,24 +1817,17 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
 {
     const int64_t npix = ny * nx;
     const C3Workspace w = c3_layout(npix, ny, k);
-    if (workspace == nullptr || workspace_bytes < w.total) {
-        set_error("nd_amd_omnibus_c3: workspace of %zu bytes needed, %zu given", w.total,
-                  workspace_bytes);
-        return ND_AMD_EWORKSPACE;
-    }
-    if (((uintptr_t)workspace & 255) != 0) {
-        set_error("nd_amd_omnibus_c3: workspace must be 256-byte aligned");
-        return ND_AMD_EINVAL;
-    }
+    if (const int rc = check_workspace("nd_amd_omnibus_c3", workspace, workspace_bytes, w.total)) return rc;
     if (k > kTabArgs) {
         set_error("nd_amd_omnibus_c3: k = %lld exceeds the supported %d dates", (long long)k, kTabArgs);
         return ND_AMD_EUNSUPPORTED;
     }
     unsigned char *ws = static_cast<unsigned char *>(workspace);
-    const std::vector<OmniTabEntry> htab = get_table<T>((int)k, n_looks, alpha, 3);
+    const std::vector<OmniTabEntry> htab = get_table((int)k, n_looks, alpha, dtype_of<T>(), OmniFamily{3, 1});
     OmniTab tab;
-    memset(&tab, 0, sizeof(tab));
-    memcpy(tab.e, htab.data(), htab.size() * sizeof(OmniTabEntry));
+    bool tab_in_args;      // always: k <= kTabArgs
+    ND_HIP_CHECK(stage_table(htab, k, &tab, reinterpret_cast<OmniTabEntry *>(ws + w.off_tab), stream,
+                             &tab_in_args));
 
     C3Args<T> g;
     for (int c = 0; c < 9; ++c) {

@@ -26,8 +26,6 @@
 //       the series from the planes -- any k.
 // Every form evaluates a test the same way (diag_fires): the f32-log2 screen against zlo_a / zhi_a, and in
 // between the exact statistic and, inside [zlo, zhi], the chi-square pair.
-#include <utility>
-
 #include "omnibus_common.hpp"
 
 namespace nd_amd {
@@ -159,7 +157,7 @@ struct DiagTabLds {
 };
 
 // Does the test over the jj dates folded into A fire?  The screen first: z_approx is within aerr of the exact
-// double statistic (make_entry_diag), NaN or infinite exactly when that is; only between zlo_a and zhi_a the
+// double statistic (make_entry, omnibus_tables.hip), NaN or infinite exactly when that is; only between zlo_a and zhi_a the
 // exact statistic is formed and decided by zlo / zhi or the chi-square pair.
 template <typename T, int Q, typename Tab>
 __device__ __forceinline__ bool diag_fires(const DiagAccum<T, Q> &A, const int jj, const double nlooks,
@@ -423,135 +421,6 @@ __global__ void __launch_bounds__(kDgThreads) omnibus_diag_fused_kernel(const Di
 // =========================================================================================
 // host side
 // =========================================================================================
-// host twin of diag_P's chi-square pair (host_chisq_pair finished at f = 1)
-static inline void host_chisq_pair_diag(double z, int a2, double lgam_a1, double *P1, double *P2)
-{
-    host_chisq_pair(z, a2, lgam_a1, P1, P2);
-    if (a2 == 1 && z >= 3.0 && z < INFINITY) {
-        const double x = 0.5 * z;
-        const double ta = exp((0.5 * log(x) - x) - lgam_a1);
-        const double qa = erfc(sqrt(x));
-        *P1 = 1.0 - qa;
-        *P2 = 1.0 - (qa + ta + ta * (x / 1.5));
-    }
-}
-
-// Decision bounds with omega2 < 0 (omni_bounds gives up outside 0 <= omega2 <= 1, where P is a mixture of two
-// CDFs).  With w = -omega2 > 0, x = z / 2, a = f / 2 and t_a = x^a e^-x / Gamma(a + 1):
-//   P(a, x) - P(a + 2, x) = t_a + t_{a+1},  so  P = P(a, x) + w (t_a + t_{a+1});
-//   d/dx P(a, x) = t_{a-1},  d/dx t_a = t_{a-1} - t_a,  t_{a+1} = t_{a-1} x^2 / (a (a + 1)),  hence
-//   dP/dx = t_{a-1} (1 + w) - w t_{a+1} = t_{a-1} (1 + w - w x^2 / (a (a + 1))).
-// P rises from 0 up to x* = sqrt(a (a + 1) (1 + 1/w)) and falls beyond it towards its limit 1, so P >= 1 on
-// [x*, inf).  For a target tau < 1 the crossing P = tau is therefore unique, lies below x*, and P < tau before
-// it, P > tau behind it: the bisection of omni_bounds holds with the bracket [0, 2 x*].  That needs
-// alpha + margin < 1; otherwise (and for j < 2, where rho is NaN) every test is evaluated exactly -- with
-// omega2 < 0, P passes 1, so "P <= 1 < alpha: nothing fires" does not hold here either.
-// margin: the kernel's roundings of P1, P2, their difference and P to T, and the series' ~1e-13 (omni_bounds).
-template <typename T>
-static void diag_bounds(int j, int a2, double omega2, double lgam, double alpha, double *zlo, double *zhi)
-{
-    *zlo = -INFINITY;
-    *zhi = INFINITY;
-    if (j < 2 || a2 < 1) return;
-    if (!(omega2 < 0.0) || !(omega2 > -INFINITY) || !(alpha == alpha)) return;
-    const double ulp = sizeof(T) == 4 ? 5.9604644775390625e-08 : 1.1102230246251565e-16;
-    const double w = -omega2;
-    const double a = 0.5 * (double)a2;
-    const double margin = 16.0 * ulp * (1.0 + 2.0 * w) + 1e-11 +
-                          8.0 * a * (1.0 + log(a + 2.0)) * 1.1102230246251565e-16;
-    const double thi = alpha + margin, tlo = alpha - margin;
-    if (!(thi < 1.0 - 1e-9)) return;
-    const double zcap = 4.0 * sqrt(a * (a + 1.0) * (1.0 + 1.0 / w));      // z = 2 x at x = 2 x*
-    if (!(zcap > 0.0) || !(zcap < INFINITY)) return;
-    auto Pz = [&](double z) {
-        double p1, p2;
-        host_chisq_pair_diag(z, a2, lgam, &p1, &p2);
-        return p1 + omega2 * (p2 - p1);
-    };
-    auto quantile = [&](double target, double *lo_out, double *hi_out) -> bool {
-        double lo = 0.0, hi = zcap;
-        if (!(Pz(hi) >= target)) return false;
-        for (int it = 0; it < 200; ++it) {
-            const double mid = 0.5 * (lo + hi);
-            if (Pz(mid) < target)
-                lo = mid;
-            else
-                hi = mid;
-            if (hi - lo <= 1e-15 * hi) break;
-        }
-        *lo_out = lo;
-        *hi_out = hi;
-        return true;
-    };
-    double lo, hi;
-    if (tlo > 0.0 && quantile(tlo, &lo, &hi)) *zlo = lo * (1.0 - 1e-9);
-    if (thi > 0.0 && quantile(thi, &lo, &hi)) *zhi = hi * (1.0 + 1e-9);
-}
-
-// make_entry (omnibus_common.hpp) for q independent 1 x 1 blocks and a real number of looks
-template <typename T>
-static OmniTabEntry make_entry_diag(int j, int q, double n, double alpha)
-{
-    OmniTabEntry e;
-    const double k = (double)j;
-    const double rho = host_rho(1.0, k, n);                   // does not depend on q
-    const T rho_t = (T)rho;
-    e.m2rho = -2.0 * (double)rho_t;
-    const T pk = (T)q * (T)j;
-    e.pklogk = (double)pk * log(k);
-    e.omega2 = (double)q * host_omega2(1.0, k, n, rho);       // -(q (j - 1) / 4) (1 - 1/rho)^2
-    const int a2 = q * (j - 1);                               // f
-    e.lgam = lgamma(0.5 * (double)a2 + 1.0);
-    diag_bounds<T>(j, a2, e.omega2, e.lgam, alpha, &e.zlo, &e.zhi);
-    // bounds for the f32-log2 screen: |z_approx - z| <= |m2rho| n (j + 1) 4.2e-8 before z is rounded to T
-    // (two hardware log2 of <= 6e-8 absolute, times ln 2, the second one j times); aerr is twenty times that,
-    // and the rounding of z to T (which zlo / zhi refer to) is added
-    const double eps = sizeof(T) == 4 ? 1.1920928955078125e-07 : 2.220446049250313e-16;
-    const double aerr = 1e-6 * fabs(e.m2rho) * n * (k + 1.0);
-    e.zlo_a = (e.zlo > -INFINITY && e.zlo < INFINITY) ? e.zlo - (aerr + (2.0 * eps + 1e-9) * fabs(e.zlo)) : e.zlo;
-    e.zhi_a = (e.zhi < INFINITY) ? e.zhi + (aerr + (2.0 * eps + 1e-9) * fabs(e.zhi)) : INFINITY;
-    if (!(aerr == aerr) || !(aerr < INFINITY)) {              // rho is NaN for j = 1: exact path only
-        e.zlo = e.zlo_a = -INFINITY;
-        e.zhi = e.zhi_a = INFINITY;
-    }
-    return e;
-}
-
-// the table cache of omnibus_common.hpp (TabCacheEntry) with this family's key: q and a real n
-struct DiagTabKey {
-    int k, dtype, q;
-    double n, alpha;
-};
-static std::vector<OmniTabEntry> get_table_diag(int k, double n, double alpha, int dtype, int q)
-{
-    static std::mutex mu;
-    static std::vector<std::pair<DiagTabKey, std::vector<OmniTabEntry>>> cache;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (const auto &c : cache)
-            if (c.first.k == k && c.first.dtype == dtype && c.first.q == q &&
-                memcmp(&c.first.n, &n, sizeof(double)) == 0 && memcmp(&c.first.alpha, &alpha, sizeof(double)) == 0)
-                return c.second;
-    }
-    std::vector<OmniTabEntry> tab((size_t)k + 1);
-    memset(tab.data(), 0, tab.size() * sizeof(OmniTabEntry));
-    for (int j = 1; j <= k; ++j)
-        tab[j] = dtype == ND_AMD_F32 ? make_entry_diag<float>(j, q, n, alpha) : make_entry_diag<double>(j, q, n, alpha);
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (cache.size() >= 32) cache.erase(cache.begin());
-        DiagTabKey key;
-        memset(&key, 0, sizeof(key));
-        key.k = k;
-        key.dtype = dtype;
-        key.q = q;
-        key.n = n;
-        key.alpha = alpha;
-        cache.emplace_back(key, tab);
-    }
-    return tab;
-}
-
 // workspace: [counters][per-j table][pixel lists: kDgShards x seg x u32]
 struct DiagWorkspace {
     size_t off_count, off_tab, off_idx, total;
@@ -577,30 +446,13 @@ static int omnibus_diag_impl(const void *const planes[], int64_t ny, int64_t nx,
 {
     const int64_t npix = ny * nx;
     const DiagWorkspace w = diag_layout(npix, ny, k);
-    if (workspace == nullptr || workspace_bytes < w.total) {
-        set_error("nd_amd_omnibus_diag: workspace of %zu bytes needed, %zu given", w.total, workspace_bytes);
-        return ND_AMD_EWORKSPACE;
-    }
-    if (((uintptr_t)workspace & 255) != 0) {
-        set_error("nd_amd_omnibus_diag: workspace must be 256-byte aligned");
-        return ND_AMD_EINVAL;
-    }
+    if (const int rc = check_workspace("nd_amd_omnibus_diag", workspace, workspace_bytes, w.total)) return rc;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
-    const std::vector<OmniTabEntry> htab =
-        get_table_diag((int)k, n_looks, alpha, sizeof(T) == 4 ? ND_AMD_F32 : ND_AMD_F64, Q);
+    const std::vector<OmniTabEntry> htab = get_table((int)k, n_looks, alpha, dtype_of<T>(), OmniFamily{1, Q});
     OmniTab tab;
-    memset(&tab, 0, sizeof(tab));
     OmniTabEntry *tab_dev = reinterpret_cast<OmniTabEntry *>(ws + w.off_tab);
-    const bool tab_in_args = k <= kTabArgs;
-    if (tab_in_args) {
-        memcpy(tab.e, htab.data(), htab.size() * sizeof(OmniTabEntry));
-    } else {
-        // long series: the table goes through a pageable host copy (synchronises the stream once)
-        hipError_t e = hipMemcpyAsync(tab_dev, htab.data(), htab.size() * sizeof(OmniTabEntry), hipMemcpyHostToDevice,
-                                      stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        ND_HIP_CHECK(e);
-    }
+    bool tab_in_args;
+    ND_HIP_CHECK(stage_table(htab, k, &tab, tab_dev, stream, &tab_in_args));
 
     DiagArgs<T> g;
     for (int c = 0; c < 3; ++c) g.pl[c] = static_cast<const T *>(planes[c < Q ? c : 0]);

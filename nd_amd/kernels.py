@@ -39,6 +39,52 @@ def _ptr(t):
 
 
 # ---------------------------------------------------------------------------
+# the checks and outputs the omnibus wrappers share
+# ---------------------------------------------------------------------------
+def _plane_stack(planes, what, names=None):
+    """CUDA float tensors, 3-D, of one shape, dtype and device and with the same strides over the axes longer
+    than 1 (strides of length-1 axes address nothing: views of one buffer may carry different ones);
+    ValueError(what) otherwise.  Returns planes[0]."""
+    p0 = planes[0]
+    for i, t in enumerate(planes):
+        _require_cuda(t, names[i] if names else 'planes[%d]' % i)
+        if (t.dim() != 3 or t.shape != p0.shape or t.dtype != p0.dtype or t.device != p0.device
+                or any(a != b for a, b, n_ in zip(t.stride(), p0.stride(), t.shape) if n_ > 1)):
+            raise ValueError(what)
+    return p0
+
+
+def _yxt(dims, p0):
+    """(ny, nx, k, sy, sx, st) of the plane p0 whose axes `dims` names."""
+    dims = tuple(dims)
+    if sorted(dims) != ['time', 'x', 'y']:
+        raise ValueError("dims must be a permutation of ('time', 'y', 'x')")
+    ay, ax, at = dims.index('y'), dims.index('x'), dims.index('time')
+    return (p0.shape[ay], p0.shape[ax], p0.shape[at], p0.stride(ay), p0.stride(ax), p0.stride(at))
+
+
+def _omnibus_outputs(ny, nx, k, dtype, dev, stats):
+    """change (y, x, time) and, with stats, z and P (y, x) -- else None, None."""
+    change = torch.empty((ny, nx, k), dtype=torch.uint8, device=dev)
+    z = torch.empty((ny, nx), dtype=dtype, device=dev) if stats else None
+    P = torch.empty((ny, nx), dtype=dtype, device=dev) if stats else None
+    return change, z, P
+
+
+def _pixel_major_ids(planes):
+    """_pixel_major_stride of every plane, or None unless all share shape, dtype and device and have one."""
+    p0 = planes[0]
+    ids = []
+    for t in planes:
+        if t.shape != p0.shape or t.dtype != p0.dtype or t.device != p0.device:
+            return None
+        ids.append(_pixel_major_stride(t))
+        if ids[-1] is None:
+            return None
+    return ids
+
+
+# ---------------------------------------------------------------------------
 # OmnibusTest C2
 # ---------------------------------------------------------------------------
 def change_detection(c11, c12re, c12im, c22, alpha, n=1, dims=('time', 'y', 'x'),
@@ -54,29 +100,14 @@ def change_detection(c11, c12re, c12im, c22, alpha, n=1, dims=('time', 'y', 'x')
         pixels are gathered from the planes).
     Returns uint8 tensor (y, x, time) [, z (y, x), P (y, x)].
     """
-    planes = (c11, c12re, c12im, c22)
-    for name, t in zip(('c11', 'c12re', 'c12im', 'c22'), planes):
-        _require_cuda(t, name)
-        if t.dim() != 3:
-            raise ValueError('%s must be 3-D, got shape %s' % (name, tuple(t.shape)))
-        # strides of length-1 axes address nothing: views of one buffer may carry different ones
-        same_strides = all(a == b for a, b, n_ in zip(t.stride(), c11.stride(), t.shape) if n_ > 1)
-        if (t.shape != c11.shape or not same_strides or t.dtype != c11.dtype
-                or t.device != c11.device):
-            raise ValueError('the four covariance planes must share shape, strides, '
-                             'dtype and device')
-    dims = tuple(dims)
-    if sorted(dims) != ['time', 'x', 'y']:
-        raise ValueError("dims must be a permutation of ('time', 'y', 'x')")
-    ay, ax, at = dims.index('y'), dims.index('x'), dims.index('time')
-    ny, nx, k = c11.shape[ay], c11.shape[ax], c11.shape[at]
-    sy, sx, st = c11.stride(ay), c11.stride(ax), c11.stride(at)
+    _plane_stack((c11, c12re, c12im, c22),
+                 'the four covariance planes must be 3-D and share shape, strides, dtype and device',
+                 names=('c11', 'c12re', 'c12im', 'c22'))
+    ny, nx, k, sy, sx, st = _yxt(dims, c11)
     dev = c11.device
     L = _lib.lib()
     with torch.cuda.device(dev):
-        change = torch.empty((ny, nx, k), dtype=torch.uint8, device=dev)
-        z = torch.empty((ny, nx), dtype=c11.dtype, device=dev) if stats else None
-        P = torch.empty((ny, nx), dtype=c11.dtype, device=dev) if stats else None
+        change, z, P = _omnibus_outputs(ny, nx, k, c11.dtype, dev, stats)
         if ny * nx * k > 0:
             min_bytes = C.c_size_t(0)
             nbytes = L.nd_amd_omnibus_c2_workspace_bytes(_DT[c11.dtype], ny, nx, k,
@@ -118,9 +149,7 @@ def change_detection_multilooked(c11, c12re, c12im, c22, alpha, ml, stats=False)
     if nbytes == 0 or sx != 1:
         return None
     with torch.cuda.device(dev):
-        change = torch.empty((ny, nx, k), dtype=torch.uint8, device=dev)
-        z = torch.empty((ny, nx), dtype=c11.dtype, device=dev) if stats else None
-        P = torch.empty((ny, nx), dtype=c11.dtype, device=dev) if stats else None
+        change, z, P = _omnibus_outputs(ny, nx, k, c11.dtype, dev, stats)
         # The dump of the fused path has a slot for every pixel of the raster (the multilooked series exists
         # nowhere else), about the size of the input, of which only the listed part is ever touched.  torch's
         # caching allocator hands the same block back from call to call; where the memory is not there the
@@ -153,13 +182,9 @@ def change_detection_pixel_major(c11, c12re, c12im, c22, alpha, n=1, stats=False
         return None
     # beyond the register-retaining sizes the kernel takes the sparse regime only (include/nd_amd.h)
     long_series = k > (24 if dt == torch.float32 else 12)
-    ids = []
-    for t in vs:
-        if t.shape != c11.shape or t.dtype != dt or t.device != c11.device:
-            return None
-        ids.append(_pixel_major_stride(t))
-        if ids[-1] is None:
-            return None
+    ids = _pixel_major_ids(vs)
+    if ids is None:
+        return None
     # The date strides come from the tensors' own strides only.  (Two views one element apart are
     # NOT proof of an interleaved complex tensor: buf[:-1] and buf[1:] of a real buffer look the
     # same.  The library pairs the two C12 reads itself when both strides are 2 and the pointers
@@ -169,9 +194,7 @@ def change_detection_pixel_major(c11, c12re, c12im, c22, alpha, n=1, stats=False
     dev = c11.device
     L = _lib.lib()
     with torch.cuda.device(dev):
-        change = torch.empty((ny, nx, k), dtype=torch.uint8, device=dev)
-        z = torch.empty((ny, nx), dtype=dt, device=dev) if stats else None
-        P = torch.empty((ny, nx), dtype=dt, device=dev) if stats else None
+        change, z, P = _omnibus_outputs(ny, nx, k, dt, dev, stats)
         nbytes = L.nd_amd_omnibus_c2_workspace_bytes(_DT[dt], ny, nx, k, None)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         rc = L.nd_amd_omnibus_c2_pixel_major(
@@ -192,34 +215,18 @@ def change_detection_c3(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=False
     planes = list(planes)
     if len(planes) != 9:
         raise ValueError('full-pol covariance needs nine real planes')
-    p0 = planes[0]
-    for i, t in enumerate(planes):
-        _require_cuda(t, 'planes[%d]' % i)
-        # strides of length-1 axes address nothing: views of one buffer may carry different ones
-        same_strides = t.dim() == 3 and all(a == b for a, b, n_ in zip(t.stride(), p0.stride(), t.shape)
-                                            if n_ > 1)
-        if (t.dim() != 3 or t.shape != p0.shape or not same_strides
-                or t.dtype != p0.dtype or t.device != p0.device):
-            raise ValueError('the nine covariance planes must be 3-D and share shape, strides, '
-                             'dtype and device')
-    dims = tuple(dims)
-    if sorted(dims) != ['time', 'x', 'y']:
-        raise ValueError("dims must be a permutation of ('time', 'y', 'x')")
-    ay, ax, at = dims.index('y'), dims.index('x'), dims.index('time')
-    ny, nx, k = p0.shape[ay], p0.shape[ax], p0.shape[at]
+    p0 = _plane_stack(planes, 'the nine covariance planes must be 3-D and share shape, strides, dtype and device')
+    ny, nx, k, sy, sx, st = _yxt(dims, p0)
     dev = p0.device
     L = _lib.lib()
     with torch.cuda.device(dev):
-        change = torch.empty((ny, nx, k), dtype=torch.uint8, device=dev)
-        z = torch.empty((ny, nx), dtype=p0.dtype, device=dev) if stats else None
-        P = torch.empty((ny, nx), dtype=p0.dtype, device=dev) if stats else None
+        change, z, P = _omnibus_outputs(ny, nx, k, p0.dtype, dev, stats)
         if ny * nx * k > 0:
             nbytes = L.nd_amd_omnibus_c3_workspace_bytes(ny, nx, k)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             ptrs = (C.c_void_p * 9)(*[t.data_ptr() for t in planes])
             _lib.check(L.nd_amd_omnibus_c3(
-                ptrs, _DT[p0.dtype], ny, nx, k, p0.stride(ay), p0.stride(ax), p0.stride(at),
-                int(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
+                ptrs, _DT[p0.dtype], ny, nx, k, sy, sx, st, int(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
                 _stream_ptr(dev)))
             ws.record_stream(torch.cuda.current_stream(dev))
     if stats:
@@ -235,33 +242,18 @@ def change_detection_diag(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=Fal
     planes = list(planes)
     if not 1 <= len(planes) <= 3:
         raise ValueError('the intensity-only test takes one to three channels, got %d' % len(planes))
-    p0 = planes[0]
-    for i, t in enumerate(planes):
-        _require_cuda(t, 'planes[%d]' % i)
-        # strides of length-1 axes address nothing: views of one buffer may carry different ones
-        same_strides = t.dim() == 3 and all(a == b for a, b, n_ in zip(t.stride(), p0.stride(), t.shape)
-                                            if n_ > 1)
-        if (t.dim() != 3 or t.shape != p0.shape or not same_strides
-                or t.dtype != p0.dtype or t.device != p0.device):
-            raise ValueError('the intensity planes must be 3-D and share shape, strides, dtype and device')
-    dims = tuple(dims)
-    if sorted(dims) != ['time', 'x', 'y']:
-        raise ValueError("dims must be a permutation of ('time', 'y', 'x')")
-    ay, ax, at = dims.index('y'), dims.index('x'), dims.index('time')
-    ny, nx, k = p0.shape[ay], p0.shape[ax], p0.shape[at]
+    p0 = _plane_stack(planes, 'the intensity planes must be 3-D and share shape, strides, dtype and device')
+    ny, nx, k, sy, sx, st = _yxt(dims, p0)
     dev = p0.device
     L = _lib.lib()
     with torch.cuda.device(dev):
-        change = torch.empty((ny, nx, k), dtype=torch.uint8, device=dev)
-        z = torch.empty((ny, nx), dtype=p0.dtype, device=dev) if stats else None
-        P = torch.empty((ny, nx), dtype=p0.dtype, device=dev) if stats else None
+        change, z, P = _omnibus_outputs(ny, nx, k, p0.dtype, dev, stats)
         if ny * nx * k > 0:
             nbytes = L.nd_amd_omnibus_diag_workspace_bytes(_DT[p0.dtype], len(planes), ny, nx, k)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             ptrs = (C.c_void_p * len(planes))(*[t.data_ptr() for t in planes])
             _lib.check(L.nd_amd_omnibus_diag(
-                ptrs, len(planes), _DT[p0.dtype], ny, nx, k, p0.stride(ay), p0.stride(ax), p0.stride(at),
-                float(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
+                ptrs, len(planes), _DT[p0.dtype], ny, nx, k, sy, sx, st, float(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
                 _stream_ptr(dev)))
             ws.record_stream(torch.cuda.current_stream(dev))
     if stats:
@@ -290,22 +282,10 @@ def change_segments(planes, change, structure, dims=('time', 'y', 'x'), directio
                          % (structure, {'diag': 'one to three', 'c2': 'four', 'c3': 'nine'}[structure], len(planes)))
     if not (direction or means):
         raise ValueError('change_segments: neither direction nor means is asked for')
-    p0 = planes[0]
-    for i, t in enumerate(planes):
-        _require_cuda(t, 'planes[%d]' % i)
-        # strides of length-1 axes address nothing: views of one buffer may carry different ones
-        same_strides = t.dim() == 3 and all(a == b for a, b, n_ in zip(t.stride(), p0.stride(), t.shape)
-                                            if n_ > 1)
-        if (t.dim() != 3 or t.shape != p0.shape or not same_strides
-                or t.dtype != p0.dtype or t.device != p0.device):
-            raise ValueError('the planes must be 3-D and share shape, strides, dtype and device')
+    p0 = _plane_stack(planes, 'the planes must be 3-D and share shape, strides, dtype and device')
     if any(st_ == 0 and n_ > 1 for st_, n_ in zip(p0.stride(), p0.shape)):
         raise ValueError('expanded planes (stride 0) are not served: the means would overlap')
-    dims = tuple(dims)
-    if sorted(dims) != ['time', 'x', 'y']:
-        raise ValueError("dims must be a permutation of ('time', 'y', 'x')")
-    ay, ax, at = dims.index('y'), dims.index('x'), dims.index('time')
-    ny, nx, k = p0.shape[ay], p0.shape[ax], p0.shape[at]
+    ny, nx, k, sy, sx, st = _yxt(dims, p0)
     if not isinstance(change, torch.Tensor):
         raise TypeError('change must be a torch.Tensor, got %r' % type(change))
     if change.dtype not in (torch.uint8, torch.bool):
@@ -329,7 +309,7 @@ def change_segments(planes, change, structure, dims=('time', 'y', 'x'), directio
             mptrs = (C.c_void_p * len(planes))(*[t.data_ptr() for t in out_m]) if means else None
             cbytes = change.view(torch.uint8) if change.dtype == torch.bool else change
             _lib.check(L.nd_amd_change_segments(
-                ptrs, len(planes), code, _DT[p0.dtype], ny, nx, k, p0.stride(ay), p0.stride(ax), p0.stride(at),
+                ptrs, len(planes), code, _DT[p0.dtype], ny, nx, k, sy, sx, st,
                 _ptr(cbytes), _ptr(out_d), mptrs, _stream_ptr(dev)))
     if direction and means:
         return out_d, out_m
@@ -350,13 +330,9 @@ def change_detection_c3_pixel_major(planes, alpha, n=1, stats=False):
     dt = p0.dtype
     if dt not in _DT or ny * nx * k == 0:
         return None
-    ids = []
-    for t in planes:
-        if t.shape != p0.shape or t.dtype != dt or t.device != p0.device:
-            return None
-        ids.append(_pixel_major_stride(t))
-        if ids[-1] is None:
-            return None
+    ids = _pixel_major_ids(planes)
+    if ids is None:
+        return None
     # the entry point's documented conditions (include/nd_amd.h), checked before anything is allocated: with the
     # reference's default alpha = 0.01 every full-pol (y, x, time) call would otherwise allocate the map and the
     # workspace only to learn that it is declined.  (0.75 is the entry point's fixed switch-over to the fused search,
@@ -368,9 +344,7 @@ def change_detection_c3_pixel_major(planes, alpha, n=1, stats=False):
     dev = p0.device
     L = _lib.lib()
     with torch.cuda.device(dev):
-        change = torch.empty((ny, nx, k), dtype=torch.uint8, device=dev)
-        z = torch.empty((ny, nx), dtype=dt, device=dev) if stats else None
-        P = torch.empty((ny, nx), dtype=dt, device=dev) if stats else None
+        change, z, P = _omnibus_outputs(ny, nx, k, dt, dev, stats)
         nbytes = L.nd_amd_omnibus_c3_workspace_bytes(ny, nx, k)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         ptrs = (C.c_void_p * 9)(*[t.data_ptr() for t in planes])
