@@ -15,6 +15,19 @@ CORE_SHAPES = [(1, 1, 1), (2, 1, 63), (3, 3, 65), (10, 5, 130), (25, 4, 257), (3
 FACTORS = np.array([0.25, 1.0, 4.0])
 
 
+def _bits(a):
+    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+def assert_bit_equal(got, want, what=''):
+    """the comparison rule of the means: same type and shape, NaN where the restatement has NaN, elsewhere the
+    same bits -- no tolerance, no excluded pixel"""
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    nan = np.isnan(want)
+    np.testing.assert_array_equal(np.isnan(got), nan, err_msg=what)
+    np.testing.assert_array_equal(_bits(np.where(nan, 0, got)), _bits(np.where(nan, 0, want)), err_msg=what)
+
+
 def bernoulli_map(rng, k, ny, nx, p=0.25):
     return (rng.random((ny, nx, k)) < p).astype(np.uint8)
 

@@ -65,3 +65,26 @@ def integer_stack(seed=0):
     X = rng.integers(0, 12, size=(4000, 3)).astype(np.float64)
     y = (X[:, 0] + 2 * X[:, 1] > 14).astype(np.int64) + (X[:, 2] > 6)
     return X, y
+
+
+def array_forest(X, n_classes, n_trees=7, depth=5, seed=0):
+    """A forest as scikit-learn's arrays, built without scikit-learn: complete trees in heap order (the children
+    of node i are 2 i + 1 and 2 i + 2) whose inner nodes take the features in turn, so that a forest of a few
+    trees reads every feature, and test them against values the float32 matrix holds: features lie exactly on
+    thresholds.  Leaf rows are random distributions over the classes.
+    -> (feature, threshold, left, right, value, tree_offsets, classes)"""
+    rng = np.random.default_rng(400 + seed)
+    X32 = X[~np.isnan(X).any(axis=1)].astype(np.float32)
+    inner, n = 2 ** depth - 1, 2 ** (depth + 1) - 1
+    feature, threshold, left, right = [], [], [], []
+    for t in range(n_trees):
+        for i in range(n):
+            f = (t + i) % X.shape[1]
+            feature.append(f if i < inner else -2)
+            threshold.append(float(X32[rng.integers(0, X32.shape[0]), f]) if i < inner else -2.0)
+            left.append(2 * i + 1 if i < inner else -1)
+            right.append(2 * i + 2 if i < inner else -1)
+    value = rng.random((len(feature), n_classes))
+    value /= value.sum(axis=1, keepdims=True)
+    return (np.array(feature), np.array(threshold), np.array(left), np.array(right), value,
+            np.arange(n_trees + 1) * n, np.arange(1, n_classes + 1))

@@ -6,21 +6,11 @@ import pytest
 
 from tests import change_segments_cases as cases
 from tests import change_segments_ref as R
+from tests.change_segments_cases import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
 
 CORE = cases.core_cases()
-
-
-def _bits(a):
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
-
-
-def assert_bit_equal(got, want, what=''):
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    nan = np.isnan(want)
-    np.testing.assert_array_equal(np.isnan(got), nan, err_msg=what)
-    np.testing.assert_array_equal(_bits(np.where(nan, 0, got)), _bits(np.where(nan, 0, want)), err_msg=what)
 
 
 def _run(device, planes, change, structure, direction=True, means=True, dims=('time', 'y', 'x')):

@@ -205,6 +205,64 @@ def test_kmeans_six_features(device, dtype, layout, scale):
     np.testing.assert_array_equal(lv[keep][ok], ref.kmeans_labels(Xp, centers)[ok])
 
 
+def many_feature_case(dtype, nt, scale):
+    """nt dates of the three variables as 3 nt features -> (data, keep, shape, scaler, the kept rows as a model
+    sees them)"""
+    data, _ = cases.stack(3, dtype, seed=9, nt=nt)
+    X, shape = ref.build_X(cases.variables(data), ('y', 'x'), ('time',))
+    assert X.shape[1] == 3 * nt and X.dtype == dtype
+    keep = ~np.isnan(X).any(axis=1)
+    assert 0 < keep.sum() < keep.size
+    sc = Scaler(np.nanmean(X, 0).astype(np.float64), np.nanstd(X, 0).astype(np.float64)) if scale else None
+    return data, keep, shape, sc, (X[keep] if sc is None else ref.scale(X[keep], sc.mean_, sc.scale_))
+
+
+def check_array_forest(device, data, layout, keep, shape, sc, Xp):
+    """a forest of arrays that reads every feature, thresholds on the (scaled) data's own values: probabilities
+    bit for bit, labels equal, NaN on the masked rows"""
+    model = classify.ForestModel(*cases.array_forest(Xp, 4, seed=Xp.shape[1]))
+    assert set(model.feature[model.feature >= 0]) == set(range(Xp.shape[1]))
+    proba = ref.forest_proba(Xp, model.feature, model.threshold, model.left, model.right, model.value,
+                             model.tree_offsets)
+    assert len(np.unique(np.argmax(proba, 1))) == 4
+    want_p = ref.masked(proba, keep)
+    want_l = ref.masked(ref.forest_predict(proba, model.classes), keep)
+    ds = dataset(data, layout, device)
+    p = classify.predict_forest(ds, model, ('time',), 'predict_proba', sc)
+    l = classify.predict_forest(ds, model, ('time',), 'predict', sc)
+    assert p.dims == ('y', 'x', 'label') and l.dims == ('y', 'x')
+    pv, lv = host(p.values).reshape(keep.size, -1), host(l.values).reshape(-1)
+    assert np.isnan(pv[~keep]).all() and np.isnan(lv[~keep]).all()
+    assert pv[keep].tobytes() == want_p[keep].tobytes()
+    np.testing.assert_array_equal(lv, want_l)
+
+
+@pytest.mark.parametrize('scale', [False, True])
+@pytest.mark.parametrize('layout', ['tyx', 'yxt'])
+@pytest.mark.parametrize('dtype', cases.DTYPES)
+def test_forest_six_features(device, dtype, layout, scale):
+    """two dates as features: 6 features, the 5-to-8-feature register form of the forest walk"""
+    data, keep, shape, sc, Xp = many_feature_case(dtype, 2, scale)
+    check_array_forest(device, data, layout, keep, shape, sc, Xp)
+
+
+@pytest.mark.parametrize('layout', ['tyx', 'yxt'])
+@pytest.mark.parametrize('dtype', cases.DTYPES)
+def test_twelve_features_with_a_scaler(device, dtype, layout):
+    """four dates as features with a scaler: the scaler on the form that reads its features from memory, for the
+    forest (bit for bit) and for k-means (labels equal outside the 1e-12 near-ties, at most 1 row in 10^4)"""
+    data, keep, shape, sc, Xp = many_feature_case(dtype, 4, True)
+    check_array_forest(device, data, layout, keep, shape, sc, Xp)
+    centers = Xp[[5, 200, 400, 600, 700]].astype(np.float64) * 1.0625
+    ok = ref.kmeans_gap(Xp, centers) >= 1e-12
+    assert (~ok).mean() <= 1e-4
+    got = classify.predict_kmeans(dataset(data, layout, device), classify.KMeansModel(centers), ('time',), sc)
+    lv = host(got.values).reshape(-1)
+    assert got.dims == ('y', 'x') and np.isnan(lv[~keep]).all()
+    np.testing.assert_array_equal(lv[keep][ok], ref.kmeans_labels(Xp, centers)[ok])
+    assert len(np.unique(lv[keep])) == 5
+
+
 def test_classifier_reuses_the_packed_model(device):
     pytest.importorskip('sklearn')
     from sklearn.ensemble import RandomForestClassifier

@@ -1,4 +1,9 @@
-"""Replay one tools/fuzz_parity.py case and print where the HIP path and the oracle differ."""
+"""Replay one tools/fuzz_parity.py case and print where the HIP path and the oracle differ.
+
+    python tools/fuzz_replay.py <family> <seed> <i>
+
+The families that keep their newest got / want in fuzz_parity.LAST get the first ten differing positions of
+every output."""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import numpy as np, torch
@@ -26,3 +31,15 @@ if 'got' in captured:
     print('n bad', len(bad), 'of', g.size)
     for idx in bad[:10]:
         idx = tuple(idx); print(idx, g[idx], w[idx], captured['in'][idx])
+if F.LAST.get('name') == name:
+    for key, w in F.LAST['want'].items():
+        g = F.LAST['got'].get(key)
+        if g is None or np.shape(g) != np.shape(w):
+            print(key, 'got', None if g is None else np.shape(g), 'want', np.shape(w))
+            continue
+        g, w = np.asarray(g), np.asarray(w)
+        with np.errstate(all='ignore'):
+            bad = np.argwhere(~((g == w) | ((g != g) & (w != w))))
+        print(key, 'n differing', len(bad), 'of', w.size)
+        for idx in bad[:10]:
+            idx = tuple(idx); print(' ', idx, 'got', g[idx], 'want', w[idx])
