@@ -2388,31 +2388,19 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_kernel(const OmniSearchA
     T *lds = reinterpret_cast<T *>(nd_smem);
     const int lane = threadIdx.x;
     const int k = s.k;
-    // Per-j constants of the screen (m2rho, pklogk, zlo_a, zhi_a): every lane looks up its own j
-    // in every iteration, so they sit in LDS as four separate arrays of doubles -- consecutive j in
-    // consecutive banks (as 64-byte records all j of one parity would share a bank).
+    // Per-j constants of the screen behind the series image (ScreenLds; FS: one 16-byte record per j; GSCR: none,
+    // the view is the table in global memory).  MODE 1 keeps no series image: the constants alone, 32 (k + 1) bytes.
     const OmniTabEntry *tabp = s.tab;          // full records, read only on the rare exact path
-    const int kp = k + 1;
-    // (MODE 1 keeps no series image: the constants alone, 32 (k + 1) bytes)
     double *scr = reinterpret_cast<double *>(nd_smem + (USE_LDS ? (size_t)k * 4 * PXW * sizeof(T) : 0));
-    DenseScreenEntry *scr_f = reinterpret_cast<DenseScreenEntry *>(scr);      // FS: one 16-byte record per j
+    DenseScreenEntry *scr_f = reinterpret_cast<DenseScreenEntry *>(scr);
+    ScreenLds scr_d{scr, k + 1};
     if (FS) {
         for (int j = lane; j <= k; j += 64) scr_f[j] = fscr.e[j];
         __syncthreads();
     } else if (!GSCR) {
-        for (int j = lane; j <= k; j += 64) {
-            const OmniTabEntry e = s.tab[j];
-            scr[j] = e.m2rho;
-            scr[kp + j] = e.pklogk;
-            scr[2 * kp + j] = e.zlo_a;
-            scr[3 * kp + j] = e.zhi_a;
-        }
+        scr_d = stage_screen(scr, tabp, k, lane);
         __syncthreads();
     }
-    auto screen = [&](int f, int j) -> double {
-        if (GSCR) return f == 0 ? tabp[j].m2rho : (f == 1 ? tabp[j].pklogk : (f == 2 ? tabp[j].zlo_a : tabp[j].zhi_a));
-        return scr[f * kp + j];
-    };
     // blocks shard, shard + kShards, ... work through the list of one shard
     const unsigned shard = blockIdx.x % kShards;
     const unsigned lblock = blockIdx.x / kShards;
@@ -2514,80 +2502,32 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_kernel(const OmniSearchA
             }
         };
 
-        // nd/_change.pyx:235-257 as ONE sweep per segment.  The reference first tests the global
-        // hypothesis over ts[l:], then the marginal ones over ts[l:l+j], j = 2, 3, ...; both are
-        // functions of the same running accumulation started at l (the global test is the state
-        // after the last date), so each lane sweeps t = l .. k-1 once, remembers the first date at
-        // which a marginal test fires, and commits it only if the global test -- known at the end
-        // of the sweep -- passes.  Every iteration of the wave is then the same small body (one
-        // date + at most one test per lane), whatever segment each lane is in.
+        // nd/_change.pyx:235-257 as one sweep per segment (omnibus_search.hpp): every iteration of the wave
+        // is the same small body (one date + at most one test per lane), whatever segment each lane is in.
         Accum<T> A;
         A.reset();
-        int l = 0;                 // segment start
-        int t = 0;                 // next date to fold
-        int fire_at = -1;          // first date of this segment whose marginal test fired
-        bool done = !active;
+        Sweep sw;
+        sw.begin(active);
         uint8_t *res = s.change + pix * (int64_t)k;
 
-        while (__any(!done)) {
-            if (!done) {
-                load_step(A, t);
-                const int jj = t - l + 1;
-                const bool last = (t == k - 1);
-                // a marginal test while none has fired yet (j >= 2); at the last date the same
-                // evaluation is the global test, needed even if a marginal fired earlier
-                const bool need = (jj >= 2) && (fire_at < 0 || last);
-                // Screen: z from the hardware log2 against the widened bounds.  fires = above the
-                // band for certain; inband = the screen cannot tell.  (NaN compares false twice.)
-                bool fires = false, inband = false;
-                if (need && FS) {
-                    const T dets = (A.s11 * A.s22) - ((A.s12r * A.s12r) + (A.s12i * A.s12i));
-                    // (the product a positive normal double: its logarithm below is then meaningful, and the
-                    //  reference's own log() of it finite)
-                    const bool ok = (dets > (T)0) & (dets < (T)INFINITY) & __builtin_amdgcn_class(A.prod, 0x100);
-                    const DenseScreenEntry c = scr_f[jj];
-                    int es, eP;
-                    float ms, mP;
-                    log2_parts(ok ? dets : (T)1, es, ms);
-                    log2_parts(ok ? A.prod : 1.0, eP, mP);
-                    const int E = (eP - c.re) - __mul24(jj, es);
-                    const float x = (float)E + __builtin_fmaf(-(float)jj, ms, mP - c.rf);
-                    fires = ok & (x < c.a);
-                    inband = !(fires | (ok & (x > c.b)));
-                } else if (need) {
-                    const double za = z_approx<T>(A, jj, s.nlooks, screen(0, jj), screen(1, jj));
-                    fires = (za > screen(3, jj)) && (za < INFINITY);
-                    inband = (za >= screen(2, jj)) && !fires;
-                }
-                // The exact evaluation (two double logs, possibly the chi-square pair) sits behind
-                // a wave-uniform branch so that the compiler cannot fold it into the loop body: it
-                // is needed for ~1e-5 of the tests, the loop body runs for all of them.
-                if (__any(inband)) {
-                    if (inband) {
-                        const OmniTabEntry e = tabp[jj];
-                        fires = exact_verdict<T>(z_stat<T>(A, jj, s.nlooks, e), 4 * (jj - 1), e, s.alpha);
-                    }
-                }
-                if (!last) {
-                    if (fires && fire_at < 0) fire_at = t;
-                    t = t + 1;
-                } else {
-                    // `fires` is the global test of ts[l:] (for jj == 1 there is nothing to test)
-                    if (fires && fire_at < 0) fire_at = t;
-                    if (fires && jj >= 2) {
-                        res[fire_at] = 1;                  // :252, l + r with r = j - 1
-                        l = fire_at;                       // :255
-                        if (l >= k - 1) {
-                            done = true;                   // :256
-                        } else {
-                            A.reset();
-                            t = l;
-                            fire_at = -1;
-                        }
-                    } else {
-                        done = true;                       // :241-242
-                    }
-                }
+        while (__any(!sw.done)) {
+            if (!sw.done) {
+                load_step(A, sw.t);
+                const int jj = sw.t - sw.l + 1;
+                const bool last = (sw.t == k - 1);
+                const bool need = sw.need(jj, last);
+                bool fires;
+                if constexpr (FS)
+                    fires = test_f32(need, A, jj, s.nlooks, s.alpha, scr_f, tabp);
+                else if constexpr (GSCR)
+                    fires = test_f64(need, A, jj, s.nlooks, s.alpha, TabGlobal{tabp}, tabp);
+                else
+                    fires = test_f64(need, A, jj, s.nlooks, s.alpha, scr_d, tabp);
+                sw.note(fires, sw.t);
+                if (!last)
+                    sw.t = sw.t + 1;
+                else
+                    sw.commit(fires, k, A, [&](const int at) { res[at] = 1; });
             }
         }
     }
@@ -2604,19 +2544,41 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_kernel(const OmniSearchA
 // in flight), every lane folding from its own segment start on; behind the last date a lane commits the first
 // firing date of its segment if the global test fired (nd/_change.pyx:235-257, one sweep per segment as in
 // omnibus_c2_search_kernel) and starts its next segment there; rounds repeat while a lane has a segment
-// left.  The fold, the float32 screen and the exact evaluation behind a wave-uniform branch are the
-// sweep's, operation for operation.  List entries beyond the dump's capacity: omnibus_c2_search_kernel
-// (OmniSearchArgs::first).
+// left.  The rounds themselves are search_rounds of omnibus_search.hpp, shared with the full-pol twin; this unit
+// adds how a lane's dates are read from its blocked dump (RoundsRing).  List entries beyond the dump's capacity:
+// omnibus_c2_search_kernel (OmniSearchArgs::first).
 // -----------------------------------------------------------------------------------------
+// this lane's series in a block of the dump, one 16-byte piece per date; four dates in flight
+template <typename T>
+struct RoundsRing {
+    static constexpr bool kGrouped = false;
+    const T *blk;                                        // the lane's values of date t: blk + t * 256 (elements)
+    Pack<T, 4> ring[4];
+    __device__ __forceinline__ void prime(const int t0, const int k)
+    {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int tu = t0 + u < k ? t0 + u : k - 1;
+            ring[u] = *reinterpret_cast<const Pack<T, 4> *>(blk + (int64_t)tu * 256);
+        }
+    }
+    __device__ __forceinline__ void group(int, int) {}
+    __device__ __forceinline__ void fold(Accum<T> &A, const int u, const int t, const int k, const bool on)
+    {
+        const Pack<T, 4> cur = ring[u];
+        const int tn = t + 4 < k ? t + 4 : k - 1;
+        ring[u] = *reinterpret_cast<const Pack<T, 4> *>(blk + (int64_t)tn * 256);
+        if (on) A.step(cur.v[0], cur.v[1], cur.v[2], cur.v[3]);
+    }
+};
+
 template <typename T>
 __global__ void __launch_bounds__(64) omnibus_c2_search_rounds_kernel(const OmniSearchArgs<T> s, const DenseScreenLong fscr)
 {
-    constexpr int PF = 4;                                // dates in flight
     extern __shared__ __align__(16) unsigned char nd_smem_rd[];
     DenseScreenEntry *scr_f = reinterpret_cast<DenseScreenEntry *>(nd_smem_rd);
     const int lane = threadIdx.x;
     const int k = s.k;
-    const OmniTabEntry *tabp = s.tab;
     for (int j = lane; j <= k; j += 64) scr_f[j] = fscr.e[j];
     __syncthreads();
     const unsigned shard = blockIdx.x % kShards;
@@ -2624,92 +2586,12 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_rounds_kernel(const Omni
     const unsigned nlblock = gridDim.x / kShards;
     const uint32_t nall = s.flag_count[shard * kCounterStride];
     const uint32_t n = nall < s.dump_cap ? nall : s.dump_cap;          // (dump_cap: a multiple of 64)
-    const uint32_t *list = s.flag_idx + (size_t)shard * s.seg;
-
-    for (uint32_t base = lblock * 64u; base < n; base += nlblock * 64u) {
-        const uint32_t idx = base + lane;
-        const bool active = idx < n;
-        const int64_t pix = active ? (int64_t)list[idx] : 0;
-        // this lane's values of date t: blk + t * 256 (elements)
-        const T *blk = s.dump + (((int64_t)shard * (s.dump_cap >> 6) + (base >> 6)) * (int64_t)k * 64 + lane) * 4;
-        uint8_t *res = s.change + pix * (int64_t)k;
-        Accum<T> A;
-        A.reset();
-        int l = 0, fire_at = -1;
-        bool done = !active;
-        while (__any(!done)) {
-            // the round starts at the earliest segment start among the unfinished lanes
-            int t0 = done ? k : l;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const int o = __shfl_xor(t0, off);
-                t0 = o < t0 ? o : t0;
-            }
-            t0 = __builtin_amdgcn_readfirstlane(t0);
-            bool fires = false;                                  // of the test met last: at t = k - 1 the global test
-            Pack<T, 4> ring[PF];
-#pragma unroll
-            for (int u = 0; u < PF; ++u) {
-                const int tu = t0 + u < k ? t0 + u : k - 1;
-                ring[u] = *reinterpret_cast<const Pack<T, 4> *>(blk + (int64_t)tu * 256);
-            }
-            for (int tb = t0; tb < k; tb += PF) {
-#pragma unroll
-                for (int u = 0; u < PF; ++u) {
-                    const int t = tb + u;                        // wave-uniform
-                    if (t < k) {
-                        const Pack<T, 4> cur = ring[u];
-                        const int tn = t + PF < k ? t + PF : k - 1;
-                        ring[u] = *reinterpret_cast<const Pack<T, 4> *>(blk + (int64_t)tn * 256);
-                        const bool on = !done && t >= l;
-                        if (on) A.step(cur.v[0], cur.v[1], cur.v[2], cur.v[3]);
-                        const int jj = t - l + 1;
-                        const bool last = (t == k - 1);
-                        const bool need = on && (jj >= 2) && (fire_at < 0 || last);
-                        bool f = false, inband = false;
-                        if (need) {
-                            const T dets = (A.s11 * A.s22) - ((A.s12r * A.s12r) + (A.s12i * A.s12i));
-                            const bool ok = (dets > (T)0) & (dets < (T)INFINITY) & __builtin_amdgcn_class(A.prod, 0x100);
-                            const DenseScreenEntry c = scr_f[jj];
-                            int es, eP;
-                            float ms, mP;
-                            log2_parts(ok ? dets : (T)1, es, ms);
-                            log2_parts(ok ? A.prod : 1.0, eP, mP);
-                            const int E = (eP - c.re) - __mul24(jj, es);
-                            const float x = (float)E + __builtin_fmaf(-(float)jj, ms, mP - c.rf);
-                            f = ok & (x < c.a);
-                            inband = !(f | (ok & (x > c.b)));
-                        }
-                        if (__any(inband)) {
-                            if (inband) {
-                                const OmniTabEntry e = tabp[jj];
-                                f = exact_verdict<T>(z_stat<T>(A, jj, s.nlooks, e), 4 * (jj - 1), e, s.alpha);
-                            }
-                        }
-                        if (need) {
-                            if (f && fire_at < 0) fire_at = t;
-                            if (last) fires = f;
-                        }
-                    }
-                }
-            }
-            // behind the last date: `fires` is the global test of ts[l:] (a segment of one date has none)
-            if (!done) {
-                if (fires && (k - l) >= 2) {
-                    res[fire_at] = 1;                          // :252
-                    l = fire_at;                               // :255
-                    if (l >= k - 1) {
-                        done = true;                           // :256
-                    } else {
-                        A.reset();
-                        fire_at = -1;
-                    }
-                } else {
-                    done = true;                               // :241-242
-                }
-            }
-        }
-    }
+    search_rounds<Accum<T>>(k, n, s.flag_idx + (size_t)shard * s.seg, lblock, nlblock, s.change, s.nlooks, s.alpha,
+                            scr_f, s.tab, lane, [&](const uint32_t base) {
+                                RoundsRing<T> ld;
+                                ld.blk = s.dump + (((int64_t)shard * (s.dump_cap >> 6) + (base >> 6)) * (int64_t)k * 64 + lane) * 4;
+                                return ld;
+                            });
 }
 
 // -----------------------------------------------------------------------------------------
@@ -2793,14 +2675,17 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_starts_kernel(const Omni
             }
             return q;
         };
-        int nxt_a = -1, nxt_b = -1, nxt_c = -1; // per sweep: the next segment start, or stop
+        // per sweep: the next segment start, or stop (three names, not an array written by `sweep`: that form took a
+        // vector register more in the float64 kernel)
+        int nxt_a = -1, nxt_b = -1, nxt_c = -1;
         for (int sweep = 0; sweep < nsweep; ++sweep) {
         const int l = l0 + 64 * sweep;
         const bool lact = active && l < ns;
         Accum<T> A;
         A.reset();
-        int fire_at = -1;
-        int nxt = -1;                           // stop
+        Sweep sw;                               // (of the one segment this lane sweeps: l stays)
+        sw.begin(true);
+        int nx = -1;                            // stop
         // Four dates per trip, the next four in flight meanwhile: the kernel's time is the dependent
         // chain of one wave, and a load per date (even one date ahead) was most of it.  (Idle lanes
         // load nothing: a stand-in read of pixel 0 from 4 x k planes far apart would put its address
@@ -2829,42 +2714,17 @@ __global__ void __launch_bounds__(64) omnibus_c2_search_starts_kernel(const Omni
                 if (on) A.step(q[u].v[0], q[u].v[1], q[u].v[2], q[u].v[3]);
                 const int jj = i + 1;
                 const bool last = (t == k - 1);
-                const bool need = on && (jj >= 2) && (fire_at < 0 || last);
-                bool fires = false, inband = false;
-                if (need) {
-                    const OmniTabEntry &e = tabp[jj];
-                    const double za = z_approx<T>(A, jj, s.nlooks, e.m2rho, e.pklogk);
-                    fires = (za > e.zhi_a) && (za < INFINITY);
-                    inband = (za >= e.zlo_a) && !fires;
-                }
-                if (__any(inband)) {
-                    if (inband) {
-                        const OmniTabEntry e = tabp[jj];
-                        fires = exact_verdict<T>(z_stat<T>(A, jj, s.nlooks, e), 4 * (jj - 1), e, s.alpha);
-                    }
-                }
-                if (on && fires && fire_at < 0) fire_at = t;
-                if (on && last && fires) nxt = fire_at;      // the global test of ts[l:] fired (jj >= 2 here)
+                const bool need = on && sw.need(jj, last);
+                const bool fires = test_f64(need, A, jj, s.nlooks, s.alpha, TabGlobal{tabp}, tabp);
+                sw.note(fires, t);
+                if (last && fires) nx = sw.fire_at;          // the global test of ts[l:] fired (jj >= 2 here)
             }
         }
-        if (sweep == 0) nxt_a = nxt; else if (sweep == 1) nxt_b = nxt; else nxt_c = nxt;
+        if (sweep == 0) nxt_a = nx; else if (sweep == 1) nxt_b = nx; else nxt_c = nx;
         }
-        // follow the chain from l = 0; the group's first lane writes the changes
-        int at = 0;
-        for (int step = 0; step < ns; ++step) {
-            const int ats = (at >= 0 && at < ns) ? at : 0;
-            const int src = grp * nsw + (ats & 63) % nsw;
-            const int na = __shfl(nxt_a, src), nb = __shfl(nxt_b, src), nc = __shfl(nxt_c, src);
-            const int n1 = (ns > 64 && ats >= 128) ? nc : ((ns > 64 && ats >= 64) ? nb : na);
-            if (at >= 0 && at < ns) {
-                if (n1 < 0) {
-                    at = -1;                                   // :241-242
-                } else {
-                    if (active && l0 == 0) s.change[pix * (int64_t)k + n1] = 1;  // :252 (the row was zero-filled)
-                    at = n1;                                   // :255; n1 = k - 1 ends the search (:256)
-                }
-            }
-        }
+        const int nxt[3] = {nxt_a, nxt_b, nxt_c};
+        // follow the chain from l = 0; the group's first lane writes the changes (the row was zero-filled)
+        follow_starts_chain<3>(nxt, ns, nsw, grp, active && l0 == 0, s.change + pix * (int64_t)k);
     }
 }
 

@@ -1,65 +1,26 @@
 // nd_amd/csrc/omnibus_c2_device.hpp -- device-side pieces of the dual-pol omnibus test shared by
-// omnibus.hip and omnibus_ml.hip: the reference's running state (nd/_change.pyx:53-77), pass A's
-// argument block, the dump of a register-held series and the two-pass search on a series
-// held in registers (dense_chain).  Moved here verbatim from omnibus.hip (round 4) so that the
+// omnibus.hip and omnibus_ml.hip: pass A's argument block, the dump of a register-held series and
+// the two-pass search on a series held in registers (dense_chain); the running state and the search
+// shared with the other families come with omnibus_search.hpp.  Moved here verbatim from omnibus.hip (round 4) so that the
 // multilooking front end can live in a translation unit of its own.
 #pragma once
 #include <type_traits>
 
 #include "omnibus_common.hpp"
+#include "omnibus_search.hpp"
 
 namespace nd_amd {
 
-// ---- the reference's running state (nd/_change.pyx:53-69) -------------------------------
-template <typename T>
-struct Accum {
-    T s11, s12r, s12i, s22;
-    double prod;
-    __device__ __forceinline__ void reset()
-    {
-        s11 = 0;
-        s12r = 0;
-        s12i = 0;
-        s22 = 0;
-        prod = 1.0;
-    }
-    __device__ __forceinline__ void step(T a, T b, T c, T d)
-    {
-        const T det = (a * d) - ((b * b) + (c * c));
-        prod = prod * (double)det;
-        s11 = s11 + a;
-        s12r = s12r + b;
-        s12i = s12i + c;
-        s22 = s22 + d;
-    }
-};
-
-// z = -2 rho ln Q over j matrices (nd/_change.pyx:72-76)
+// The running state Accum<T> and the statistic over it: omnibus_search.hpp.  The entry forms, as pass A asks them:
 template <typename T>
 __device__ __forceinline__ T z_stat(const Accum<T> &A, int j, double nlooks, const OmniTabEntry &e)
 {
-    const T det_of_sum = (A.s11 * A.s22) - ((A.s12r * A.s12r) + (A.s12i * A.s12i));
-    const double logQ =
-        nlooks * ((e.pklogk + log(A.prod)) - ((double)j * log((double)det_of_sum)));
-    return (T)(e.m2rho * logQ);
-}
-
-// Screen statistic: z from approx_ln.  |z_approx - z| <= |m2rho| n (k+1) 1e-7; the host widens
-// zlo_a / zhi_a by ten times that, so z_approx < zlo_a implies z < zlo (omni tables).
-template <typename T>
-__device__ __forceinline__ double z_approx(const Accum<T> &A, int j, double nlooks, double m2rho,
-                                           double pklogk)
-{
-    const T det_of_sum = (A.s11 * A.s22) - ((A.s12r * A.s12r) + (A.s12i * A.s12i));
-    const double logQ = nlooks * ((pklogk + approx_ln(A.prod)) -
-                                  ((double)j * approx_ln((double)det_of_sum)));
-    return m2rho * logQ;
+    return z_stat(A, j, nlooks, e.m2rho, e.pklogk);
 }
 template <typename T>
-__device__ __forceinline__ double z_approx(const Accum<T> &A, int j, double nlooks,
-                                           const OmniTabEntry &e)
+__device__ __forceinline__ double z_approx(const Accum<T> &A, int j, double nlooks, const OmniTabEntry &e)
 {
-    return z_approx<T>(A, j, nlooks, e.m2rho, e.pklogk);
+    return z_approx(A, j, nlooks, e.m2rho, e.pklogk);
 }
 
 // The input planes are read exactly once and the change map is written once: both bypass the

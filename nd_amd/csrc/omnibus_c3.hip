@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "omnibus_common.hpp"
+#include "omnibus_search.hpp"
 
 namespace nd_amd {
 
@@ -32,58 +33,17 @@ constexpr int kC3CounterStride = 32;
 constexpr int kC3Chunk = 4;          // dates per load chunk in pass A
 constexpr size_t kC3CounterBytes = (size_t)kC3Shards * kC3CounterStride * sizeof(uint32_t);
 
-template <typename T>
-__device__ __forceinline__ T det3(const T (&v)[9])
-{
-    const T a = v[0], b = v[1], c = v[2];
-    const T xr = v[3], xi = v[4], yr = v[5], yi = v[6], zr = v[7], zi = v[8];
-    const T re = (((xr * zr) - (xi * zi)) * yr) + (((xr * zi) + (xi * zr)) * yi);
-    return (((((a * b) * c) - (a * ((zr * zr) + (zi * zi)))) - (b * ((yr * yr) + (yi * yi)))) -
-            (c * ((xr * xr) + (xi * xi)))) +
-           ((T)2 * re);
-}
-
-template <typename T>
-struct Accum3 {
-    T s[9];
-    double prod;
-    __device__ __forceinline__ void reset()
-    {
-#pragma unroll
-        for (int c = 0; c < 9; ++c) s[c] = 0;
-        prod = 1.0;
-    }
-    __device__ __forceinline__ void step(const T (&v)[9])
-    {
-        prod = prod * (double)det3<T>(v);
-#pragma unroll
-        for (int c = 0; c < 9; ++c) s[c] = s[c] + v[c];
-    }
-};
-
+// det3, the running state Accum3<T> and the statistic over it: omnibus_search.hpp.  The entry forms, as pass A
+// asks them:
 template <typename T>
 __device__ __forceinline__ T z_stat3(const Accum3<T> &A, int j, double nlooks, const OmniTabEntry &e)
 {
-    const T det_of_sum = det3<T>(A.s);
-    const double logQ =
-        nlooks * ((e.pklogk + log(A.prod)) - ((double)j * log((double)det_of_sum)));
-    return (T)(e.m2rho * logQ);
-}
-
-template <typename T>
-__device__ __forceinline__ double z_approx3(const Accum3<T> &A, int j, double nlooks, double m2rho,
-                                            double pklogk)
-{
-    const T det_of_sum = det3<T>(A.s);
-    const double logQ = nlooks * ((pklogk + approx_ln(A.prod)) -
-                                  ((double)j * approx_ln((double)det_of_sum)));
-    return m2rho * logQ;
+    return z_stat(A, j, nlooks, e.m2rho, e.pklogk);
 }
 template <typename T>
-__device__ __forceinline__ double z_approx3(const Accum3<T> &A, int j, double nlooks,
-                                            const OmniTabEntry &e)
+__device__ __forceinline__ double z_approx3(const Accum3<T> &A, int j, double nlooks, const OmniTabEntry &e)
 {
-    return z_approx3<T>(A, j, nlooks, e.m2rho, e.pklogk);
+    return z_approx(A, j, nlooks, e.m2rho, e.pklogk);
 }
 
 template <typename T>
@@ -904,7 +864,9 @@ __global__ void __launch_bounds__(kC3Threads) omnibus_c3_stream_kernel(const C3A
         const unsigned slot = wave_claim(listed, g.flag_count + shard * kC3CounterStride, lane);
         if (listed) g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
     }
-    // a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275)
+    // a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275).  Not zero_fill_span:
+    // that helper's 16-byte stores are non-temporal, these are plain ones -- another instruction, and which of the
+    // two is faster here has not been measured, so the text stays as it is.
     if (!dense && wnp > 0) {
         const int nb = wnp * k;
         int head = (int)((16 - ((uintptr_t)wob & 15)) & 15);
@@ -1161,7 +1123,9 @@ __global__ void __launch_bounds__(kC3Threads) omnibus_c3_stream_chain_kernel(con
         const unsigned slot = wave_claim(listed, g.flag_count + shard * kC3CounterStride, lane);
         if (listed) g.flag_idx[(size_t)shard * g.seg + slot] = (uint32_t)(row * g.nx + x0);
     }
-    // a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275)
+    // a sparse wave zero-fills its own slice of the change map (np.zeros, nd/_change.pyx:275).  Not zero_fill_span:
+    // that helper's 16-byte stores are non-temporal, these are plain ones -- another instruction, and which of the
+    // two is faster here has not been measured, so the text stays as it is.
     if (!dense && wnp > 0) {
         const int nb = wnp * k;
         int head = (int)((16 - ((uintptr_t)wob & 15)) & 15);
@@ -1197,17 +1161,9 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_kernel(const C3Args<T> s
     const unsigned first = s.dump != nullptr ? s.dump_cap : 0u;
     if (first >= n || lblock * (unsigned)LANES >= n - first) return;   // nothing for this block
     if (n <= s.starts_max) return;                        // a short list: omnibus_c3_search_starts_kernel's
-    // per-j constants of the screen as four LDS arrays behind the series image (omnibus.hip): every
-    // lane looks up its own j in every iteration
-    const int kp = k + 1;
-    double *scr = reinterpret_cast<double *>(nd_smem3 + (USE_LDS ? (size_t)k * 9 * LANES * sizeof(T) : 0));
-    for (int j = lane; j <= k; j += 64) {
-        const OmniTabEntry e = s.tab_dev[j];
-        scr[j] = e.m2rho;
-        scr[kp + j] = e.pklogk;
-        scr[2 * kp + j] = e.zlo_a;
-        scr[3 * kp + j] = e.zhi_a;
-    }
+    // per-j constants of the screen behind the series image
+    const ScreenLds scr = stage_screen(
+        reinterpret_cast<double *>(nd_smem3 + (USE_LDS ? (size_t)k * 9 * LANES * sizeof(T) : 0)), s.tab_dev, k, lane);
     __syncthreads();
 
     for (uint32_t base = first + lblock * (unsigned)LANES; base < n; base += nlblock * (unsigned)LANES) {
@@ -1317,7 +1273,8 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_kernel(const C3Args<T> s
             A.step(v);
         };
 
-        // one sweep per segment, as in omnibus_c2_search_kernel (nd/_change.pyx:235-257)
+        // one sweep per segment (nd/_change.pyx:235-257, omnibus_search.hpp).  The state of the sweep is spelled out:
+        // through Sweep the float32 image forms take two accumulation registers more (profiles/omnibus_search_codeobj.txt)
         Accum3<T> A;
         A.reset();
         int l = 0, t = 0, fire_at = -1;
@@ -1329,35 +1286,22 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_kernel(const C3Args<T> s
                 const int jj = t - l + 1;
                 const bool last = (t == k - 1);
                 const bool need = (jj >= 2) && (fire_at < 0 || last);
-                // screen on the hardware-log2 statistic; the exact evaluation sits behind a
-                // wave-uniform branch so that it is not folded into the loop body (omnibus.hip)
-                bool fires = false, inband = false;
-                if (need) {
-                    const double za = z_approx3<T>(A, jj, s.nlooks, scr[jj], scr[kp + jj]);
-                    fires = (za > scr[3 * kp + jj]) && (za < INFINITY);
-                    inband = (za >= scr[2 * kp + jj]) && !fires;
-                }
-                if (__any(inband)) {
-                    if (inband) {
-                        const OmniTabEntry e = s.tab_dev[jj];
-                        fires = exact_verdict<T>(z_stat3<T>(A, jj, s.nlooks, e), 9 * (jj - 1), e, s.alpha);
-                    }
-                }
+                const bool fires = test_f64(need, A, jj, s.nlooks, s.alpha, scr, s.tab_dev);
                 if (fires && fire_at < 0) fire_at = t;
                 if (!last) {
                     t = t + 1;
                 } else if (fires && jj >= 2) {
-                    res[fire_at] = 1;
-                    l = fire_at;
+                    res[fire_at] = 1;                          // :252
+                    l = fire_at;                               // :255
                     if (l >= k - 1) {
-                        done = true;
+                        done = true;                           // :256
                     } else {
                         A.reset();
                         t = l;
                         fire_at = -1;
                     }
                 } else {
-                    done = true;
+                    done = true;                               // :241-242
                 }
             }
         }
@@ -1372,9 +1316,8 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_kernel(const C3Args<T> s
 // sweep instead of 432 isolated values, and a second sweep of the same pixel finds them in the L2), no LDS but
 // the per-j constants, so that the occupancy is what the registers allow.  (The image form ran 16 pixels
 // per wave to fit five waves on a CU: three quarters of every vector instruction idle, 0.84 ms on config
-// 4's share with the dump as its source.)  The search itself is omnibus_c3_search_kernel's, step for step:
-// one sweep per segment (nd/_change.pyx:235-257), the hardware-log2 screen, the exact evaluation behind a
-// wave-uniform branch.
+// 4's share with the dump as its source.)  The search itself is omnibus_search.hpp's: one sweep per segment
+// (Sweep), the double screen and the exact evaluation behind a wave-uniform branch (test_f64).
 // MODE 0: the dump.  MODE 1 / 2 (round 6 as well): pixel-major inputs (nd_amd_omnibus_c3_pixel_major), where
 // a listed pixel's series is a contiguous run per variable in the caller's arrays -- nine real arrays (1) or
 // three real and three interleaved complex ones (2): the same chunks of four dates, one or two 16-byte
@@ -1401,7 +1344,6 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_dump_kernel(const C3Args
     constexpr int NV = CD * 9 / VE;                      // pieces per chunk
     typedef C3Pack<T, VE> PV;
     extern __shared__ __align__(16) unsigned char nd_smem3d[];
-    double *scr = reinterpret_cast<double *>(nd_smem3d);
     const int lane = threadIdx.x;
     const int k = s.k;
     const unsigned shard = blockIdx.x % kC3Shards;
@@ -1410,14 +1352,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_dump_kernel(const C3Args
     const uint32_t n = (MODE != 0 || nall < s.dump_cap) ? nall : s.dump_cap;
     const uint32_t *list = s.flag_idx + (size_t)shard * s.seg;
     if (lblock * 64u >= n) return;
-    const int kp = k + 1;
-    for (int j = lane; j <= k; j += 64) {
-        const OmniTabEntry e = s.tab_dev[j];
-        scr[j] = e.m2rho;
-        scr[kp + j] = e.pklogk;
-        scr[2 * kp + j] = e.zlo_a;
-        scr[3 * kp + j] = e.zhi_a;
-    }
+    const ScreenLds scr = stage_screen(reinterpret_cast<double *>(nd_smem3d), s.tab_dev, k, lane);
     __syncthreads();
 
     for (uint32_t base = lblock * 64u; base < n; base += nlblock * 64u) {
@@ -1431,8 +1366,8 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_dump_kernel(const C3Args
         const int64_t off = pix * (int64_t)k;              // (MODE 1 / 2: the pixel's run in every variable)
         Accum3<T> A;
         A.reset();
-        int l = 0, t = 0, fire_at = -1;
-        bool done = !active;
+        Sweep sw;
+        sw.begin(active);
         uint8_t *res = s.change + pix * (int64_t)k;
         // chunk `ci` of this lane's series into q (MODE 1 / 2: whole 16-byte pieces of dates, a piece behind
         // the series is not read)
@@ -1456,13 +1391,13 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_dump_kernel(const C3Args
         };
         // (reading the next chunk ahead into a second set of registers was built and measured slower:
         //  0.335 against 0.235 ms on config 4's share)
-        while (__any(!done)) {
-            const int ci = t / CD;                          // this lane's chunk (lanes restart at different dates)
+        while (__any(!sw.done)) {
+            const int ci = sw.t / CD;                       // this lane's chunk (lanes restart at different dates)
             PV q[NV];
-            if (!done) load_chunk(ci, q);
+            if (!sw.done) load_chunk(ci, q);
 #pragma unroll 1
             for (int tt = 0; tt < CD; ++tt) {
-                const bool on = !done && (t == ci * CD + tt);
+                const bool on = !sw.done && (sw.t == ci * CD + tt);
                 if (!__any(on)) continue;
                 T v[9];
                 // (tt is wave-uniform: a scalar switch over static positions, no indexed register access)
@@ -1481,37 +1416,14 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_dump_kernel(const C3Args
                 }
                 if (on) {
                     A.step(v);
-                    const int jj = t - l + 1;
-                    const bool last = (t == k - 1);
-                    const bool need = (jj >= 2) && (fire_at < 0 || last);
-                    bool fires = false, inband = false;
-                    if (need) {
-                        const double za = z_approx3<T>(A, jj, s.nlooks, scr[jj], scr[kp + jj]);
-                        fires = (za > scr[3 * kp + jj]) && (za < INFINITY);
-                        inband = (za >= scr[2 * kp + jj]) && !fires;
-                    }
-                    if (__any(inband)) {
-                        if (inband) {
-                            const OmniTabEntry e = s.tab_dev[jj];
-                            fires = exact_verdict<T>(z_stat3<T>(A, jj, s.nlooks, e), 9 * (jj - 1), e, s.alpha);
-                        }
-                    }
-                    if (fires && fire_at < 0) fire_at = t;
-                    if (!last) {
-                        t = t + 1;
-                    } else if (fires && jj >= 2) {
-                        res[fire_at] = 1;
-                        l = fire_at;
-                        if (l >= k - 1) {
-                            done = true;
-                        } else {
-                            A.reset();
-                            t = l;                          // (an earlier date: met again behind the next chunk load)
-                            fire_at = -1;
-                        }
-                    } else {
-                        done = true;
-                    }
+                    const int jj = sw.t - sw.l + 1;
+                    const bool last = (sw.t == k - 1);
+                    const bool fires = test_f64(sw.need(jj, last), A, jj, s.nlooks, s.alpha, scr, s.tab_dev);
+                    sw.note(fires, sw.t);
+                    if (!last)
+                        sw.t = sw.t + 1;
+                    else                                    // (t = l, an earlier date: met again behind the next chunk load)
+                        sw.commit(fires, k, A, [&](const int at) { res[at] = 1; });
                 }
             }
         }
@@ -1528,14 +1440,44 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_dump_kernel(const C3Args
 // per group of four dates (the next group in flight), every lane folding from its own segment start on; behind
 // the last date a lane commits the first firing date of its segment if the global test fired
 // (nd/_change.pyx:235-257, one sweep per segment) and starts its next segment there; rounds repeat while a lane
-// has a segment left.  Fold, screen and exact evaluation are omnibus_c3_search_kernel's, operation for operation.
+// has a segment left.  The rounds themselves are search_rounds of omnibus_search.hpp, shared with the dual-pol twin;
+// this unit adds how a lane's dates are read from its blocked dump (RoundsGroups).
 // The screen of a test is the float32 one of the dual-pol sweeps (x = log2 prod det - j log2 det(sum) relative to the
 // decision point, from exponents and the hardware log2 of the mantissas of the reference's own running values, against
 // the per-j band of make_dense_entry -- p-agnostic): whatever it cannot decide takes the exact evaluation.
+// this lane's series in a block of the dump, nine 16-byte pieces per group of four dates; the next group in flight
+template <typename T>
+struct RoundsGroups {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    static constexpr bool kGrouped = true;
+    const f4 *blk;                                       // group g, component c: blk[(g * 9 + c) * 64]
+    f4 cur[9], nxt[9];
+    __device__ __forceinline__ void prime(const int t0, int)
+    {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) nxt[c] = blk[((size_t)(t0 >> 2) * 9 + c) * 64];
+    }
+    __device__ __forceinline__ void group(const int tb, const int k)
+    {
+        const int gq = tb >> 2, gn = (k + 3) >> 2;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) cur[c] = nxt[c];
+        const int gq1 = gq + 1 < gn ? gq + 1 : gq;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) nxt[c] = blk[((size_t)gq1 * 9 + c) * 64];
+    }
+    __device__ __forceinline__ void fold(Accum3<T> &A, const int u, int, int, const bool on)
+    {
+        T v[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) v[c] = cur[c][u];
+        if (on) A.step(v);
+    }
+};
+
 template <typename T>
 __global__ void __launch_bounds__(64) omnibus_c3_search_rounds_kernel(const C3Args<T> s, const DenseScreen fscr)
 {
-    typedef float f4 __attribute__((ext_vector_type(4)));
     extern __shared__ __align__(16) unsigned char nd_smem3r[];
     DenseScreenEntry *scr_f = reinterpret_cast<DenseScreenEntry *>(nd_smem3r);
     const int lane = threadIdx.x;
@@ -1544,97 +1486,17 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_rounds_kernel(const C3Ar
     const unsigned lblock = blockIdx.x / kC3Shards, nlblock = gridDim.x / kC3Shards;
     const uint32_t nall = s.flag_count[shard * kC3CounterStride];
     const uint32_t n = nall < s.dump_cap ? nall : s.dump_cap;            // (dump_cap: a multiple of 64)
-    const uint32_t *list = s.flag_idx + (size_t)shard * s.seg;
     if (lblock * 64u >= n) return;
     for (int j = lane; j <= k; j += 64) scr_f[j] = fscr.e[j];
     __syncthreads();
     const unsigned G = s.dump_stride / 36u;
-
-    for (uint32_t base = lblock * 64u; base < n; base += nlblock * 64u) {
-        const uint32_t idx = base + lane;
-        const bool active = idx < n;
-        const int64_t pix = active ? (int64_t)list[idx] : 0;
-        // group g, component c of this lane's series: blk[(g * 9 + c) * 64]
-        const f4 *blk = reinterpret_cast<const f4 *>(s.dump) + ((size_t)shard * (s.dump_cap >> 6) + (base >> 6)) * G * 9 * 64 + lane;
-        uint8_t *res = s.change + pix * (int64_t)k;
-        Accum3<T> A;
-        A.reset();
-        int l = 0, fire_at = -1;
-        bool done = !active;
-        while (__any(!done)) {
-            int t0 = done ? k : l;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const int o = __shfl_xor(t0, off);
-                t0 = o < t0 ? o : t0;
-            }
-            t0 = __builtin_amdgcn_readfirstlane(t0);
-            const int g0 = t0 >> 2, gn = (k + 3) >> 2;
-            bool fires = false;                                  // of the test met at the last date: the global test
-            f4 cur[9], nxt[9];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) nxt[c] = blk[((size_t)g0 * 9 + c) * 64];
-            for (int gq = g0; gq < gn; ++gq) {
-#pragma unroll
-                for (int c = 0; c < 9; ++c) cur[c] = nxt[c];
-                const int gq1 = gq + 1 < gn ? gq + 1 : gq;
-#pragma unroll
-                for (int c = 0; c < 9; ++c) nxt[c] = blk[((size_t)gq1 * 9 + c) * 64];
-#pragma unroll
-                for (int tt = 0; tt < 4; ++tt) {
-                    const int t = 4 * gq + tt;                   // wave-uniform
-                    if (t < k && t >= t0) {
-                        T v[9];
-#pragma unroll
-                        for (int c = 0; c < 9; ++c) v[c] = cur[c][tt];
-                        const bool on = !done && t >= l;
-                        if (on) A.step(v);
-                        const int jj = t - l + 1;
-                        const bool last = (t == k - 1);
-                        const bool need = on && (jj >= 2) && (fire_at < 0 || last);
-                        bool f = false, inband = false;
-                        if (need) {
-                            const T dets = det3<T>(A.s);
-                            const bool ok = (dets > (T)0) & (dets < (T)INFINITY) & __builtin_amdgcn_class(A.prod, 0x100);
-                            const DenseScreenEntry c = scr_f[jj];
-                            int es, eP;
-                            float ms, mP;
-                            log2_parts(ok ? dets : (T)1, es, ms);
-                            log2_parts(ok ? A.prod : 1.0, eP, mP);
-                            const int E = (eP - c.re) - __mul24(jj, es);
-                            const float x = (float)E + __builtin_fmaf(-(float)jj, ms, mP - c.rf);
-                            f = ok & (x < c.a);
-                            inband = !(f | (ok & (x > c.b)));
-                        }
-                        if (__any(inband)) {
-                            if (inband) {
-                                const OmniTabEntry e = s.tab_dev[jj];
-                                f = exact_verdict<T>(z_stat3<T>(A, jj, s.nlooks, e), 9 * (jj - 1), e, s.alpha);
-                            }
-                        }
-                        if (need) {
-                            if (f && fire_at < 0) fire_at = t;
-                            if (last) fires = f;
-                        }
-                    }
-                }
-            }
-            if (!done) {
-                if (fires && (k - l) >= 2) {
-                    res[fire_at] = 1;                          // :252
-                    l = fire_at;                               // :255
-                    if (l >= k - 1) {
-                        done = true;                           // :256
-                    } else {
-                        A.reset();
-                        fire_at = -1;
-                    }
-                } else {
-                    done = true;                               // :241-242
-                }
-            }
-        }
-    }
+    search_rounds<Accum3<T>>(k, n, s.flag_idx + (size_t)shard * s.seg, lblock, nlblock, s.change, s.nlooks, s.alpha,
+                             scr_f, s.tab_dev, lane, [&](const uint32_t base) {
+                                 RoundsGroups<T> ld;
+                                 ld.blk = reinterpret_cast<const typename RoundsGroups<T>::f4 *>(s.dump) +
+                                          ((size_t)shard * (s.dump_cap >> 6) + (base >> 6)) * G * 9 * 64 + lane;
+                                 return ld;
+                             });
 }
 
 // ---- pass B, one lane per SEGMENT START (short lists behind the streaming search) ------------------
@@ -1652,7 +1514,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_starts_kernel(const C3Ar
     // the series of the wave's pixels (gathered once, every load of a pixel in flight together: the
     // sweeps then run without a memory access) and the per-j constants of the screen
     __shared__ T ser[9 * (kTabArgs + 2) + 9 * 64];
-    __shared__ double scr[4 * (kTabArgs + 1)];
+    __shared__ double scr_lds[4 * (kTabArgs + 1)];
     const int lane = threadIdx.x;
     const int k = s.k;
     const int ns = k - 1;                       // segment starts per pixel: 0 .. k - 2
@@ -1667,14 +1529,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_starts_kernel(const C3Ar
     if (n > s.starts_max) return;               // a long list: the gather-and-sweep form's
     if (lblock * (uint32_t)ppw >= n) return;
     const uint32_t *list = s.flag_idx + (size_t)shard * s.seg;
-    const int kp = k + 1;
-    for (int j = lane; j <= k; j += 64) {
-        const OmniTabEntry e = s.tab_dev[j];
-        scr[j] = e.m2rho;
-        scr[kp + j] = e.pklogk;
-        scr[2 * kp + j] = e.zlo_a;
-        scr[3 * kp + j] = e.zhi_a;
-    }
+    const ScreenLds scr = stage_screen(scr_lds, s.tab_dev, k, lane);      // (the barrier: in front of the gather below)
     for (uint32_t base = lblock * (uint32_t)ppw; base < n; base += nlblock * (uint32_t)ppw) {
         const uint32_t idx = base + (uint32_t)grp;
         const bool active = (grp < ppw) && (idx < n);
@@ -1686,14 +1541,15 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_starts_kernel(const C3Ar
         if (active)
             for (int e = l0; e < k * 9; e += nsw) mine[e] = s.pl[e % 9][(off + (int64_t)(e / 9) * s.st) * s.mult[e % 9]];
         __syncthreads();
-        int nxt_a = -1, nxt_b = -1;             // per sweep: the next segment start, or stop
+        int nxt[2] = {-1, -1};                  // per sweep: the next segment start, or stop
         for (int sweep = 0; sweep < nsweep; ++sweep) {
             const int l = l0 + 64 * sweep;
             const bool lact = active && l < ns;
             Accum3<T> A;
             A.reset();
-            int fire_at = -1;
-            int nxt = -1;                       // stop
+            Sweep sw;                           // (of the one segment this lane sweeps: l stays)
+            sw.begin(true);
+            int nx = -1;                        // stop
             for (int i = 0; i < k; ++i) {       // the lane's dates are l, l + 1, ...
                 const int t = l + i;
                 if (!__any(lact && t < k)) break;
@@ -1704,40 +1560,17 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_starts_kernel(const C3Ar
                 if (on) A.step(q);
                 const int jj = i + 1;
                 const bool last = (t == k - 1);
-                const bool need = on && (jj >= 2) && (fire_at < 0 || last);
-                bool fires = false, inband = false;
-                if (need) {
-                    const double za = z_approx3<T>(A, jj, s.nlooks, scr[jj], scr[kp + jj]);
-                    fires = (za > scr[3 * kp + jj]) && (za < INFINITY);
-                    inband = (za >= scr[2 * kp + jj]) && !fires;
-                }
-                if (__any(inband)) {
-                    if (inband) {
-                        const OmniTabEntry e = s.tab_dev[jj];
-                        fires = exact_verdict<T>(z_stat3<T>(A, jj, s.nlooks, e), 9 * (jj - 1), e, s.alpha);
-                    }
-                }
-                if (on && fires && fire_at < 0) fire_at = t;
-                if (on && last && fires) nxt = fire_at;      // the global test of ts[l:] fired (jj >= 2 here)
+                const bool need = on && sw.need(jj, last);
+                const bool fires = test_f64(need, A, jj, s.nlooks, s.alpha, scr, s.tab_dev);
+                sw.note(fires, t);
+                if (last && fires) nx = sw.fire_at;          // the global test of ts[l:] fired (jj >= 2 here)
             }
-            if (sweep == 0) nxt_a = nxt; else nxt_b = nxt;
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                if (sweep == u) nxt[u] = nx;
         }
-        // follow the chain from l = 0; the group's first lane writes the changes
-        int at = 0;
-        for (int step = 0; step < ns; ++step) {
-            const int ats = (at >= 0 && at < ns) ? at : 0;
-            const int src = grp * nsw + (ats & 63) % nsw;
-            const int na = __shfl(nxt_a, src), nb = __shfl(nxt_b, src);
-            const int n1 = (ns > 64 && ats >= 64) ? nb : na;
-            if (at >= 0 && at < ns) {
-                if (n1 < 0) {
-                    at = -1;                                   // :241-242
-                } else {
-                    if (active && l0 == 0) s.change[pix * (int64_t)k + n1] = 1;  // :252 (the row is all zeros)
-                    at = n1;                                   // :255; n1 = k - 1 ends the search (:256)
-                }
-            }
-        }
+        // follow the chain from l = 0; the group's first lane writes the changes (the row is all zeros)
+        follow_starts_chain<2>(nxt, ns, nsw, grp, active && l0 == 0, s.change + pix * (int64_t)k);
     }
 }
 

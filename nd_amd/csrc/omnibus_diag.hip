@@ -27,6 +27,7 @@
 // Every form evaluates a test the same way (diag_fires): the f32-log2 screen against zlo_a / zhi_a, and in
 // between the exact statistic and, inside [zlo, zhi], the chi-square pair.
 #include "omnibus_common.hpp"
+#include "omnibus_search.hpp"
 
 namespace nd_amd {
 
@@ -38,51 +39,7 @@ constexpr int kDgFusedBytes = 192;   // bytes of series per pixel up to which th
 constexpr double kDgFusedAlpha = 0.75;
 constexpr size_t kDgCounterBytes = (size_t)kDgShards * kDgCounterStride * sizeof(uint32_t);
 
-// ---- running state of one segment: the reference's sums and product --------------------------------
-template <typename T, int Q>
-struct DiagAccum {
-    T s[Q];
-    double prod;
-    __device__ __forceinline__ void reset()
-    {
-#pragma unroll
-        for (int c = 0; c < Q; ++c) s[c] = (T)0;
-        prod = 1.0;
-    }
-    __device__ __forceinline__ void step(const T (&v)[Q])
-    {
-        T det = v[0];
-#pragma unroll
-        for (int c = 1; c < Q; ++c) det = det * v[c];
-        prod = prod * (double)det;
-#pragma unroll
-        for (int c = 0; c < Q; ++c) s[c] = s[c] + v[c];
-    }
-    __device__ __forceinline__ T det_of_sum() const
-    {
-        T d = s[0];
-#pragma unroll
-        for (int c = 1; c < Q; ++c) d = d * s[c];
-        return d;
-    }
-};
-
-template <typename T, int Q>
-__device__ __forceinline__ T diag_z(const DiagAccum<T, Q> &A, int j, double nlooks, double m2rho, double pklogk)
-{
-    const T dets = A.det_of_sum();
-    const double logQ = nlooks * ((pklogk + log(A.prod)) - ((double)j * log((double)dets)));
-    return (T)(m2rho * logQ);
-}
-
-template <typename T, int Q>
-__device__ __forceinline__ double diag_z_approx(const DiagAccum<T, Q> &A, int j, double nlooks, double m2rho,
-                                                double pklogk)
-{
-    const T dets = A.det_of_sum();
-    const double logQ = nlooks * ((pklogk + approx_ln(A.prod)) - ((double)j * approx_ln((double)dets)));
-    return m2rho * logQ;
-}
+// (the running state DiagAccum<T, Q>, z_stat / z_approx over it and the table views: omnibus_search.hpp)
 
 // P of the test whose statistic is z.  chisq_pair's upper form sums Q(a, x) = t_{a-1} (1 + (a-1)/x + ...) over
 // the factors >= 1 and starts that sum at 1 -- right for every a >= 1, but at a = 1/2 (f = 1: one channel, two
@@ -113,62 +70,21 @@ __device__ __forceinline__ bool diag_verdict(const T z, const int a2, const Omni
     return verdict == 1;
 }
 
-// ---- the per-j table as the kernels read it ---------------------------------------------------------
-// in global memory, as the host built it
-struct DiagTabGlobal {
-    const OmniTabEntry *p;
-    __device__ __forceinline__ double m2rho(int j) const { return p[j].m2rho; }
-    __device__ __forceinline__ double pklogk(int j) const { return p[j].pklogk; }
-    __device__ __forceinline__ double zlo_a(int j) const { return p[j].zlo_a; }
-    __device__ __forceinline__ double zhi_a(int j) const { return p[j].zhi_a; }
-    __device__ __forceinline__ OmniTabEntry entry(int j) const { return p[j]; }
-};
-// the one entry pass A needs, from the kernel's arguments
-struct DiagTabOne {
-    const OmniTabEntry &e;
-    __device__ __forceinline__ double m2rho(int) const { return e.m2rho; }
-    __device__ __forceinline__ double pklogk(int) const { return e.pklogk; }
-    __device__ __forceinline__ double zlo_a(int) const { return e.zlo_a; }
-    __device__ __forceinline__ double zhi_a(int) const { return e.zhi_a; }
-    __device__ __forceinline__ OmniTabEntry entry(int) const { return e; }
-};
-// in LDS, field by field (lanes at different j read different banks): field f of entry j at p[f * kp + j],
-// f in the order of OmniTabEntry
-struct DiagTabLds {
-    const double *p;
-    int kp;
-    __device__ __forceinline__ double m2rho(int j) const { return p[j]; }
-    __device__ __forceinline__ double pklogk(int j) const { return p[kp + j]; }
-    __device__ __forceinline__ double zlo_a(int j) const { return p[5 * kp + j]; }
-    __device__ __forceinline__ double zhi_a(int j) const { return p[7 * kp + j]; }
-    __device__ __forceinline__ OmniTabEntry entry(int j) const
-    {
-        OmniTabEntry e;
-        e.m2rho = p[j];
-        e.pklogk = p[kp + j];
-        e.omega2 = p[2 * kp + j];
-        e.lgam = p[3 * kp + j];
-        e.zlo = p[4 * kp + j];
-        e.zlo_a = p[5 * kp + j];
-        e.zhi = p[6 * kp + j];
-        e.zhi_a = p[7 * kp + j];
-        return e;
-    }
-};
-
 // Does the test over the jj dates folded into A fire?  The screen first: z_approx is within aerr of the exact
 // double statistic (make_entry, omnibus_tables.hip), NaN or infinite exactly when that is; only between zlo_a and zhi_a the
-// exact statistic is formed and decided by zlo / zhi or the chi-square pair.
+// exact statistic is formed and decided by zlo / zhi or the chi-square pair.  (test_f64 of omnibus_search.hpp with
+// this family's own exact tail: diag_verdict for f = 1, the view's own copy of the full entry, and no wave-uniform
+// branch in front of it.)
 template <typename T, int Q, typename Tab>
 __device__ __forceinline__ bool diag_fires(const DiagAccum<T, Q> &A, const int jj, const double nlooks,
                                            const double alpha, const Tab &tab)
 {
-    const double za = diag_z_approx<T, Q>(A, jj, nlooks, tab.m2rho(jj), tab.pklogk(jj));
+    const double za = z_approx(A, jj, nlooks, tab.m2rho(jj), tab.pklogk(jj));
     bool fires = (za > tab.zhi_a(jj)) && (za < INFINITY);
     const bool inband = (za >= tab.zlo_a(jj)) && !fires;
     if (inband) {
         const OmniTabEntry e = tab.entry(jj);
-        fires = diag_verdict<T>(diag_z<T, Q>(A, jj, nlooks, e.m2rho, e.pklogk), Q * (jj - 1), e, alpha);
+        fires = diag_verdict<T>(z_stat(A, jj, nlooks, e.m2rho, e.pklogk), DiagAccum<T, Q>::kDof * (jj - 1), e, alpha);
     }
     return fires;
 }
@@ -182,6 +98,8 @@ template <typename T, int Q, typename Tab, typename Fetch, typename Fire>
 __device__ __forceinline__ void diag_search(const int k, const bool active, const double nlooks, const double alpha,
                                             const Tab &tab, Fetch fetch, Fire fire)
 {
+    // (spelled out, not through Sweep of omnibus_search.hpp: with it the fused and the search kernels spill one or
+    //  two scalar registers more -- profiles/omnibus_search_codeobj.txt)
     int l = 0;
     bool done = !active || k < 2;
     while (!done) {
@@ -271,7 +189,7 @@ __global__ void __launch_bounds__(kDgThreads) omnibus_diag_global_kernel(const D
 
     bool flag;
     if (STATS) {
-        const T z = diag_z<T, Q>(A, k, g.nlooks, g.e.m2rho, g.e.pklogk);
+        const T z = z_stat(A, k, g.nlooks, g.e.m2rho, g.e.pklogk);
         const T P = diag_P<T>(z, Q * (k - 1), g.e);
         flag = in && ((double)P > g.alpha);
         if (in) {
@@ -280,7 +198,7 @@ __global__ void __launch_bounds__(kDgThreads) omnibus_diag_global_kernel(const D
             if (g.p_out) g.p_out[pix] = P;
         }
     } else {
-        const DiagTabOne one{g.e};
+        const TabOne one{g.e};
         flag = in && diag_fires<T, Q>(A, k, g.nlooks, g.alpha, one);
     }
     flag = flag && k >= 2;                                    // a single date has no change to place
@@ -309,7 +227,7 @@ __global__ void __launch_bounds__(64) omnibus_diag_search_kernel(const DiagArgs<
     const unsigned lblock = blockIdx.x / kDgShards, nlblock = gridDim.x / kDgShards;
     const uint32_t n = s.flag_count[shard * kDgCounterStride];
     const uint32_t *list = s.flag_idx + (size_t)shard * s.seg;
-    const DiagTabGlobal tab{s.tab_dev};
+    const TabGlobal tab{s.tab_dev};
     for (uint32_t base = lblock * 64u; base < n; base += nlblock * 64u) {
         const uint32_t idx = base + (uint32_t)lane;
         const bool active = idx < n;
@@ -379,7 +297,7 @@ __global__ void __launch_bounds__(kDgThreads) omnibus_diag_fused_kernel(const Di
         }
     }
     __syncthreads();
-    const DiagTabLds tv{tl, kp};
+    const TabLds tv{tl, kp};
     auto fetch = [&](const int t, T(&v)[Q]) {
 #pragma unroll
         for (int c = 0; c < Q; ++c) v[c] = ser[(t * Q + c) * 64 + lane];
@@ -392,7 +310,7 @@ __global__ void __launch_bounds__(kDgThreads) omnibus_diag_fused_kernel(const Di
             fetch(t, v);
             A.step(v);
         }
-        const T z = diag_z<T, Q>(A, k, g.nlooks, g.e.m2rho, g.e.pklogk);
+        const T z = z_stat(A, k, g.nlooks, g.e.m2rho, g.e.pklogk);
         const T P = diag_P<T>(z, Q * (k - 1), g.e);
         if (in) {
             const int64_t pix = row * g.nx + x0;

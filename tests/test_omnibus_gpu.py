@@ -324,3 +324,39 @@ def test_long_series_sparse_regime(oracle, device, dtype, k):
             torch.cuda.synchronize()
             assert int((got.cpu().numpy() != want).sum()) == 0, (k, alpha, ws)
         assert want.sum() > 0
+
+
+@pytest.mark.parametrize('dtype,k,alpha', [(np.float32, 130, 0.01), (np.float64, 130, 0.01), (np.float32, 192, 0.01),
+                                           (np.float32, 12, 0.99), (np.float64, 12, 0.99)])
+def test_pass_b_one_lane_per_segment_start(oracle, device, dtype, k, alpha):
+    """omnibus_c2_search_starts_kernel where no other test takes it.  130 and 192 dates at a low threshold: 129 and
+    191 segment starts, three per lane (the streaming chain search hands over what its screen cannot vouch for).
+    12 dates in the sparse regime: behind the chain form of pass B, the pixels that form marked.  A raster of
+    30 x 90 pixels: short lists and a partial last wave in every shard.  The pixels the screens must hand over are
+    planted: nearly singular matrices (the rounding band of the determinant is too wide), series scaled so that the
+    product of the determinants leaves the screen's range but stays a normal double, and one pixel each that is not
+    positive definite, NaN at one date and zero throughout.  Change maps byte for byte."""
+    import torch
+    from nd_amd import kernels
+    ny, nx = 30, 90
+    planes = [p.copy() for p in synth.omnibus_stack(seed=900 + k, k=k, ny=ny, nx=nx, dtype=dtype, change_frac=0.3)]
+    planes[1][:, 3, 5:45] = 0.9995 * np.sqrt(planes[0][:, 3, 5:45] * planes[3][:, 3, 5:45])    # nearly singular
+    planes[2][:, 3, 5:45] = 0
+    for p in planes:
+        p[:, 7, 10:50] *= dtype(2.0 ** (-480.0 / k))           # product of k determinants: ~2^-960 of its own
+        p[:, 11, 10:50] *= dtype(2.0 ** (460.0 / k))
+    planes[1][:, 20, 17] *= 6.0                                # |C12|^2 > C11 C22
+    planes[0][k // 2, 21, 33] = np.nan
+    for p in planes:
+        p[:, 22, 44] = 0.0
+    yxt = [np.ascontiguousarray(np.moveaxis(p, 0, -1)) for p in planes]
+    dev = [torch.from_numpy(p).to(device) for p in planes]
+    with np.errstate(all='ignore'):
+        want = oracle.change_detection_planes(yxt, alpha, 9, njobs=8)
+    got = kernels.change_detection(*dev, alpha=alpha, n=9, dims=('time', 'y', 'x'))
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(got.cpu().numpy(), want)
+    # the planted pixels do change (nearly singular ones in the short series only: over 130 dates the product of
+    # their determinants underflows, z is infinite and the reference reports no change)
+    assert want[7, 10:50].any() and want[11, 10:50].any() and (k > 32 or want[3, 5:45].any())
+    assert not want[22, 44].any()
