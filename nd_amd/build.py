@@ -59,9 +59,10 @@ PER_FILE = {'nlmeans.hip': ['-fno-slp-vectorize'],
 # segment by wave-uniform index or from LDS, never through a private copy
 # change_segments.hip: a streaming walk over the dates; the sums, a chunk's loads and the carried means are
 # indexed statically
+# rasterize.hip: the crossing list lives in LDS and the kernels index nothing private at run time
 NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_', 'classify.hip': 'class',
               'kmeans_fit.hip': '_kernel', 'omnibus_diag.hip': 'omnibus_diag_',
-              'change_segments.hip': 'change_segments_kernel'}
+              'change_segments.hip': 'change_segments_kernel', 'rasterize.hip': 'rasterize_'}
 # bytes per lane by the kernel's template arguments <K, KMAX, STATS, CHAIN>, keyed (STATS, CHAIN)
 SCRATCH_BUDGET = {(False, False): 0, (False, True): 96, (True, False): 256, (True, True): 384}
 

@@ -1386,3 +1386,184 @@ def gather_rows(features, sizes, strides, index, mean=None, scale=None):
             _ptr(ws), ws.numel(), _stream_ptr(dev)))
         _record(list(features) + [index, mean, scale, ws], dev)
     return X, valid
+
+
+# ---------------------------------------------------------------------------
+# polygons burned into a label raster (nd/vector.py:48-187; include/nd_amd.h nd_amd_rasterize_polygons)
+# ---------------------------------------------------------------------------
+RASTERIZE_MAX_CROSSINGS = _lib.RASTERIZE_MAX_CROSSINGS
+# |pixel coordinate| the table accepts.  xc = x1 + ((v - y1) * (x2 - x1)) / (y2 - y1) with (v - y1) / (y2 - y1) in
+# [0, 1) lies within a few roundings of [x1, x2]: at most 4 * 2^-53 * 2^41 = 2^-10 pixel beyond it below this cap.  The
+# column box (the extent and one pixel beyond) may stand for the row only while that excess stays under a pixel.
+RASTERIZE_MAX_COORD = float(2 ** 40)
+_VALUE_DT = {torch.int64: _lib.I64, torch.float64: _lib.F64}
+
+
+def _offsets(a, name, last):
+    a = np.ascontiguousarray(np.asarray(a.cpu() if torch.is_tensor(a) else a), dtype=np.int64)
+    if a.ndim != 1 or a.size < 1 or a[0] != 0 or a[-1] != last or np.any(np.diff(a) < 0):
+        raise ValueError('%s must be non-decreasing int64 offsets from 0 to %d' % (name, last))
+    return a
+
+
+class PolygonTable:
+    """The polygons of one raster on the device -- pixel-coordinate vertices, ring and polygon offsets, and the
+    row / column boxes with the prefix sums of their rows -- uploaded once and shared by every
+    rasterize_polygons call (the columns and dates of one nd_amd.vector.rasterize)."""
+
+    def __init__(self, verts, ring_offsets, poly_offsets, ny, nx, device=None):
+        if torch.is_tensor(verts):
+            if not verts.is_cuda:
+                raise ValueError('verts must be a numpy array or live on a ROCm device (got %s); nd_amd has no '
+                                 'CPU path' % verts.device)
+            device = verts.device if device is None else device
+            host = verts.detach().cpu().numpy()
+        else:
+            host = np.asarray(verts)
+        host = np.ascontiguousarray(host, dtype=np.float64)
+        if host.size == 0:
+            host = host.reshape(0, 2)
+        if host.ndim != 2 or host.shape[1] != 2:
+            raise ValueError('verts must be (nverts, 2) pixel coordinates, got shape %s' % (host.shape,))
+        if not np.all(np.isfinite(host)):
+            raise ValueError('non-finite vertex coordinates')
+        if host.size and np.max(np.abs(host)) > RASTERIZE_MAX_COORD:
+            raise ValueError('pixel coordinates beyond 2^40 are not served (the crossing abscissa would no longer '
+                             'stay within a pixel of the polygon\'s extent)')
+        ny, nx = int(ny), int(nx)
+        if ny < 0 or nx < 0:
+            raise ValueError('negative raster size (%d, %d)' % (ny, nx))
+        if ny >= 2 ** 31 or nx >= 2 ** 31:
+            raise ValueError('raster sides of 2^31 pixels or more are not served')
+        ring_offsets = _offsets(ring_offsets, 'ring_offsets', host.shape[0])
+        poly_offsets = _offsets(poly_offsets, 'poly_offsets', ring_offsets.size - 1)
+        self.npolys = poly_offsets.size - 1
+        if self.npolys >= 2 ** 32 - 1:
+            raise ValueError('fewer than 2^32 - 1 polygons are served')
+        self.ny, self.nx = ny, nx
+        boxes, row_work = polygon_boxes(host, ring_offsets, poly_offsets, ny, nx)
+        self.items = int(row_work[-1])
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError('nd_amd needs a ROCm GPU: the compute path is HIP only')
+            device = torch.device('cuda', torch.cuda.current_device())
+        up = lambda a: torch.from_numpy(a).to(torch.device(device))
+        # one spare vertex keeps the table non-empty (and its pointer non-null) for polygons without vertices
+        self.verts = up(np.concatenate([host, np.zeros((1, 2))]))
+        self.ring_offsets, self.poly_offsets = up(ring_offsets), up(poly_offsets)
+        self.boxes, self.row_work = up(np.concatenate([boxes, np.zeros((1, 4), np.int32)])), up(row_work)
+        self.device = self.verts.device         # with its index, whatever form `device` had ('cuda', 'cuda:0')
+
+
+def polygon_boxes(verts, ring_offsets, poly_offsets, ny, nx):
+    """-> boxes int32 (npolys, 4) r0, r1, c0, c1 clipped to the raster, row_work int64 (npolys + 1) prefix sums of
+    r1 - r0.  A box holds every row i with ymin <= i + 0.5 <= ymax over the polygon's vertices (columns
+    likewise), and a pixel beyond.  A superset is all the kernel needs while the crossing abscissae stay within
+    a pixel of the extent, which RASTERIZE_MAX_COORD sees to: inside the box the rule decides."""
+    npolys = poly_offsets.size - 1
+    boxes = np.zeros((npolys, 4), np.int32)
+    v0 = ring_offsets[poly_offsets[:-1]]
+    v1 = ring_offsets[poly_offsets[1:]]
+    some = np.nonzero(v1 > v0)[0]
+    if some.size:
+        # reduceat over the non-empty polygons: their vertex ranges are consecutive and cover what lies between
+        starts = v0[some]
+        for col, (n, lo, hi) in enumerate(((nx, 2, 3), (ny, 0, 1))):
+            cmin = np.minimum.reduceat(verts[:, col], starts)
+            cmax = np.maximum.reduceat(verts[:, col], starts)
+            first = np.clip(np.floor(cmin - 0.5), 0, n)
+            end = np.clip(np.floor(cmax - 0.5) + 2, 0, n)
+            boxes[some, lo] = first.astype(np.int32)
+            boxes[some, hi] = np.maximum(first, end).astype(np.int32)
+    empty = (boxes[:, 1] <= boxes[:, 0]) | (boxes[:, 3] <= boxes[:, 2])
+    boxes[empty] = 0
+    row_work = np.zeros(npolys + 1, np.int64)
+    np.cumsum(boxes[:, 1].astype(np.int64) - boxes[:, 0], out=row_work[1:])
+    return boxes, row_work
+
+
+def rasterize_polygons(verts, ring_offsets, poly_offsets, values, ny, nx, layer=None, nlayers=1, fill=0, out=None):
+    """Burn polygons into a raster (include/nd_amd.h has the rule).  verts: (nverts, 2) float64 pixel coordinates
+    (px, py) as a numpy array or a ROCm tensor, with ring_offsets (nrings + 1) and poly_offsets (npolys + 1, into
+    the rings) -- or a PolygonTable built from them once, ring_offsets and poly_offsets then None.  The boxes and
+    the prefix sums of their rows are computed here on the host from those coordinates.  values: one per polygon,
+    integers (burned as int64) or floats (float64), a sequence, numpy array or ROCm tensor.  layer: npolys layer
+    numbers in [0, nlayers), None = all 0.  out: a ROCm tensor shaped (nlayers, ny, nx) of the values' type, any
+    non-negative strides (a permuted (ny, nx, nlayers) buffer gives the reference's (y, x, time) result without a
+    transpose); allocated contiguous when None.  -> out.  The value of a pixel is that of the highest-index polygon
+    of its layer that contains its centre, `fill` where there is none."""
+    for t, nm in ((verts, 'verts'), (values, 'values'), (layer, 'layer'), (out, 'out')):
+        if torch.is_tensor(t) and not t.is_cuda:
+            raise ValueError('%s must live on a ROCm device (got %s); nd_amd has no CPU path' % (nm, t.device))
+    ny, nx, nlayers = int(ny), int(nx), int(nlayers)
+    if nlayers < 0:
+        raise ValueError('nlayers must not be negative, got %d' % nlayers)
+    dev = next((t.device for t in (out, values, verts) if torch.is_tensor(t)), None)
+    if isinstance(verts, PolygonTable):
+        if ring_offsets is not None or poly_offsets is not None:
+            raise ValueError('a PolygonTable carries its offsets: pass ring_offsets=None, poly_offsets=None')
+        table = verts
+        if (table.ny, table.nx) != (ny, nx):
+            raise ValueError('the PolygonTable was built for a (%d, %d) raster, not (%d, %d)'
+                             % (table.ny, table.nx, ny, nx))
+    else:
+        table = PolygonTable(verts, ring_offsets, poly_offsets, ny, nx, device=dev)
+    dev = table.device
+    npolys = table.npolys
+    if ny * nx * nlayers >= 2 ** 32:
+        raise ValueError('rasters of 2^32 pixels x layers or more are not served (%d x %d x %d)' % (ny, nx, nlayers))
+
+    if torch.is_tensor(values):
+        vals = values
+        if vals.dtype not in _VALUE_DT:
+            vals = vals.to(torch.float64 if vals.is_floating_point() else torch.int64)
+    else:
+        host = np.asarray(values)
+        if host.dtype.kind in 'biu':
+            if host.dtype.kind == 'u' and host.size and host.max() > np.iinfo(np.int64).max:
+                raise ValueError('values beyond int64')
+            host = host.astype(np.int64)
+        elif host.dtype.kind == 'f':
+            host = host.astype(np.float64)
+        else:
+            raise TypeError('values must be integers or floats, got %s' % host.dtype)
+        vals = torch.from_numpy(np.ascontiguousarray(host)).to(dev)
+    if vals.dim() != 1 or vals.numel() != npolys or vals.device != dev:
+        raise ValueError('values must be one per polygon (%d) on %s, got shape %s on %s'
+                         % (npolys, dev, tuple(vals.shape), vals.device))
+    vals = vals.contiguous()
+
+    lay = None
+    if layer is not None:
+        host = np.asarray(layer.cpu() if torch.is_tensor(layer) else layer)
+        if host.shape != (npolys,) or (host.size and host.dtype.kind not in 'iu'):
+            raise ValueError('layer must be %d integers, one per polygon' % npolys)
+        if host.size and (host.min() < 0 or host.max() >= nlayers):
+            raise ValueError('layer numbers must lie in [0, %d)' % nlayers)
+        lay = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(dev) if host.size else None
+    elif npolys and nlayers < 1:
+        raise ValueError('polygons without a layer to burn them into')
+
+    shape = (nlayers, ny, nx)
+    if out is None:
+        with torch.cuda.device(dev):
+            out = torch.empty(shape, dtype=vals.dtype, device=dev)
+    else:
+        if tuple(out.shape) != shape or out.dtype != vals.dtype or out.device != dev:
+            raise ValueError('out must be %s of %s on %s, got %s of %s on %s'
+                             % (shape, vals.dtype, dev, tuple(out.shape), out.dtype, out.device))
+        if any(s == 0 and n > 1 for s, n in zip(out.stride(), shape)):
+            raise ValueError('an expanded out (stride 0) is not served')
+    fill_host = (C.c_int64(int(fill)) if vals.dtype == torch.int64 else C.c_double(float(fill)))
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = L.nd_amd_rasterize_workspace_bytes(nlayers, ny, nx)
+        ws = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        _lib.check(L.nd_amd_rasterize_polygons(
+            _ptr(table.verts), _ptr(table.ring_offsets), _ptr(table.poly_offsets), _ptr(lay), _ptr(table.row_work),
+            _ptr(table.boxes), _ptr(vals), _VALUE_DT[vals.dtype], C.cast(C.pointer(fill_host), C.c_void_p), npolys,
+            nlayers, ny, nx, _ptr(out), out.stride(0), out.stride(1), out.stride(2), _ptr(ws), int(nbytes),
+            _stream_ptr(dev)))
+        _record([table.verts, table.ring_offsets, table.poly_offsets, table.row_work, table.boxes, lay, vals, ws,
+                 out], dev)
+    return out

@@ -7,6 +7,9 @@ nd_amd/warp.py -- Coregistration (nd/warp.py:1104-1163) with the arithmetic on t
                   variable with the dimensions time, y and x translated by it (skimage.transform.warp,
                   bicubic, 0 outside, clipped to the plane's input range) -> nd_amd_warp_translate.
 
+  get_transform / get_resolution / get_bounds   the coordinate-based arithmetic of nd/warp.py:175-251 as plain
+                  tuples (no affine / rasterio objects): what nd_amd.vector.rasterize places its grid with.
+
 Reprojection, Resample and Alignment (GDAL wrappers) are not part of this package.  Arrays may be
 numpy (copied to the device and back) or torch ROCm tensors (the result stays on the device).
 """
@@ -18,7 +21,7 @@ from . import _adapter, _device, kernels
 from .algorithm import Algorithm, wrap_algorithm
 from .io import disassemble_complex
 
-__all__ = ['Coregistration', 'coregister']
+__all__ = ['Coregistration', 'coregister', 'get_transform', 'get_resolution', 'get_bounds']
 
 NAN_MESSAGE = ('NaN values found, please remove NaNs from your input data or use the '
                '`reference_mask`/`moving_mask` keywords, eg: phase_cross_correlation(reference_image, '
@@ -113,3 +116,64 @@ def _coregister(ds, reference, upsampling, ref_var='C11'):
 
 
 coregister = wrap_algorithm(Coregistration, 'coregister')
+
+
+# ---- the grid of a dataset, read off its x / y coordinates ----------------------------------------------------
+def _xy_coords(ds):
+    """the x and y coordinate arrays (float64) where the dataset has both with at least two entries, else None"""
+    coords = getattr(ds, 'coords', {})
+    if 'x' in coords and 'y' in coords:
+        x = np.asarray(getattr(coords['x'], 'values', coords['x']), dtype=np.float64)
+        y = np.asarray(getattr(coords['y'], 'values', coords['y']), dtype=np.float64)
+        if x.ndim == 1 and y.ndim == 1 and len(x) > 1 and len(y) > 1:
+            return x, y
+    return None
+
+
+def _attrs_transform(ds):
+    t = getattr(ds, 'attrs', {}).get('transform')
+    if t is None:
+        raise ValueError('the dataset has neither x / y coordinates (two or more each) nor attrs[\'transform\']')
+    t = tuple(float(v) for v in tuple(t)[:6])
+    if len(t) != 6:
+        raise ValueError("attrs['transform'] must hold the six terms (a, b, c, d, e, f), got %r" % (t,))
+    return t
+
+
+def get_transform(ds):
+    """The geographic transform of a dataset as the 6-tuple (a, b, c, d, e, f) of nd.warp.get_transform
+    (nd/warp.py:175-199): from the coordinates, a = (x[-1] - x[0]) / (len(x) - 1), c = x[0], e and f likewise
+    from y, b = d = 0 -- x[0] / y[0] taken as the corner of pixel (0, 0), as the reference passes it on.  Falls
+    back to attrs['transform']; ValueError without either."""
+    xy = _xy_coords(ds)
+    if xy is None:
+        return _attrs_transform(ds)
+    x, y = xy
+    resx = (x[-1] - x[0]) / (len(x) - 1)
+    resy = (y[-1] - y[0]) / (len(y) - 1)
+    return (float(resx), 0.0, float(x[0]), 0.0, float(resy), float(y[0]))
+
+
+def get_resolution(ds):
+    """(|a|, |e|): the pixel size along x and y in the units of the coordinates, as nd.warp.get_resolution
+    (nd/warp.py:202-224)."""
+    xy = _xy_coords(ds)
+    if xy is None:
+        t = _attrs_transform(ds)
+        return (abs(t[0]), abs(t[4]))
+    x, y = xy
+    return (float(abs(x[-1] - x[0]) / (len(x) - 1)), float(abs(y[-1] - y[0]) / (len(y) - 1)))
+
+
+def get_bounds(ds):
+    """(left, bottom, right, top) in the units of the coordinates: the smallest and largest x and y values, as
+    nd.warp.get_bounds
+    (nd/warp.py:227-251); from attrs['transform'] and the raster's size where there are no coordinates."""
+    xy = _xy_coords(ds)
+    if xy is not None:
+        x, y = xy
+        return (float(x.min()), float(y.min()), float(x.max()), float(y.max()))
+    a, _, c, _, e, f = _attrs_transform(ds)
+    nx, ny = int(ds.sizes['x']), int(ds.sizes['y'])
+    xs, ys = (c, c + a * nx), (f, f + e * ny)
+    return (min(xs), min(ys), max(xs), max(ys))

@@ -137,6 +137,16 @@ class DataArray:
             raise ValueError('dimensions %r do not exist' % sorted(unknown))
         return DataArray(self._data[tuple(idx)], dims, coords, self.attrs, self.name)
 
+    def squeeze(self, dim=None):
+        """drop the dimensions of length 1 (all of them, or the named one / ones) and their coordinates"""
+        names = self.dims if dim is None else ((dim,) if isinstance(dim, str) else tuple(dim))
+        for d in names:
+            if d not in self.dims:
+                raise ValueError('dimension %r does not exist' % (d,))
+            if dim is not None and self.sizes[d] != 1:
+                raise ValueError('cannot squeeze dimension %r of length %d' % (d, self.sizes[d]))
+        return self.isel(**{d: 0 for d in names if self.sizes[d] == 1})
+
     def equals(self, other):
         return (isinstance(other, DataArray) and self.dims == other.dims
                 and _equal(self._data, other._data))

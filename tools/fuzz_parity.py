@@ -1206,6 +1206,94 @@ def compare_c3(got, want, inp):
     return True
 
 
+# ---- rasterize: kernels.rasterize_polygons against tests/rasterize_ref.py ---------------------------------------------
+RASTER_LAYOUTS = ('lyx', 'yxl', 'pad')
+
+
+def gen_rasterize(rng):
+    """random polygon sets (stars, holes, half-integer snaps, combs around the crossing list's capacity, polygons
+    off the raster, empty ones), a random grid of either orientation, layers, value types and output strides"""
+    from tests import rasterize_cases as cases
+    ny, nx = draw_extent(rng, 70), draw_extent(rng, 130)
+    n = int(rng.choice([0, 1, 2, 5, 20, 40]))
+    polys = []
+    for k in range(n):
+        kind = rng.random()
+        if kind < 0.06:
+            crossings = int(rng.choice([cases.MAX_CROSSINGS - 2, cases.MAX_CROSSINGS, cases.MAX_CROSSINGS + 2,
+                                        2 * cases.MAX_CROSSINGS + 2]))
+            polys.append(cases.comb(crossings, x1=nx - 0.3 if (nx >= 40 and rng.random() < 0.5) else 39.7,
+                                    ytop=float(rng.uniform(0.7, ny + 1))))
+        elif kind < 0.1:
+            polys.append([] if rng.random() < 0.5 else [rng.uniform(0, nx, (2, 2))])
+        else:
+            g = cases.random_polygon(rng, ny, nx, hole=bool(rng.random() < 0.4), m=int(rng.choice([3, 4, 7, 12, 64, 65, 130])))
+            scale = float(rng.choice([0.1, 0.3, 1.0, 3.0]))
+            c = g[0].mean(0)
+            g = [c + (ring - c) * scale for ring in g]
+            polys.append([cases.snap(ring) for ring in g] if rng.random() < 0.2 else g)
+    # the grid: world = c + a * px, pixel coordinates come back through the bracketed division
+    a = float(rng.choice([1.0, -1.0, 10.0, -0.25, 1 / 3]))
+    e = float(rng.choice([1.0, -1.0, -10.0, 0.25, -1 / 3]))
+    c, f = float(rng.choice([0.0, 5e5, -37.3])), float(rng.choice([0.0, 4.2e6, 11.1]))
+    world = [[np.stack([c + a * r[:, 0], f + e * r[:, 1]], axis=1) for r in g] for g in polys]
+    nlayers = int(rng.choice([1, 1, 2, 3]))
+    layer = rng.integers(0, nlayers, n) if (nlayers > 1 or rng.random() < 0.3) else None
+    floats = bool(rng.random() < 0.5)
+    if floats:
+        values = rng.choice([np.nan, -0.0, 1.5, -2.25, np.inf, 1e-310, 3.0], n).astype(np.float64)
+        fill = float(rng.choice([0.0, -1.0, np.nan]))
+    else:
+        values = rng.choice([1, 2, 3, -7, 2 ** 53 + 1, -2 ** 62 - 1, 0], n).astype(np.int64)
+        fill = int(rng.choice([0, -1, 2 ** 40]))
+    layout = str(rng.choice(RASTER_LAYOUTS))
+    table = bool(rng.random() < 0.5)
+    desc = dict(ny=ny, nx=nx, n=n, a=a, e=e, c=c, f=f, nlayers=nlayers, layered=layer is not None, floats=floats,
+                fill=fill, layout=layout, table=table)
+    return dict(world=world, transform=(a, 0.0, c, 0.0, e, f), ny=ny, nx=nx, values=values, layer=layer,
+                nlayers=nlayers, fill=fill, layout=layout, table=table), desc
+
+
+def want_rasterize(inp):
+    from tests import rasterize_ref as R
+    polys = [[R.to_pixel(r, inp['transform']) for r in g] for g in inp['world']]
+    return dict(out=R.burn(polys, inp['values'], inp['ny'], inp['nx'], layer=inp['layer'], nlayers=inp['nlayers'],
+                           fill=inp['fill']))
+
+
+def run_rasterize(inp):
+    from nd_amd import vector
+    from tests import rasterize_ref as R
+    ny, nx, nl = inp['ny'], inp['nx'], inp['nlayers']
+    polys = [[vector._to_pixel(r, inp['transform']) for r in g] for g in inp['world']]
+    verts, ro, po = R.pack(polys)
+    dt = torch.float64 if inp['values'].dtype.kind == 'f' else torch.int64
+    if inp['layout'] == 'lyx':
+        base, out = None, None
+    elif inp['layout'] == 'yxl':
+        base = torch.full((ny, nx, nl), 77, dtype=dt, device=DEV)
+        out = base.permute(2, 0, 1)
+    else:
+        base = torch.full((nl, ny + 2, nx + 5), 77, dtype=dt, device=DEV)
+        out = base[:, 1:ny + 1, 3:nx + 3]
+    args = (kernels.PolygonTable(verts, ro, po, ny, nx, device=DEV), None, None) if inp['table'] else (verts, ro, po)
+    res = kernels.rasterize_polygons(*args, inp['values'], ny, nx, layer=inp['layer'], nlayers=nl, fill=inp['fill'],
+                                     out=out)
+    got = dict(out=host(res))
+    if inp['layout'] == 'pad':
+        frame = base.clone()
+        frame[:, 1:ny + 1, 3:nx + 3] = 77
+        got['untouched'] = np.asarray(bool((frame == 77).all()))
+    return got
+
+
+def compare_rasterize(got, want, inp):
+    """the same type, shape and bytes everywhere (no tolerance, no excluded pixels); nothing written around a view"""
+    g, w = np.ascontiguousarray(got['out']), want['out']
+    return bool(g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes()
+                and bool(got.get('untouched', True)))
+
+
 want_c3_more, run_c3_more, compare_c3_more = want_c3, run_c3, compare_c3
 
 
@@ -1223,7 +1311,7 @@ def newer_case(name):
 
 
 NEWER = ('omnibus_diag', 'change_segments', 'to_rgb', 'forest', 'kmeans_predict', 'knn', 'linear', 'kmeans_step', 'warp',
-         'c3_more')
+         'c3_more', 'rasterize')
 
 
 CASES = {'omnibus': case_omnibus, 'omnibus_long': case_omnibus_long, 'omnibus_ml': case_omnibus_ml, 'c3': newer_case('c3'),
