@@ -34,6 +34,15 @@ struct KernelTimer {
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Lets `kernel` be launched with `bytes` of dynamic LDS (a launch beyond 64 KB needs the attribute raised first).
+// It belongs to the CURRENT device's function object, so callers set it on every launch that needs it.
+template <class Kernel>
+static inline hipError_t allow_dynamic_lds(Kernel *kernel, size_t bytes)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)bytes);
+}
+
 // A library switch from the environment (README.md lists them all); `def` where it is unset.  Callers keep the
 // value in a `static const`: one look per process.
 static inline int env_int(const char *name, int def)

@@ -32,6 +32,7 @@
 // function has closed recurrences (chisq_pair in omnibus_common.hpp).
 #include <type_traits>
 
+#include "dispatch.hpp"
 #include "omnibus_c2_device.hpp"
 
 namespace nd_amd {
@@ -2821,6 +2822,15 @@ struct OmniWorkspace {
 };
 
 constexpr int kRetainMaxF32 = 48, kRetainMaxF64 = 24;
+// The series lengths (KMAX) a register form is instantiated for, by element type: the retaining pass A, the chain
+// form, and the dense kernel / the chain form of pass B.  A ladder over KMAX states its rule with `if constexpr`
+// on one of these.
+template <typename T>
+constexpr bool retain_has(int kmax) { return kmax <= (sizeof(T) == 4 ? kRetainMaxF32 : kRetainMaxF64); }
+template <typename T>
+constexpr bool chain_has(int kmax) { return kmax <= (sizeof(T) == 4 ? 32 : 24); }
+template <typename T>
+constexpr bool dense_has(int kmax) { return kmax <= (sizeof(T) == 4 ? 32 : 16); }
 
 constexpr size_t kCounterBytes = (size_t)kShards * kCounterStride * sizeof(uint32_t);
 
@@ -2864,56 +2874,38 @@ static OmniWorkspace omni_layout(int64_t npix, int64_t ny, int64_t k, size_t ele
     return w;
 }
 
+// the series of a pixel is addressable with a 32-bit buffer offset
+template <typename T>
+static bool series_fits_buffer(const OmniGlobalArgs<T> &g)
+{
+    return g.sx == 1 && (int64_t)g.k * g.st * (int64_t)sizeof(T) < 0x7fffffffLL && g.st >= 0;
+}
+
 template <typename T, int PPT>
 static void launch_global(const OmniGlobalArgs<T> &g, const OmniTab &tab, int64_t nblocks,
                           bool stats, hipStream_t stream)
 {
-    if (stats)
-        hipLaunchKernelGGL((omnibus_c2_global_kernel<T, PPT, true>), dim3((unsigned)nblocks),
+    pick(stats, [&](auto S) {
+        hipLaunchKernelGGL((omnibus_c2_global_kernel<T, PPT, decltype(S)::value>), dim3((unsigned)nblocks),
                            dim3(kGlobalThreads), 0, stream, g, tab);
-    else
-        hipLaunchKernelGGL((omnibus_c2_global_kernel<T, PPT, false>), dim3((unsigned)nblocks),
-                           dim3(kGlobalThreads), 0, stream, g, tab);
+    });
 }
 
-template <typename T, int KMAX>
-static void launch_retain_k(const OmniGlobalArgs<T> &g, const OmniTab &tab, int64_t nblocks,
-                            bool stats, hipStream_t stream)
+template <typename T>
+static void launch_retain(const OmniGlobalArgs<T> &g, const OmniTab &tab, int64_t nblocks,
+                          bool stats, hipStream_t stream)
 {
     const dim3 grid((unsigned)nblocks), block(kRetainThreads);
-    if (g.k == KMAX && g.sx == 1 &&
-        (int64_t)g.k * g.st * (int64_t)sizeof(T) < 0x7fffffffLL && g.st >= 0) {
-        if (stats)
-            hipLaunchKernelGGL((omnibus_c2_retain_kernel<T, KMAX, true, true>), grid, block, 0,
-                               stream, g, tab);
-        else
-            hipLaunchKernelGGL((omnibus_c2_retain_kernel<T, KMAX, true, false>), grid, block, 0,
-                               stream, g, tab);
-    } else {
-        if (stats)
-            hipLaunchKernelGGL((omnibus_c2_retain_kernel<T, KMAX, false, true>), grid, block, 0,
-                               stream, g, tab);
-        else
-            hipLaunchKernelGGL((omnibus_c2_retain_kernel<T, KMAX, false, false>), grid, block, 0,
-                               stream, g, tab);
-    }
-}
-
-template <typename T, int KMAX>
-static void launch_chain_k(const OmniGlobalArgs<T> &g, const OmniTab &tab, const StreamScreen<chain_nj(KMAX)> &ss,
-                           int64_t nblocks, hipStream_t stream, bool stats = false)
-{
-    const dim3 grid((unsigned)nblocks), block(kRetainThreads);
-    const bool exact = g.k == KMAX && g.sx == 1 && (int64_t)g.k * g.st * (int64_t)sizeof(T) < 0x7fffffffLL && g.st >= 0;
-    if (stats) {
-        if (exact)
-            hipLaunchKernelGGL((omnibus_c2_chain_kernel<T, KMAX, true, true>), grid, block, 0, stream, g, tab, ss);
-        else
-            hipLaunchKernelGGL((omnibus_c2_chain_kernel<T, KMAX, false, true>), grid, block, 0, stream, g, tab, ss);
-    } else if (exact)
-        hipLaunchKernelGGL((omnibus_c2_chain_kernel<T, KMAX, true>), grid, block, 0, stream, g, tab, ss);
-    else
-        hipLaunchKernelGGL((omnibus_c2_chain_kernel<T, KMAX, false>), grid, block, 0, stream, g, tab, ss);
+    pick_le<8, 16, 24, 32, 48>(g.k, [&](auto K) {
+        constexpr int KMAX = decltype(K)::value;
+        if constexpr (retain_has<T>(KMAX))
+            pick(g.k == KMAX && series_fits_buffer(g), [&](auto E) {
+                pick(stats, [&](auto S) {
+                    hipLaunchKernelGGL((omnibus_c2_retain_kernel<T, KMAX, decltype(E)::value, decltype(S)::value>),
+                                       grid, block, 0, stream, g, tab);
+                });
+            });
+    });
 }
 
 // k <= 32 (float) / 24 (double): the series lengths the chain form keeps in registers
@@ -2922,44 +2914,18 @@ static void launch_chain(const OmniGlobalArgs<T> &g, const OmniTab &tab, const s
                          const DenseScreen &scr, uint32_t n_looks, int64_t nblocks, hipStream_t stream,
                          bool stats = false)
 {
-    const int k = g.k;
-    if (sizeof(T) == 8 && k > 16) {
-        const StreamScreen<32> ss = make_stream_screen<T, 32>(htab, scr, k, n_looks);
-        launch_chain_k<double, 24>(reinterpret_cast<const OmniGlobalArgs<double> &>(g), tab, ss, nblocks, stream, stats);
-        return;
-    }
-    const StreamScreen<32> ss = make_stream_screen<T, 32>(htab, scr, k, n_looks);
-    if (k <= 8)
-        launch_chain_k<T, 8>(g, tab, ss, nblocks, stream, stats);
-    else if (k <= 16)
-        launch_chain_k<T, 16>(g, tab, ss, nblocks, stream, stats);
-    else if (sizeof(T) == 4) {
-        if (k <= 24)
-            launch_chain_k<float, 24>(reinterpret_cast<const OmniGlobalArgs<float> &>(g), tab, ss, nblocks, stream, stats);
-        else
-            launch_chain_k<float, 32>(reinterpret_cast<const OmniGlobalArgs<float> &>(g), tab, ss, nblocks, stream, stats);
-    }
-}
-
-template <typename T>
-static void launch_retain(const OmniGlobalArgs<T> &g, const OmniTab &tab, int64_t nblocks,
-                          bool stats, hipStream_t stream)
-{
-    const int k = g.k;
-    if (k <= 8)
-        launch_retain_k<T, 8>(g, tab, nblocks, stats, stream);
-    else if (k <= 16)
-        launch_retain_k<T, 16>(g, tab, nblocks, stats, stream);
-    else if (k <= 24)
-        launch_retain_k<T, 24>(g, tab, nblocks, stats, stream);
-    else if (sizeof(T) == 4) {
-        if (k <= 32)
-            launch_retain_k<float, 32>(reinterpret_cast<const OmniGlobalArgs<float> &>(g), tab,
-                                       nblocks, stats, stream);
-        else
-            launch_retain_k<float, 48>(reinterpret_cast<const OmniGlobalArgs<float> &>(g), tab,
-                                       nblocks, stats, stream);
-    }
+    const dim3 grid((unsigned)nblocks), block(kRetainThreads);
+    const StreamScreen<32> ss = make_stream_screen<T, 32>(htab, scr, g.k, n_looks);
+    pick_le<8, 16, 24, 32>(g.k, [&](auto K) {
+        constexpr int KMAX = decltype(K)::value;
+        if constexpr (chain_has<T>(KMAX))
+            pick(g.k == KMAX && series_fits_buffer(g), [&](auto E) {
+                pick(stats, [&](auto S) {
+                    hipLaunchKernelGGL((omnibus_c2_chain_kernel<T, KMAX, decltype(E)::value, decltype(S)::value>),
+                                       grid, block, 0, stream, g, tab, ss);
+                });
+            });
+    });
 }
 
 // ND_AMD_SEARCH_FS=0: the sweeps of pass B screen a test with z_approx in double, as before round 6, instead of the
@@ -3193,16 +3159,11 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         const DenseScreen scr = make_dense_screen<T>(htab, (int)k, n_looks);
         const StreamScreen<32> ssd = make_stream_screen<T, 32>(htab, scr, (int)k, n_looks);
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_DENSE, sq);
-        if (k <= 8)
-            hipLaunchKernelGGL((omnibus_c2_dense_kernel<T, 8>), gridd, blockd, 0, sq, d, ssd);
-        else if (k <= 16)
-            hipLaunchKernelGGL((omnibus_c2_dense_kernel<T, 16>), gridd, blockd, 0, sq, d, ssd);
-        else if (sizeof(T) == 4 && k <= 24)
-            hipLaunchKernelGGL((omnibus_c2_dense_kernel<float, 24>), gridd, blockd, 0, sq,
-                               reinterpret_cast<const OmniDenseArgs<float> &>(d), ssd);
-        else if (sizeof(T) == 4)
-            hipLaunchKernelGGL((omnibus_c2_dense_kernel<float, 32>), gridd, blockd, 0, sq,
-                               reinterpret_cast<const OmniDenseArgs<float> &>(d), ssd);
+        pick_le<8, 16, 24, 32>((int)k, [&](auto K) {
+            constexpr int KMAX = decltype(K)::value;
+            if constexpr (dense_has<T>(KMAX))
+                hipLaunchKernelGGL((omnibus_c2_dense_kernel<T, KMAX>), gridd, blockd, 0, sq, d, ssd);
+        });
     };
     const bool low_threshold = fused || stream_long || ml_chain || (pm_ids != nullptr && alpha < fused_alpha && !exact_flags);
     auto launch_search = [&](hipStream_t sq, const uint32_t *count, const uint32_t *idx, const T *dump,
@@ -3249,20 +3210,24 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             fscr.e[j].b = INFINITY;
             if (fs && j >= 1 && j <= (int)k) fscr.e[j] = make_dense_entry<T>(htab[(size_t)j], j, n_looks);
         }
-        if (use_lds && lds_bytes > 64 * 1024) {
-            ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c2_search_kernel<T, 0, 64, false>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c2_search_kernel<T, 0, 64, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        }
-// the sweep kernel with or without the float32 screen
-#define ND_LAUNCH_SWEEP(MODE_, PXW_, GRID_, LDS_)                                                                  \
-    do {                                                                                                          \
-        if (fs)                                                                                                   \
-            hipLaunchKernelGGL((omnibus_c2_search_kernel<T, MODE_, PXW_, true>), GRID_, dim3(64), LDS_, sq, s, fscr);  \
-        else                                                                                                      \
-            hipLaunchKernelGGL((omnibus_c2_search_kernel<T, MODE_, PXW_, false>), GRID_, dim3(64), LDS_, sq, s, fscr); \
-    } while (0)
+        // an image beyond 64 KB: both forms of the image sweep of that width, without and with the float32 screen
+        auto allow_image_lds = [](auto PXW, size_t bytes) -> hipError_t {
+            hipError_t e = hipSuccess;
+            for (const bool with_fs : {false, true})
+                pick(with_fs, [&](auto FS) {
+                    if (e == hipSuccess)
+                        e = allow_dynamic_lds(&omnibus_c2_search_kernel<T, 0, decltype(PXW)::value, decltype(FS)::value>, bytes);
+                });
+            return e;
+        };
+        if (use_lds && lds_bytes > 64 * 1024) ND_HIP_CHECK(allow_image_lds(int_c<64>{}, lds_bytes));
+        // the sweep kernel with or without the float32 screen
+        auto launch_sweep = [&](auto MODE, auto PXW, dim3 grid, size_t lds) {
+            pick(fs, [&](auto FS) {
+                hipLaunchKernelGGL((omnibus_c2_search_kernel<T, decltype(MODE)::value, decltype(PXW)::value, decltype(FS)::value>),
+                                   grid, dim3(64), lds, sq, s, fscr);
+            });
+        };
         // kShards x (blocks per shard); a shard's blocks stride through its list
         int64_t per_shard = ceil_div(ceil_div(npix_listed, kShards), 64);
         if (per_shard > 64) per_shard = 64;
@@ -3301,16 +3266,11 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             s.hand_bits = hand;
             const StreamScreen<32> ss0 = make_stream_screen<T, 32>(htab, scr, (int)k, n_looks);
             const dim3 gr((unsigned)sblocks), bl(64);
-            if (k <= 8)
-                hipLaunchKernelGGL((omnibus_c2_search_chain_kernel<T, 8>), gr, bl, 0, sq, s, ss0);
-            else if (k <= 16)
-                hipLaunchKernelGGL((omnibus_c2_search_chain_kernel<T, 16>), gr, bl, 0, sq, s, ss0);
-            else if (sizeof(T) == 4 && k <= 24)
-                hipLaunchKernelGGL((omnibus_c2_search_chain_kernel<float, 24>), gr, bl, 0, sq,
-                                   reinterpret_cast<const OmniSearchArgs<float> &>(s), ss0);
-            else if (sizeof(T) == 4)
-                hipLaunchKernelGGL((omnibus_c2_search_chain_kernel<float, 32>), gr, bl, 0, sq,
-                                   reinterpret_cast<const OmniSearchArgs<float> &>(s), ss0);
+            pick_le<8, 16, 24, 32>((int)k, [&](auto K) {
+                constexpr int KMAX = decltype(K)::value;
+                if constexpr (dense_has<T>(KMAX))
+                    hipLaunchKernelGGL((omnibus_c2_search_chain_kernel<T, KMAX>), gr, bl, 0, sq, s, ss0);
+            });
         }
         // the exact form: every listed pixel, or (behind a register form) the marked ones
         KernelTimer timer((chain_form || starts_form) ? ND_AMD_KERNEL_OMNIBUS_EXACT : ND_AMD_KERNEL_OMNIBUS_SEARCH, sq);
@@ -3343,7 +3303,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             }
             hipLaunchKernelGGL((omnibus_c2_search_rounds_kernel<T>), dim3((unsigned)sblocks), dim3(64), (size_t)(k + 1) * sizeof(DenseScreenEntry), sq, s, fscr);
             s.first = dump_cap;
-            ND_LAUNCH_SWEEP(1, 64, dim3((unsigned)sblocks), scr_bytes);
+            launch_sweep(int_c<1>{}, int_c<64>{}, dim3((unsigned)sblocks), scr_bytes);
             return ND_AMD_OK;
         }
         // images beyond 48 KB (three waves per CU or fewer at 64 series per wave): 16 series per wave
@@ -3356,26 +3316,17 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             if (ps > 256) ps = 256;
             if (ps < 1) ps = 1;
             const dim3 gn((unsigned)(ps * kShards));
-#define ND_LAUNCH_PXW(P)                                                                                   \
-    do {                                                                                                  \
-        if (lds_n > 64 * 1024) {                                                                          \
-            ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c2_search_kernel<T, 0, P, false>), \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_n));    \
-            ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c2_search_kernel<T, 0, P, true>), \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_n));    \
-        }                                                                                                 \
-        ND_LAUNCH_SWEEP(0, P, gn, lds_n);                                                                 \
-    } while (0)
-            if (pxw == 32)
-                ND_LAUNCH_PXW(32);
-            else
-                ND_LAUNCH_PXW(16);      // (8 per wave measured the same: the gather's sector traffic bounds it)
-#undef ND_LAUNCH_PXW
+            hipError_t e = hipSuccess;
+            pick_eq<32, 16>(pxw, [&](auto P) {      // (8 per wave measured the same: the gather's sector traffic bounds it)
+                if (lds_n > 64 * 1024) e = allow_image_lds(P, lds_n);
+                if (e == hipSuccess) launch_sweep(int_c<0>{}, P, gn, lds_n);
+            });
+            ND_HIP_CHECK(e);
             return ND_AMD_OK;
         }
         const dim3 gx((unsigned)xblocks);
         if (mode == 0 && use_lds) {
-            ND_LAUNCH_SWEEP(0, 64, gx, lds_bytes);
+            launch_sweep(int_c<0>{}, int_c<64>{}, gx, lds_bytes);
             return ND_AMD_OK;
         }
         // MODE 1 stages only the screen constants, 32 (k + 1) bytes: up to 64 KB (k <= 2046) as they are, up to
@@ -3387,17 +3338,15 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             hipError_t e = hipGetDevice(&dev);
             if (e == hipSuccess) e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
             if (e == hipSuccess && scr_bytes <= (size_t)lds_max) {
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c2_search_kernel<T, 1, 64, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)scr_bytes);
+                e = allow_dynamic_lds(&omnibus_c2_search_kernel<T, 1, 64, false>, scr_bytes);
                 scr_lds = (e == hipSuccess);
             }
             if (e != hipSuccess) (void)hipGetLastError();   // a refused attribute is no failure: the global form serves
         }
         if (scr_lds)
-            ND_LAUNCH_SWEEP(1, 64, gx, scr_bytes);
+            launch_sweep(int_c<1>{}, int_c<64>{}, gx, scr_bytes);
         else
             hipLaunchKernelGGL((omnibus_c2_search_kernel<T, 1, 64, false, true>), gx, dim3(64), 0, sq, s, fscr);
-#undef ND_LAUNCH_SWEEP
         return ND_AMD_OK;
     };
 
@@ -3471,24 +3420,14 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         g.dump_cap = 0;                          // nothing is dumped: pass B reads the series where they lie
         const dim3 gridw((unsigned)ceil_div(npix, (int64_t)pxw)), blockw(64);
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
-#define ND_LAUNCH_PM_LONG(PXW_)                                                                               \
-    do {                                                                                                      \
-        if (stats_a && joint)                                                                                   \
-            hipLaunchKernelGGL((omnibus_c2_pm_long_kernel<T, PXW_, true, true>), gridw, blockw, lds_long, stream, g, tab, dm);   \
-        else if (stats_a)                                                                                       \
-            hipLaunchKernelGGL((omnibus_c2_pm_long_kernel<T, PXW_, true, false>), gridw, blockw, lds_long, stream, g, tab, dm);  \
-        else if (joint)                                                                                       \
-            hipLaunchKernelGGL((omnibus_c2_pm_long_kernel<T, PXW_, false, true>), gridw, blockw, lds_long, stream, g, tab, dm);  \
-        else                                                                                                  \
-            hipLaunchKernelGGL((omnibus_c2_pm_long_kernel<T, PXW_, false, false>), gridw, blockw, lds_long, stream, g, tab, dm); \
-    } while (0)
-        if (pxw == 64)
-            ND_LAUNCH_PM_LONG(64);
-        else if (pxw == 32)
-            ND_LAUNCH_PM_LONG(32);
-        else
-            ND_LAUNCH_PM_LONG(16);
-#undef ND_LAUNCH_PM_LONG
+        pick_eq<64, 32, 16>(pxw, [&](auto P) {
+            pick(stats_a, [&](auto S) {
+                pick(joint, [&](auto J) {
+                    hipLaunchKernelGGL((omnibus_c2_pm_long_kernel<T, decltype(P)::value, decltype(S)::value, decltype(J)::value>),
+                                       gridw, blockw, lds_long, stream, g, tab, dm);
+                });
+            });
+        });
     } else if (pm_ids != nullptr) {
         if (!flat) {
             set_error("nd_amd_omnibus_c2_pixel_major: the variables must be contiguous");
@@ -3557,22 +3496,16 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
                     dd.img_off[1] = 0;
                     dd.img_off[2] = 64 * (int)k * dd.ids[1];
                     const size_t lds_c12 = (size_t)64 * k * (dd.ids[1] + (dd.c12_joint ? 0 : dd.ids[2])) * sizeof(T);
-                    if (k <= 8)
-                        hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, 8, false, true, true>), gridw, blockw, lds_c12, stream, g, tab, dd, ss0);
-                    else if (k <= 16)
-                        hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, 16, false, true, true>), gridw, blockw, lds_c12, stream, g, tab, dd, ss0);
-                    else
-                        hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, 24, false, true, true>), gridw, blockw, lds_c12, stream, g, tab, dd, ss0);
+                    pick_le<8, 16, 24>((int)k, [&](auto K) {
+                        hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, decltype(K)::value, false, true, true>), gridw, blockw, lds_c12, stream, g, tab, dd, ss0);
+                    });
                 } else
                 if ((fused_form_pm == 2 || (fused_form_pm != 0 && alpha > 0.02) || !kvec) && k <= 24) {
                     // dense_chain behind the LDS-DMA staging: the form for the thresholds in between (and, at every
                     // low threshold, for the series lengths that are not a multiple of the vector)
-                    if (k <= 8)
-                        hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, 8, false, true>), gridw, blockw, lds_dma, stream, g, tab, dm, ss0);
-                    else if (k <= 16)
-                        hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, 16, false, true>), gridw, blockw, lds_dma, stream, g, tab, dm, ss0);
-                    else
-                        hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, 24, false, true>), gridw, blockw, lds_dma, stream, g, tab, dm, ss0);
+                    pick_le<8, 16, 24>((int)k, [&](auto K) {
+                        hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, decltype(K)::value, false, true>), gridw, blockw, lds_dma, stream, g, tab, dm, ss0);
+                    });
                 } else
                 if (pm_lds)
                     hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, 2, 2>), gridw, blockw, lds_dma, stream, g, tab, dm, ss0);
@@ -3589,20 +3522,11 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
             StreamScreen<32> ss_unused;
             memset(&ss_unused, 0, sizeof(ss_unused));
-#define ND_LAUNCH_DMA(KM)                                                                              \
-    do {                                                                                              \
-        if (stats_a)                                                                                  \
-            hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, KM, true>), gridw, blockw, lds_dma, stream, g, tab, dm, ss_unused);  \
-        else                                                                                          \
-            hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, KM, false>), gridw, blockw, lds_dma, stream, g, tab, dm, ss_unused); \
-    } while (0)
-            if (k <= 8)
-                ND_LAUNCH_DMA(8);
-            else if (k <= 16)
-                ND_LAUNCH_DMA(16);
-            else
-                ND_LAUNCH_DMA(24);
-#undef ND_LAUNCH_DMA
+            pick_le<8, 16, 24>((int)k, [&](auto K) {
+                pick(stats_a, [&](auto S) {
+                    hipLaunchKernelGGL((omnibus_c2_pm_dma_kernel<T, decltype(K)::value, decltype(S)::value>), gridw, blockw, lds_dma, stream, g, tab, dm, ss_unused);
+                });
+            });
             }
             g.gate_mode = 0;
         } else {
@@ -3614,24 +3538,15 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         }
         const dim3 grid((unsigned)nblocks), block(kRetainThreads);
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
-#define ND_LAUNCH_PM(KM)                                                                              \
-    do {                                                                                              \
-        if (stats_a)                                                                                  \
-            hipLaunchKernelGGL((omnibus_c2_retain_pm_kernel<T, KM, true>), grid, block, lds, stream, g, tab, pm);  \
-        else                                                                                          \
-            hipLaunchKernelGGL((omnibus_c2_retain_pm_kernel<T, KM, false>), grid, block, lds, stream, g, tab, pm); \
-    } while (0)
-        if (k <= 8)
-            ND_LAUNCH_PM(8);
-        else if (k <= 16)
-            ND_LAUNCH_PM(16);
-        else if (k <= 24)
-            ND_LAUNCH_PM(24);
-        else {
+        const bool launched = pick_le<8, 16, 24>((int)k, [&](auto K) {
+            pick(stats_a, [&](auto S) {
+                hipLaunchKernelGGL((omnibus_c2_retain_pm_kernel<T, decltype(K)::value, decltype(S)::value>), grid, block, lds, stream, g, tab, pm);
+            });
+        });
+        if (!launched) {
             set_error("nd_amd_omnibus_c2_pixel_major: at most 24 dates");
             return ND_AMD_EUNSUPPORTED;
         }
-#undef ND_LAUNCH_PM
         }
     } else if (fused) {
         // z / P rasters asked for on top (fused_stats): the chain form evaluates them from the series it
@@ -3682,11 +3597,9 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             OmniPmDmaArgs<T> nopm;
             memset(&nopm, 0, sizeof(nopm));
             const StreamScreen<32> ss0 = make_stream_screen<T, 32>(htab, scr, (int)k, n_looks);
-            const bool buf1 = g.sx == 1 && (int64_t)g.k * g.st * (int64_t)sizeof(T) < 0x7fffffffLL && g.st >= 0;
-            if (buf1)
-                hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, 1>), grid, block, 0, stream, g, tab, nopm, ss0);
-            else
-                hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, 0>), grid, block, 0, stream, g, tab, nopm, ss0);
+            pick(series_fits_buffer(g), [&](auto B) {
+                hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, decltype(B)::value ? 1 : 0>), grid, block, 0, stream, g, tab, nopm, ss0);
+            });
         }
         }
         if (gated) {
@@ -3735,7 +3648,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             constexpr int PF = sizeof(T) == 4 ? 6 : 4;
             OmniPmDmaArgs<T> nopm;
             memset(&nopm, 0, sizeof(nopm));
-            const bool buf = g.sx == 1 && (int64_t)g.k * g.st * (int64_t)sizeof(T) < 0x7fffffffLL && g.st >= 0;
+            const bool buf = series_fits_buffer(g);
             const int fused_form_long = fused_form_env();
             // float64 series of 17 .. 24 dates still fit the registers (as 32 float32 dates do): the
             // chain form.  (33 .. 48 float32 dates: that instantiation spilled 2 KB per lane under the
@@ -3763,47 +3676,32 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
                     ss3.e[j].mj = (float)j * 1.01f;
                     ss3.e[j].pad = 0.f;
                 }
-                if (stats_long_chain) {
-                    if (buf) hipLaunchKernelGGL((omnibus_c2_stream_chain_kernel<T, PF, 1, 3, true>), grid, block, 0, stream, g, tab, ss3);
-                    else hipLaunchKernelGGL((omnibus_c2_stream_chain_kernel<T, PF, 0, 3, true>), grid, block, 0, stream, g, tab, ss3);
-                } else {
-                    if (buf) hipLaunchKernelGGL((omnibus_c2_stream_chain_kernel<T, PF, 1, 3, false>), grid, block, 0, stream, g, tab, ss3);
-                    else hipLaunchKernelGGL((omnibus_c2_stream_chain_kernel<T, PF, 0, 3, false>), grid, block, 0, stream, g, tab, ss3);
-                }
+                pick(buf, [&](auto B) {
+                    pick(stats_long_chain, [&](auto S) {
+                        hipLaunchKernelGGL((omnibus_c2_stream_chain_kernel<T, PF, decltype(B)::value ? 1 : 0, 3, decltype(S)::value>), grid, block, 0, stream, g, tab, ss3);
+                    });
+                });
             } else if (stats_long_chain || fused_form_long == 3 || (fused_form_long < 0 && alpha > 0.02)) {
                 // longer series between the streaming search's thresholds and the sparse regime: the
                 // chain search in two streaming passes (ND_AMD_FUSED_FORM=3 forces it, 0 the one-pass form)
-#define ND_LAUNCH_SCHAIN(MODE_, MW_, NJ_)                                                                         \
-    do {                                                                                                          \
-        if (stats_long_chain)                                                                                     \
-            hipLaunchKernelGGL((omnibus_c2_stream_chain_kernel<T, PF, MODE_, MW_, true>), grid, block, 0, stream, g, tab, \
-                               make_stream_screen<T, NJ_>(htab, scr, (int)k, n_looks));                           \
-        else                                                                                                      \
-            hipLaunchKernelGGL((omnibus_c2_stream_chain_kernel<T, PF, MODE_, MW_, false>), grid, block, 0, stream, g, tab, \
-                               make_stream_screen<T, NJ_>(htab, scr, (int)k, n_looks));                           \
-    } while (0)
-                if (k <= 32) {
-                    if (buf) ND_LAUNCH_SCHAIN(1, 0, 32);
-                    else ND_LAUNCH_SCHAIN(0, 0, 32);
-                } else if (k <= 64) {
-                    if (buf) ND_LAUNCH_SCHAIN(1, 1, 64);
-                    else ND_LAUNCH_SCHAIN(0, 1, 64);
-                } else {
-                    if (buf) ND_LAUNCH_SCHAIN(1, 2, 128);
-                    else ND_LAUNCH_SCHAIN(0, 2, 128);
-                }
-#undef ND_LAUNCH_SCHAIN
+                // (masks of MW + 1 words: a screen of 32, 64 or 128 dates)
+                pick_le<32, 64, 128>((int)k, [&](auto NJ) {
+                    constexpr int NJ_ = decltype(NJ)::value, MW = NJ_ / 64;
+                    pick(buf, [&](auto B) {
+                        pick(stats_long_chain, [&](auto S) {
+                            hipLaunchKernelGGL((omnibus_c2_stream_chain_kernel<T, PF, decltype(B)::value ? 1 : 0, MW, decltype(S)::value>), grid, block, 0, stream, g, tab,
+                                               make_stream_screen<T, NJ_>(htab, scr, (int)k, n_looks));
+                        });
+                    });
+                });
             } else
-            if (k <= 32) {
-                if (buf) hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, 1, 0>), grid, block, 0, stream, g, tab, nopm, make_stream_screen<T, 32>(htab, scr, (int)k, n_looks));
-                else hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, 0, 0>), grid, block, 0, stream, g, tab, nopm, make_stream_screen<T, 32>(htab, scr, (int)k, n_looks));
-            } else if (k <= 64) {
-                if (buf) hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, 1, 1>), grid, block, 0, stream, g, tab, nopm, make_stream_screen<T, 64>(htab, scr, (int)k, n_looks));
-                else hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, 0, 1>), grid, block, 0, stream, g, tab, nopm, make_stream_screen<T, 64>(htab, scr, (int)k, n_looks));
-            } else {
-                if (buf) hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, 1, 2>), grid, block, 0, stream, g, tab, nopm, make_stream_screen<T, 128>(htab, scr, (int)k, n_looks));
-                else hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, 0, 2>), grid, block, 0, stream, g, tab, nopm, make_stream_screen<T, 128>(htab, scr, (int)k, n_looks));
-            }
+                pick_le<32, 64, 128>((int)k, [&](auto NJ) {
+                    constexpr int NJ_ = decltype(NJ)::value, MW = NJ_ / 64;
+                    pick(buf, [&](auto B) {
+                        hipLaunchKernelGGL((omnibus_c2_stream_kernel<T, PF, decltype(B)::value ? 1 : 0, MW>), grid, block, 0, stream, g, tab, nopm,
+                                           make_stream_screen<T, NJ_>(htab, scr, (int)k, n_looks));
+                    });
+                });
             g.blocks_per_row = bpr_keep;
         }
         g.dense_min = 65;                           // no register search at these lengths
@@ -3824,37 +3722,27 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         // rounding band of the re-associated sums: 3 (5 k + 8) u (see the kernel), u = half an ulp of T
         const float rel = 3.f * (5.f * (float)k + 8.f) * (sizeof(T) == 4 ? 5.9604645e-08f : 1.1102230e-16f);
         const dim3 grid((unsigned)nbs);
-#define ND_LAUNCH_SPLIT(TT_, KQ_, NS_)                                                                         \
-    do {                                                                                                       \
-        if (stats)                                                                                             \
-            hipLaunchKernelGGL((omnibus_c2_split_kernel<TT_, KQ_, NS_, true>), grid, dim3(64 * NS_), 0, stream, \
-                               reinterpret_cast<const OmniGlobalArgs<TT_> &>(g), tab, rel);                     \
-        else                                                                                                   \
-            hipLaunchKernelGGL((omnibus_c2_split_kernel<TT_, KQ_, NS_, false>), grid, dim3(64 * NS_), 0, stream, \
-                               reinterpret_cast<const OmniGlobalArgs<TT_> &>(g), tab, rel);                     \
-    } while (0)
+        // NS waves of a block, each with KQ dates of its pixels in registers
+        auto launch_split = [&](auto KQ, auto NS) {
+            constexpr int NS_ = decltype(NS)::value;
+            pick(stats, [&](auto S) {
+                hipLaunchKernelGGL((omnibus_c2_split_kernel<T, decltype(KQ)::value, NS_, decltype(S)::value>), grid, dim3(64 * NS_), 0, stream,
+                                   g, tab, rel);
+            });
+        };
         if constexpr (std::is_same<T, float>::value) {
-            // 4 KQ registers per lane: four waves up to 96 dates, eight beyond
+            // 4 KQ registers per lane: four waves up to 96 dates, eight beyond; 16, 20 or 24 dates per wave
             const int ns = k <= 96 ? 4 : 8;
-            const int kqc = (int)ceil_div(k, ns);
-            const int kq = kqc <= 16 ? 16 : (kqc <= 20 ? 20 : 24);
-            if (ns == 4) {
-                if (kq <= 16) ND_LAUNCH_SPLIT(float, 16, 4);
-                else if (kq == 20) ND_LAUNCH_SPLIT(float, 20, 4);
-                else ND_LAUNCH_SPLIT(float, 24, 4);
-            } else {
-                if (kq == 16) ND_LAUNCH_SPLIT(float, 16, 8);
-                else if (kq == 20) ND_LAUNCH_SPLIT(float, 20, 8);
-                else ND_LAUNCH_SPLIT(float, 24, 8);
-            }
+            pick_eq<4, 8>(ns, [&](auto NS) {
+                pick_le<16, 20, 24>((int)ceil_div(k, ns), [&](auto KQ) { launch_split(KQ, NS); });
+            });
         } else {
-            // float64 (25 .. 96 dates): 8 KQ registers per lane -- 8 or 12 dates per wave
-            if (k <= 32) ND_LAUNCH_SPLIT(double, 8, 4);
-            else if (k <= 48) ND_LAUNCH_SPLIT(double, 12, 4);
-            else if (k <= 64) ND_LAUNCH_SPLIT(double, 8, 8);
-            else ND_LAUNCH_SPLIT(double, 12, 8);
+            // float64 (25 .. 96 dates): 8 KQ registers per lane -- 8 or 12 dates per wave, four waves up to 48 dates
+            const int ns = k <= 48 ? 4 : 8;
+            pick_eq<4, 8>(ns, [&](auto NS) {
+                pick_le<8, 12>((int)ceil_div(k, ns), [&](auto KQ) { launch_split(KQ, NS); });
+            });
         }
-#undef ND_LAUNCH_SPLIT
     } else {
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
         if (retain)

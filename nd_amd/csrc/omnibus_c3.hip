@@ -22,6 +22,7 @@
 // chi-square pair handles both (omnibus_common.hpp).
 #include <type_traits>
 
+#include "dispatch.hpp"
 #include "omnibus_common.hpp"
 #include "omnibus_search.hpp"
 
@@ -1633,12 +1634,10 @@ static int c3_launch_retain(const C3Workspace &w, C3Args<float> &g, const OmniTa
         return ND_AMD_EUNSUPPORTED;
     }
     const dim3 grid((unsigned)nblocks), block((unsigned)(64 * kC3Slices));
-    switch (w.kq) {
-    case 4: hipLaunchKernelGGL((omnibus_c3_retain_kernel<4>), grid, block, 0, stream, g, tab); break;
-    case 8: hipLaunchKernelGGL((omnibus_c3_retain_kernel<8>), grid, block, 0, stream, g, tab); break;
-    case 12: hipLaunchKernelGGL((omnibus_c3_retain_kernel<12>), grid, block, 0, stream, g, tab); break;
-    default: hipLaunchKernelGGL((omnibus_c3_retain_kernel<16>), grid, block, 0, stream, g, tab); break;
-    }
+    // (w.kq is a multiple of 4, at most 16 where c3_retain_ok holds)
+    pick_le<4, 8, 12, 16>(w.kq, [&](auto KQ) {
+        hipLaunchKernelGGL((omnibus_c3_retain_kernel<decltype(KQ)::value>), grid, block, 0, stream, g, tab);
+    });
     return ND_AMD_OK;
 }
 
@@ -1748,24 +1747,14 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
         const size_t lds_pm = (size_t)off * sizeof(T);
         const dim3 gridw((unsigned)ceil_div(npix, (int64_t)pxw)), blockw(64);
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
-#define ND_C3_PM(PXW_)                                                                                       \
-    do {                                                                                                     \
-        if (stats && joint)                                                                                  \
-            hipLaunchKernelGGL((omnibus_c3_pm_kernel<T, PXW_, true, true>), gridw, blockw, lds_pm, stream, g, tab, pa);   \
-        else if (stats)                                                                                      \
-            hipLaunchKernelGGL((omnibus_c3_pm_kernel<T, PXW_, true, false>), gridw, blockw, lds_pm, stream, g, tab, pa);  \
-        else if (joint)                                                                                      \
-            hipLaunchKernelGGL((omnibus_c3_pm_kernel<T, PXW_, false, true>), gridw, blockw, lds_pm, stream, g, tab, pa);  \
-        else                                                                                                 \
-            hipLaunchKernelGGL((omnibus_c3_pm_kernel<T, PXW_, false, false>), gridw, blockw, lds_pm, stream, g, tab, pa); \
-    } while (0)
-        if (pxw == 64)
-            ND_C3_PM(64);
-        else if (pxw == 32)
-            ND_C3_PM(32);
-        else
-            ND_C3_PM(16);
-#undef ND_C3_PM
+        pick_eq<64, 32, 16>(pxw, [&](auto P) {
+            pick(stats, [&](auto S) {
+                pick(joint, [&](auto J) {
+                    hipLaunchKernelGGL((omnibus_c3_pm_kernel<T, decltype(P)::value, decltype(S)::value, decltype(J)::value>),
+                                       gridw, blockw, lds_pm, stream, g, tab, pa);
+                });
+            });
+        });
     } else
     if (!fused && !stats && !exact_flags && c3_retain_ok<T>(w, g)) {
         // the sparse design with the candidates' series handed over from registers (omnibus_c3_retain_kernel)
@@ -1775,12 +1764,10 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     if (!fused || stats) {
         // the sparse design -- or, with a fused search, only the z / P rasters of it
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
-        if (stats || exact_flags)
-            hipLaunchKernelGGL((omnibus_c3_global_kernel<T, true>), dim3((unsigned)nblocks),
+        pick(stats || exact_flags, [&](auto S) {
+            hipLaunchKernelGGL((omnibus_c3_global_kernel<T, decltype(S)::value>), dim3((unsigned)nblocks),
                                dim3(kC3Threads), 0, stream, g, tab);
-        else
-            hipLaunchKernelGGL((omnibus_c3_global_kernel<T, false>), dim3((unsigned)nblocks),
-                               dim3(kC3Threads), 0, stream, g, tab);
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     if (fused) {
@@ -1792,25 +1779,18 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
         // the chain search in two streaming passes above alpha = 0.02 (where marginal tests over four and more
         // dates stop being rare), the streaming search below; speed only
         const bool chain = k >= 3 && alpha > 0.02;
-        if (k <= 64) {
-            StreamScreen<64> ss = make_stream_screen<T, 64>(htab, scr, (int)k, n_looks);
-            for (int j = 0; j <= 64; ++j) ss.e[j].cj = cu3 * (21.f * (float)j + 20.f);
+        // (masks of MW words: a screen of 64 or 128 dates)
+        pick_le<64, 128>((int)k, [&](auto NJ) {
+            constexpr int NJ_ = decltype(NJ)::value, MW = NJ_ / 64;
+            StreamScreen<NJ_> ss = make_stream_screen<T, NJ_>(htab, scr, (int)k, n_looks);
+            for (int j = 0; j <= NJ_; ++j) ss.e[j].cj = cu3 * (21.f * (float)j + 20.f);
             if (chain)
-                hipLaunchKernelGGL((omnibus_c3_stream_chain_kernel<T, 1>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
+                hipLaunchKernelGGL((omnibus_c3_stream_chain_kernel<T, MW>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
                                    stream, g, tab, ss, kDenseMin);
             else
-                hipLaunchKernelGGL((omnibus_c3_stream_kernel<T, 1>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
+                hipLaunchKernelGGL((omnibus_c3_stream_kernel<T, MW>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
                                    stream, g, tab, scr, ss, kDenseMin);
-        } else {
-            StreamScreen<kDenseMax> ss = make_stream_screen<T, kDenseMax>(htab, scr, (int)k, n_looks);
-            for (int j = 0; j <= kDenseMax; ++j) ss.e[j].cj = cu3 * (21.f * (float)j + 20.f);
-            if (chain)
-                hipLaunchKernelGGL((omnibus_c3_stream_chain_kernel<T, 2>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
-                                   stream, g, tab, ss, kDenseMin);
-            else
-                hipLaunchKernelGGL((omnibus_c3_stream_kernel<T, 2>), dim3((unsigned)nblocks), dim3(kC3Threads), 0,
-                                   stream, g, tab, scr, ss, kDenseMin);
-        }
+        });
         ND_HIP_CHECK(hipGetLastError());
     }
 
@@ -1835,8 +1815,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     // traffic of its gather, not by the occupancy the image costs.
     const bool use_lds = lds_bytes <= 150 * 1024;
     if (use_lds && lds_bytes > 64 * 1024) {
-        ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c3_search_kernel<T, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        ND_HIP_CHECK(allow_dynamic_lds(&omnibus_c3_search_kernel<T, true>, lds_bytes));
     }
     int64_t per_shard = ceil_div(ceil_div(npix, kC3Shards), 64);
     if (per_shard > 64) per_shard = 64;
@@ -1870,10 +1849,9 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
         if (per_shard_d > 64) per_shard_d = 64;
         if (per_shard_d < 1) per_shard_d = 1;
         const dim3 gridd((unsigned)(per_shard_d * kC3Shards));
-        if (g.mult[3] == 2)
-            hipLaunchKernelGGL((omnibus_c3_search_dump_kernel<T, 2>), gridd, dim3(64), scr_bytes, stream, g);
-        else
-            hipLaunchKernelGGL((omnibus_c3_search_dump_kernel<T, 1>), gridd, dim3(64), scr_bytes, stream, g);
+        pick(g.mult[3] == 2, [&](auto C) {      // interleaved complex arrays, or nine real ones
+            hipLaunchKernelGGL((omnibus_c3_search_dump_kernel<T, decltype(C)::value ? 2 : 1>), gridd, dim3(64), scr_bytes, stream, g);
+        });
         ND_HIP_CHECK(hipGetLastError());
     } else
     {
@@ -1885,17 +1863,14 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
             if (per_shard_h > 256) per_shard_h = 256;
             if (per_shard_h < 1) per_shard_h = 1;
             const dim3 gridh((unsigned)(per_shard_h * kC3Shards));
-            if (lanes == 16) {
-                if (lds_part > 64 * 1024)
-                    ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c3_search_kernel<T, true, 16>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_part));
-                hipLaunchKernelGGL((omnibus_c3_search_kernel<T, true, 16>), gridh, dim3(64), lds_part, stream, g);
-            } else {
-                if (lds_part > 64 * 1024)
-                    ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&omnibus_c3_search_kernel<T, true, 32>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_part));
-                hipLaunchKernelGGL((omnibus_c3_search_kernel<T, true, 32>), gridh, dim3(64), lds_part, stream, g);
-            }
+            hipError_t e = hipSuccess;
+            pick_eq<16, 32>(lanes, [&](auto L) {
+                constexpr int LANES = decltype(L)::value;
+                if (lds_part > 64 * 1024) e = allow_dynamic_lds(&omnibus_c3_search_kernel<T, true, LANES>, lds_part);
+                if (e == hipSuccess)
+                    hipLaunchKernelGGL((omnibus_c3_search_kernel<T, true, LANES>), gridh, dim3(64), lds_part, stream, g);
+            });
+            ND_HIP_CHECK(e);
         } else if (use_lds)
             hipLaunchKernelGGL((omnibus_c3_search_kernel<T, true>), dim3((unsigned)sblocks), dim3(64),
                                lds_bytes, stream, g);

@@ -26,6 +26,7 @@
 //       the series from the planes -- any k.
 // Every form evaluates a test the same way (diag_fires): the f32-log2 screen against zlo_a / zhi_a, and in
 // between the exact statistic and, inside [zlo, zhi], the chi-square pair.
+#include "dispatch.hpp"
 #include "omnibus_common.hpp"
 #include "omnibus_search.hpp"
 
@@ -410,10 +411,9 @@ static int omnibus_diag_impl(const void *const planes[], int64_t ny, int64_t nx,
     if (fused) {
         const size_t lds = (size_t)(k + 1) * sizeof(OmniTabEntry) + (size_t)k * Q * kDgThreads * sizeof(T);
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_FUSED, stream);
-        if (stats)
-            hipLaunchKernelGGL((omnibus_diag_fused_kernel<T, Q, true>), grid, block, lds, stream, g, tab);
-        else
-            hipLaunchKernelGGL((omnibus_diag_fused_kernel<T, Q, false>), grid, block, lds, stream, g, tab);
+        pick(stats, [&](auto S) {
+            hipLaunchKernelGGL((omnibus_diag_fused_kernel<T, Q, decltype(S)::value>), grid, block, lds, stream, g, tab);
+        });
         ND_HIP_CHECK(hipGetLastError());
         return ND_AMD_OK;
     }
@@ -421,10 +421,9 @@ static int omnibus_diag_impl(const void *const planes[], int64_t ny, int64_t nx,
     ND_HIP_CHECK(hipMemsetAsync(g.flag_count, 0, kDgCounterBytes, stream));
     {
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
-        if (stats)
-            hipLaunchKernelGGL((omnibus_diag_global_kernel<T, Q, true>), grid, block, 0, stream, g, tab);
-        else
-            hipLaunchKernelGGL((omnibus_diag_global_kernel<T, Q, false>), grid, block, 0, stream, g, tab);
+        pick(stats, [&](auto S) {
+            hipLaunchKernelGGL((omnibus_diag_global_kernel<T, Q, decltype(S)::value>), grid, block, 0, stream, g, tab);
+        });
         ND_HIP_CHECK(hipGetLastError());
     }
     if (k >= 2) {
@@ -444,14 +443,13 @@ static int omnibus_diag_q(int nch, const void *const planes[], int64_t ny, int64
                           int64_t sx, int64_t st, double n_looks, double alpha, uint8_t *change, void *z_out,
                           void *p_out, void *workspace, size_t workspace_bytes, hipStream_t stream)
 {
-    if (nch == 1)
-        return omnibus_diag_impl<T, 1>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out, workspace,
-                                       workspace_bytes, stream);
-    if (nch == 2)
-        return omnibus_diag_impl<T, 2>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out, workspace,
-                                       workspace_bytes, stream);
-    return omnibus_diag_impl<T, 3>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out, workspace,
-                                   workspace_bytes, stream);
+    // (the entry point admits one to three channels)
+    int rc = ND_AMD_EINVAL;
+    pick_eq<1, 2, 3>(nch, [&](auto Q) {
+        rc = omnibus_diag_impl<T, decltype(Q)::value>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out,
+                                                      workspace, workspace_bytes, stream);
+    });
+    return rc;
 }
 
 }  // namespace nd_amd

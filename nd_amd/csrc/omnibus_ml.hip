@@ -44,6 +44,7 @@
 // Traffic: 4 k planes x (12 + 2h) / 12 rows, nothing else.  Work: w^2 dependent double additions per
 // value (scipy's order leaves no sharing between neighbouring windows) -- vector issue, not memory,
 // is what bounds the kernel.
+#include "dispatch.hpp"
 #include "omnibus_ml_common.hpp"
 
 namespace nd_amd {
@@ -537,25 +538,19 @@ static int launch_ml_k(const OmniGlobalArgs<float> &g, const OmniTab &tab, const
     const dim3 grid((unsigned)nblocks), block(M::NT);
     StreamScreen<32> none;
     if (!ss) memset(&none, 0, sizeof(none));
-#define ND_ML_LAUNCH(STATS_, CHAIN_)                                                                          \
-    do {                                                                                                      \
-        /* on every launch: the attribute belongs to the CURRENT device's function object (one thread */     \
-        /* per device in algorithm.parallel(devices=...)), and a failure must not go unnoticed */            \
-        ND_HIP_CHECK(hipFuncSetAttribute(                                                                     \
-            reinterpret_cast<const void *>(&omnibus_c2_ml_kernel<K, KMAX, STATS_, CHAIN_>),                   \
-            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                           \
-        hipLaunchKernelGGL((omnibus_c2_ml_kernel<K, KMAX, STATS_, CHAIN_>), grid, block, lds, stream, g, tab, a, \
-                           ss ? *ss : none);                                                                  \
-    } while (0)
-    if (ss && stats)
-        ND_ML_LAUNCH(true, true);
-    else if (ss)
-        ND_ML_LAUNCH(false, true);
-    else if (stats)
-        ND_ML_LAUNCH(true, false);
-    else
-        ND_ML_LAUNCH(false, false);
-#undef ND_ML_LAUNCH
+    hipError_t e = hipSuccess;
+    pick(stats, [&](auto S) {
+        pick(ss != nullptr, [&](auto C) {
+            constexpr bool STATS = decltype(S)::value, CHAIN = decltype(C)::value;
+            // on every launch: the attribute belongs to the CURRENT device's function object (one thread
+            // per device in algorithm.parallel(devices=...)), and a failure must not go unnoticed
+            e = allow_dynamic_lds(&omnibus_c2_ml_kernel<K, KMAX, STATS, CHAIN>, lds);
+            if (e == hipSuccess)
+                hipLaunchKernelGGL((omnibus_c2_ml_kernel<K, KMAX, STATS, CHAIN>), grid, block, lds, stream, g, tab, a,
+                                   ss ? *ss : none);
+        });
+    });
+    ND_HIP_CHECK(e);
     return ND_AMD_OK;
 }
 
@@ -575,21 +570,14 @@ int launch_ml_pass_a(const OmniGlobalArgs<float> &g, const OmniTab &tab, const O
     a.spx = a.nstrips = 0;
     a.trace = nullptr;
     a.trace_block = 1000;
-    const int k = g.k;
-#define ND_ML_K(KK)                                                                       \
-    do {                                                                                  \
-        if (k <= 8)                                                                       \
-            return launch_ml_k<KK, 8>(g, tab, a, ss, stats, p.nblocks, stream);           \
-        else if (k <= 16)                                                                 \
-            return launch_ml_k<KK, 16>(g, tab, a, ss, stats, p.nblocks, stream);          \
-        else                                                                              \
-            return launch_ml_k<KK, 24>(g, tab, a, ss, stats, p.nblocks, stream);          \
-    } while (0)
-    if (p.ml == 3)
-        ND_ML_K(3);
-    else
-        ND_ML_K(5);
-#undef ND_ML_K
+    // (omni_ml_plan admits ml = 3 or 5 and 2 <= k <= 24)
+    int rc = ND_AMD_EUNSUPPORTED;
+    pick_eq<3, 5>(p.ml, [&](auto ML) {
+        pick_le<8, 16, 24>(g.k, [&](auto KMAX) {
+            rc = launch_ml_k<decltype(ML)::value, decltype(KMAX)::value>(g, tab, a, ss, stats, p.nblocks, stream);
+        });
+    });
+    return rc;
 }
 
 }  // namespace nd_amd

@@ -39,6 +39,23 @@ def test_c3_against_generic_oracle(oracle, device, dtype, k, alpha):
 
 
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('k', [4, 8, 9, 13, 17, 32, 49])
+def test_c3_retain_boundaries(oracle, device, dtype, k):
+    """The series lengths around the bounds of the time-split pass A's instantiations that the tests above and
+    test_c3_sparse_regime_degenerate_values (5, 12, 16, 33, 48, 64) leave out: 4 | 5, 8 | 9, 12 | 13 and 16 | 17 dates,
+    and 32 | 33, 48 | 49, where a slice's share passes 8 and 12 dates.  Sparse regime, with and without the rasters
+    (_run asks for both; float32 without them takes the time-split form), 24 x 323 pixels: ragged last block and wave."""
+    planes = synth.omnibus_stack_c3(seed=70 + k, k=k, ny=24, nx=323, dtype=dtype, change_frac=0.15)
+    yxt = [np.ascontiguousarray(np.moveaxis(p, 0, -1)) for p in planes]
+    want, z0, P0 = oracle.change_detection_pol(yxt, 3, 0.9, 9, njobs=8, stats=True)
+    ch, z, P = _run(planes, 0.9, 9, device)
+    assert int((ch != want).sum()) == 0
+    np.testing.assert_allclose(z, z0, rtol=1e-5, equal_nan=True)
+    np.testing.assert_allclose(P, P0, rtol=1e-5, atol=1e-30, equal_nan=True)
+    assert 0 < want.sum() < want.size
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
 @pytest.mark.parametrize('k', [8, 12, 16, 32, 48, 64, 96])
 def test_c3_pixel_major_entry_point(oracle, device, dtype, k):
     """nd_amd_omnibus_c3_pixel_major: the nine variables in the reference's (y, x, time) layout read where

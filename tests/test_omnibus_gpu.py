@@ -51,6 +51,22 @@ def test_wishart_parity(oracle, device, dtype, alpha):
     assert want[0].sum() > 0
 
 
+@pytest.mark.parametrize('alpha', [0.01, 0.5, 0.99])
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+@pytest.mark.parametrize('k', [2, 8, 9, 16, 17, 24, 25, 32, 33, 48, 49])
+def test_series_length_boundaries(oracle, device, k, dtype, alpha):
+    """Both sides of every bound of the launch sites' series-length lists (8 / 16 / 24 / 32 / 48, and 32 / 64 of the
+    streaming forms' lower end), in the fused, the in-between and the sparse regime, with the z / P rasters: a wrong
+    bound would hand k = 17 to a 16-date instantiation.  24 x 323 pixels: 31 blocks of 256, the last one and its last
+    wave ragged.  From three dates on every oracle map holds both values (checked for this seed and change_frac)."""
+    planes = synth.omnibus_stack(seed=41 + k, k=k, ny=24, nx=323, dtype=dtype, change_frac=0.3)
+    want = _run_oracle(oracle, planes, alpha, 9)
+    if k >= 3:
+        assert 0 < int(want[0].sum()) < want[0].size
+    got = _run_gpu(planes, alpha, 9, device)
+    _compare(got, want)
+
+
 @pytest.mark.parametrize('shape', [(24, 33, 77), (5, 8, 1030), (2, 3, 5), (37, 16, 64),
                                    (1, 4, 4), (24, 1, 1), (70, 9, 12)])
 @pytest.mark.parametrize('layout', ['tyx', 'yxt', 'yxtv'])
@@ -160,7 +176,9 @@ def test_minimal_workspace_gathers_from_planes(oracle, device, dtype):
 
 @pytest.mark.parametrize('dtype,k', [(np.float32, 24), (np.float32, 7), (np.float32, 16), (np.float64, 12),
                                      (np.float64, 5), (np.float32, 21), (np.float32, 22), (np.float32, 23),
-                                     (np.float32, 10), (np.float32, 2), (np.float32, 3), (np.float64, 11)])
+                                     (np.float32, 10), (np.float32, 2), (np.float32, 3), (np.float64, 11),
+                                     (np.float32, 8), (np.float32, 9), (np.float32, 17), (np.float64, 8),
+                                     (np.float64, 9)])
 def test_pixel_major_kernel_equals_planar(oracle, device, dtype, k):
     """nd_amd_omnibus_c2_pixel_major: variables in the reference's (y, x, time) layout, C12 as one
     interleaved complex tensor or as two real ones; ragged raster sizes (last spans of fewer than 64 pixels);
