@@ -159,6 +159,13 @@ const char *nd_amd_last_error(void);
 size_t nd_amd_omnibus_c2_workspace_bytes(int dtype, int64_t ny, int64_t nx, int64_t k,
                                          size_t *min_bytes);
 
+/* 1 if nd_amd_omnibus_c2 serves a call with these arguments in the wave-search form of its first pass (a wave
+ * searches the few candidates it finds itself; float32, 2 <= k <= 24, no z / P rasters, alpha >= 0.99), 0 if
+ * in another form.  Host only; every form gives the same map.  ND_AMD_WAVE_SEARCH=0 (read once per process)
+ * turns the form off. */
+int nd_amd_omnibus_c2_uses_wave_search(int dtype, int64_t k, int64_t stride_x, double alpha,
+                                       uint32_t n_looks, int stats);
+
 int nd_amd_omnibus_c2(const void *c11, const void *c12re, const void *c12im,
                       const void *c22, int dtype,
                       int64_t ny, int64_t nx, int64_t k,

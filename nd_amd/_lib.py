@@ -28,7 +28,7 @@ STRUCT_DIAG, STRUCT_C2, STRUCT_C3 = 0, 1, 2
 
 # every symbol include/nd_amd.h declares
 SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
-           'nd_amd_omnibus_c2_workspace_bytes', 'nd_amd_omnibus_c2',
+           'nd_amd_omnibus_c2_workspace_bytes', 'nd_amd_omnibus_c2_uses_wave_search', 'nd_amd_omnibus_c2',
            'nd_amd_omnibus_c2_pixel_major',
            'nd_amd_omnibus_c2_ml_workspace_bytes', 'nd_amd_omnibus_c2_ml',
            'nd_amd_omnibus_c3_workspace_bytes', 'nd_amd_omnibus_c3', 'nd_amd_omnibus_c3_pixel_major',
@@ -81,6 +81,8 @@ def lib():
     L.nd_amd_omnibus_c2_workspace_bytes.restype = C.c_size_t
     L.nd_amd_omnibus_c2_workspace_bytes.argtypes = [i32, i64, i64, i64,
                                                     C.POINTER(C.c_size_t)]
+    L.nd_amd_omnibus_c2_uses_wave_search.restype = i32
+    L.nd_amd_omnibus_c2_uses_wave_search.argtypes = [i32, i64, i64, dbl, C.c_uint32, i32]
     L.nd_amd_omnibus_c2.restype = i32
     L.nd_amd_omnibus_c2.argtypes = ([vp] * 4 + [i32] + [i64] * 6 + [C.c_uint32, dbl]
                                     + [vp, vp, vp, vp, C.c_size_t, vp])

@@ -212,40 +212,7 @@ omnibus_c2_retain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)
 
     // ---- issue every load of the series ----
     T v[KMAX][4];
-    if (EXACT) {
-        // x-contiguous planes: buffer loads through one descriptor per plane (base = first pixel
-        // of this block, uniform), a per-date scalar byte offset and a 32-bit lane offset -- no
-        // 64-bit per-lane address arithmetic, which keeps the kernel at 4 waves per SIMD.
-        const int64_t ub = row * g.sy + bpx0;
-        const unsigned lx = in ? (unsigned)tid : (unsigned)(g.nx - 1 - bpx0);   // idle lanes re-read the last pixel
-        const unsigned voff = lx * (unsigned)sizeof(T);
-        const auto r11 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c11 + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r12r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12r + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r12i = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12i + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r22 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c22 + ub), 0, 0x7fffffff, 0x00020000);
-        const unsigned sstep = (unsigned)g.st * (unsigned)sizeof(T);   // host guarantees k * st * sizeof(T) < 2^31
-#pragma unroll
-        for (int t = 0; t < KMAX; ++t) {
-            const unsigned soff = (unsigned)t * sstep;
-            v[t][0] = buffer_load<T>(r11, voff, soff);
-            v[t][1] = buffer_load<T>(r12r, voff, soff);
-            v[t][2] = buffer_load<T>(r12i, voff, soff);
-            v[t][3] = buffer_load<T>(r22, voff, soff);
-        }
-    } else {
-        const int64_t xc = in ? x0 : g.nx - 1;
-        const int64_t off0 = row * g.sy + xc * g.sx;
-#pragma unroll
-        for (int t = 0; t < KMAX; ++t) {
-            if (t < k) {
-                const int64_t off = off0 + (int64_t)t * g.st;
-                v[t][0] = __builtin_nontemporal_load(g.c11 + off);
-                v[t][1] = __builtin_nontemporal_load(g.c12r + off);
-                v[t][2] = __builtin_nontemporal_load(g.c12i + off);
-                v[t][3] = __builtin_nontemporal_load(g.c22 + off);
-            }
-        }
-    }
+    retain_load_series<T, KMAX, EXACT>(g, row, bpx0, tid, in, k, v);
 
     if (g.write_tab && b == 0) {
         for (int j = tid; j <= k; j += kRetainThreads) g.tab_dev[j] = tab.e[j];
@@ -294,6 +261,94 @@ omnibus_c2_retain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab)
         const int64_t left = g.nx - bpx0;
         const int npx = left > kRetainThreads ? kRetainThreads : (int)left;
         zero_fill_span<kRetainThreads>(g.change + (row * g.nx + bpx0) * (int64_t)k, npx * k, tid);   // <= 256 * k bytes
+    }
+}
+
+// -----------------------------------------------------------------------------------------
+// pass A, WAVE-SEARCH form of the register-retaining pass (float32, 2 <= k <= 24, sparse regime, no rasters):
+// loads, fold and screen as omnibus_c2_retain_kernel, but a wave that finds 1 .. kWaveSearchMax candidates
+// searches them itself while the other waves of the CU keep the memory system busy -- no list, no dump, no
+// atomic, no barrier.  The candidate lanes store their series into a wave-private LDS image (16-byte writes; the
+// 4 KMAX series registers are dead behind them), the wave runs wave_search_starts on it -- exact: nothing is
+// handed to a later kernel -- and writes its slice of the change map ONCE: the candidates' rows with the zeros
+// of the other lanes (a wave without candidates zero-fills its slice; no block-wide fill that a later store of
+// another wave would have to be ordered against).  A wave with kDenseMin candidates or more enters the dense
+// list as before: omnibus_c2_dense_kernel and the searches behind it serve it and what it hands on.
+// LDS per wave: 15 x KMAX x 16 bytes of series and 15 x KMAX bytes of rows -- 24.5 KB per block at 24 dates: four
+// blocks per CU fit.  Four waves per SIMD: at most 128 vector registers, no scratch (110 at 24 dates).
+// -----------------------------------------------------------------------------------------
+template <typename T, int KMAX, bool EXACT>
+__global__ void __launch_bounds__(kRetainThreads, 4)
+omnibus_c2_retain_wsearch_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const DenseScreen fscr)
+{
+    static_assert(KMAX % 4 == 0 && KMAX <= 24, "rows of whole words; 4 KMAX series registers within four waves per SIMD");
+    constexpr int kWaves = kRetainThreads / 64;
+    __shared__ __align__(16) T series_img[kWaves][kWaveSearchMax * KMAX * 4];    // also the image of store_change_rows_wave
+    __shared__ __align__(4) uint8_t rows_img[kWaves][kWaveSearchMax * KMAX];
+    static_assert(sizeof(series_img[0]) >= 16 * KMAX * sizeof(uint32_t), "store_change_rows_wave's image");
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int64_t b = blockIdx.x;
+    const int64_t row = b / g.blocks_per_row;
+    const int64_t bx = b - row * g.blocks_per_row;
+    const int64_t bpx0 = bx * (int64_t)kRetainThreads;
+    const int64_t x0 = bpx0 + tid;
+    const int k = EXACT ? KMAX : g.k;
+    const bool in = x0 < g.nx;
+
+    T v[KMAX][4];
+    retain_load_series<T, KMAX, EXACT>(g, row, bpx0, tid, in, k, v);
+
+    if (g.write_tab && b == 0) {
+        for (int j = tid; j <= k; j += kRetainThreads) g.tab_dev[j] = tab.e[j];
+    }
+
+    // ---- fold in time order, screen ----
+    Accum<T> A;
+    A.reset();
+#pragma unroll
+    for (int t = 0; t < KMAX; ++t)
+        if (EXACT || t < k) A.step(v[t][0], v[t][1], v[t][2], v[t][3]);
+    const bool flag = in && (z_approx<T>(A, k, g.nlooks, g.e) >= g.e.zlo_a);
+
+    const unsigned long long m = __ballot(flag);
+    const int nc = __popcll(m);
+    const int64_t wpx0 = bpx0 + (tid & ~63);                  // first pixel of this wave in its row
+    const int64_t wleft = g.nx - wpx0;
+    const int wnp = wleft > 64 ? 64 : (wleft > 0 ? (int)wleft : 0);
+    uint8_t *wob = g.change + (row * g.nx + wpx0) * (int64_t)k;
+
+    if (nc == 0 || nc > kWaveSearchMax) {
+        // dense wave: one entry for all 64 pixels (the dense kernel reloads them and decides every pixel itself)
+        if (nc != 0 && lane == 0) {
+            const unsigned shard = (unsigned)(b % kShards);
+            const unsigned slot = atomicAdd(g.flag_count + shard * kCounterStride + 1, 1u);
+            g.dense_idx[(size_t)shard * g.segd + slot] = (uint32_t)(row * g.nx + wpx0);
+        }
+        if (wnp > 0) zero_fill_span(wob, wnp * k, lane);
+        return;
+    }
+
+    // ---- sparse wave: stage the candidates' series, search them, write the slice ----
+    T *img = series_img[tid >> 6];
+    uint8_t *rows = rows_img[tid >> 6];
+    uint32_t *rows_w = reinterpret_cast<uint32_t *>(rows);
+    const int rank = __popcll(m & ((1ull << lane) - 1ull));
+    if (flag) dump_series<T, KMAX, EXACT>(img + rank * (KMAX * 4), v, k);
+    for (int w = lane; w < kWaveSearchMax * KMAX / 4; w += 64) rows_w[w] = 0u;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // same wave: LDS operations complete in order
+    wave_search_starts<T, KMAX>(img, rows, nc, k, g.nlooks, g.alpha, fscr.e, tab.e, lane);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    unsigned mask = 0u;
+    if (flag) {
+#pragma unroll
+        for (int q = 0; q < KMAX / 4; ++q)                  // bytes 0 / 1 of a word -> four bits
+            mask |= (((rows_w[rank * (KMAX / 4) + q] * 0x01020408u) >> 24) & 0xFu) << (4 * q);
+    }
+    if (change_rows_wave_ok(wob, k, wnp)) {
+        store_change_rows_wave(wob, reinterpret_cast<uint32_t *>(img), k, mask, lane);
+    } else if (in) {
+        store_change_row_lane<KMAX>(wob + (int64_t)lane * k, k, mask);
     }
 }
 
@@ -2908,6 +2963,61 @@ static void launch_retain(const OmniGlobalArgs<T> &g, const OmniTab &tab, int64_
     });
 }
 
+// ---- the wave-search form of pass A (omnibus_c2_retain_wsearch_kernel): which calls take it ----
+// ND_AMD_WAVE_SEARCH=0: the two-pass form (list and dump in pass A, the searches behind it), as before
+static bool wave_search_enabled()
+{
+    static const bool v = env_int("ND_AMD_WAVE_SEARCH", 1) != 0;
+    return v;
+}
+// ND_AMD_FUSED_ALPHA overrides the switch-over between the fused register search and the sparse design
+// (0 = never fuse, 2 = always); see omnibus_c2_impl
+static double fused_alpha_regs()
+{
+    static const double v = env_double("ND_AMD_FUSED_ALPHA", 0.93);
+    return v;
+}
+// (25 .. 32 dates keep the two-pass form: 128 series registers alone fill the budget of four waves per SIMD, the
+// instantiation spilled 124 bytes per lane)
+constexpr int kWaveSearchMaxDates = 24;
+// Below this threshold a wave holds several candidates and searches them in as many trips, which pass A no longer
+// hides: 24 x 4096^2 at alpha = 0.97 / 0.95 / 0.93 took 1.50 / 1.87 / 2.31 ms against 1.40 / 1.54 / 1.71 ms of the
+// two-pass form, at 0.99 / 0.999 1.22 / 1.21 against 1.29 / 1.27 (profiles/wave_search_forms.txt).  The lowest
+// threshold MEASURED to win is the switch; what lies between it and 0.97 keeps the two-pass form.
+constexpr double kWaveSearchAlpha = 0.99;
+// Host only.  float32 planes (any strides: stride_x == 1 selects the buffer-load instantiation, nothing else),
+// 2 <= k <= 24, no z / P rasters, the sparse regime (alpha at or above the fused switch-over and kWaveSearchAlpha), and screens that
+// can decide: the whole-series one of pass A and the float32 one of every sub-series length.
+static bool omni_c2_wave_search(int dtype, int64_t k, int64_t stride_x, double alpha, uint32_t n_looks, bool stats)
+{
+    (void)stride_x;
+    if (!wave_search_enabled() || dtype != ND_AMD_F32 || stats || n_looks == 0) return false;
+    if (k < 2 || k > kWaveSearchMaxDates || !(alpha >= fused_alpha_regs()) || !(alpha >= kWaveSearchAlpha)) return false;
+    const std::vector<OmniTabEntry> htab = get_table((int)k, n_looks, alpha, dtype, OmniFamily{2, 1});
+    if (!((htab[(size_t)k].zlo > -INFINITY) || (htab[(size_t)k].zhi < INFINITY))) return false;
+    const DenseScreen scr = make_dense_screen<float>(htab, (int)k, n_looks);
+    for (int j = 2; j <= (int)k; ++j)
+        if (!(scr.e[j].a > -INFINITY) && !(scr.e[j].b < INFINITY)) return false;
+    return true;
+}
+
+// (float32 only: omni_c2_wave_search says no to anything else)
+template <typename T>
+static void launch_retain_wsearch(const OmniGlobalArgs<T> &g, const OmniTab &tab, const DenseScreen &scr,
+                                  int64_t nblocks, hipStream_t stream)
+{
+    if constexpr (std::is_same<T, float>::value) {
+        const dim3 grid((unsigned)nblocks), block(kRetainThreads);
+        pick_le<8, 16, kWaveSearchMaxDates>(g.k, [&](auto K) {
+            constexpr int KMAX = decltype(K)::value;
+            pick(g.k == KMAX && series_fits_buffer(g), [&](auto E) {
+                hipLaunchKernelGGL((omnibus_c2_retain_wsearch_kernel<T, KMAX, decltype(E)::value>), grid, block, 0,
+                                   stream, g, tab, scr);
+            });
+        });
+    }
+}
+
 // k <= 32 (float) / 24 (double): the series lengths the chain form keeps in registers
 template <typename T>
 static void launch_chain(const OmniGlobalArgs<T> &g, const OmniTab &tab, const std::vector<OmniTabEntry> &htab,
@@ -3022,7 +3132,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
     // 2.9 / 2.5 / 2.1 ms): it is offered up to 0.93, and the device-side sample decides.  The forms
     // that pay more for fusing (pixel-major: the LDS images; longer series: two streaming passes)
     // keep 0.75.
-    static const double fused_alpha_regs = env_double("ND_AMD_FUSED_ALPHA", 0.93);
+    const double fused_alpha_regs = nd_amd::fused_alpha_regs();
     // (z / P rasters asked for on top: they come from one launch of the plain pass A first, see below)
     const bool fused = retain && dense_ok && alpha < fused_alpha_regs && !exact_flags;
     const bool fused_stats = fused && stats;
@@ -3745,7 +3855,11 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         }
     } else {
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
-        if (retain)
+        // the wave-search form: sparse waves search their own candidates (no list, no dump); the dense waves'
+        // entries and what the dense kernel hands on are served by the launches below, as before
+        if (omni_c2_wave_search(dtype_of<T>(), k, sx, alpha, n_looks, stats) && g.dense_min == kDenseMin)
+            launch_retain_wsearch<T>(g, tab, make_dense_screen<T>(htab, (int)k, n_looks), nblocks, stream);
+        else if (retain)
             launch_retain<T>(g, tab, nblocks, stats || exact_flags, stream);
         else if (aligned)
             launch_global<T, VPPT>(g, tab, nblocks, stats || exact_flags, stream);
@@ -3780,6 +3894,12 @@ extern "C" size_t nd_amd_omnibus_c2_workspace_bytes(int dtype, int64_t ny, int64
     const OmniWorkspace w = omni_layout(ny * nx, ny, k, dtype == ND_AMD_F64 ? 8 : 4);
     if (min_bytes) *min_bytes = w.min_total;
     return w.recommended;
+}
+
+extern "C" int nd_amd_omnibus_c2_uses_wave_search(int dtype, int64_t k, int64_t stride_x, double alpha,
+                                                  uint32_t n_looks, int stats)
+{
+    return omni_c2_wave_search(dtype, k, stride_x, alpha, n_looks, stats != 0) ? 1 : 0;
 }
 
 extern "C" int nd_amd_omnibus_c2(const void *c11, const void *c12re, const void *c12im,

@@ -123,6 +123,114 @@ constexpr int kShards = 128;
 constexpr int kCounterStride = 32;   // uint32 words between shard counters (128 B)
 constexpr int kTimeChunk = 4;
 
+// The loads of the register-retaining pass A: one thread per pixel issues all k x 4 loads at once.
+// EXACT (k == KMAX, stride_x == 1): buffer loads through one descriptor per plane (base = first pixel of
+// this block, uniform), a per-date scalar byte offset and a 32-bit lane offset -- no 64-bit per-lane
+// address arithmetic, which keeps the kernel at 4 waves per SIMD.  Otherwise: plain loads of the dates
+// t < k; v[t] of the others stays unset.
+template <typename T, int KMAX, bool EXACT>
+__device__ __forceinline__ void retain_load_series(const OmniGlobalArgs<T> &g, const int64_t row, const int64_t bpx0,
+                                                   const int tid, const bool in, const int k, T (&v)[KMAX][4])
+{
+    if (EXACT) {
+        const int64_t ub = row * g.sy + bpx0;
+        const unsigned lx = in ? (unsigned)tid : (unsigned)(g.nx - 1 - bpx0);   // idle lanes re-read the last pixel
+        const unsigned voff = lx * (unsigned)sizeof(T);
+        const auto r11 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c11 + ub), 0, 0x7fffffff, 0x00020000);
+        const auto r12r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12r + ub), 0, 0x7fffffff, 0x00020000);
+        const auto r12i = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12i + ub), 0, 0x7fffffff, 0x00020000);
+        const auto r22 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c22 + ub), 0, 0x7fffffff, 0x00020000);
+        const unsigned sstep = (unsigned)g.st * (unsigned)sizeof(T);   // host guarantees k * st * sizeof(T) < 2^31
+#pragma unroll
+        for (int t = 0; t < KMAX; ++t) {
+            const unsigned soff = (unsigned)t * sstep;
+            v[t][0] = buffer_load<T>(r11, voff, soff);
+            v[t][1] = buffer_load<T>(r12r, voff, soff);
+            v[t][2] = buffer_load<T>(r12i, voff, soff);
+            v[t][3] = buffer_load<T>(r22, voff, soff);
+        }
+    } else {
+        const int64_t xc = in ? bpx0 + tid : g.nx - 1;
+        const int64_t off0 = row * g.sy + xc * g.sx;
+#pragma unroll
+        for (int t = 0; t < KMAX; ++t) {
+            if (t < k) {
+                const int64_t off = off0 + (int64_t)t * g.st;
+                v[t][0] = __builtin_nontemporal_load(g.c11 + off);
+                v[t][1] = __builtin_nontemporal_load(g.c12r + off);
+                v[t][2] = __builtin_nontemporal_load(g.c12i + off);
+                v[t][3] = __builtin_nontemporal_load(g.c22 + off);
+            }
+        }
+    }
+}
+
+// A lane's row of the change map from its mask, where the wave cannot store its rows as one span
+// (change_rows_wave_ok): 4-byte pieces if the row allows them, bytes otherwise.
+template <int KMAX, typename MT>
+__device__ __forceinline__ void store_change_row_lane(uint8_t *res, const int k, const MT mask)
+{
+    if ((k & 3) == 0 && ((uintptr_t)res & 3) == 0) {
+        uint32_t *w = reinterpret_cast<uint32_t *>(res);
+#pragma unroll
+        for (int q = 0; q < KMAX / 4; ++q)
+            if (q < (k >> 2)) w[q] = (mask_nibble(mask, q) * 0x00204081u) & 0x01010101u;
+    } else {
+        for (int t = 0; t < k; ++t) res[t] = (uint8_t)((mask >> t) & (MT)1);
+    }
+}
+
+// -----------------------------------------------------------------------------------------
+// The search of a sparse wave's own candidates (the wave-search form of pass A): one lane per SEGMENT
+// START, the algorithm of omnibus_c2_search_starts_kernel on series the wave has staged in LDS.
+//   img   the wave's image [candidate][KMAX dates][4], nc candidates (1 <= nc <= kWaveSearchMax)
+//   rows  [candidate][KMAX] bytes, zeroed: the candidate's row of the change map, written here
+// Lane l of a group of k - 1 lanes sweeps ts[l:] of the group's candidate once -- one 16-byte LDS read per
+// date, the next one in flight -- 64 / (k - 1) candidates per trip.  At step i every lane tests over
+// j = i + 1 dates: the constants of the float32 screen (scr, a kernel argument) are one scalar load.
+// What the screen cannot decide is evaluated exactly on the spot (exact_tail; full_table: the kernel's
+// own copy of the table), so the wave finishes its pixels: nothing is handed on.
+// -----------------------------------------------------------------------------------------
+constexpr int kWaveSearchMax = kDenseMin - 1;    // candidates of a wave below which it is not searched as a whole
+template <typename T, int KMAX>
+__device__ __forceinline__ void wave_search_starts(const T *img, uint8_t *rows, const int nc, const int k,
+                                                   const double nlooks, const double alpha,
+                                                   const DenseScreenEntry *scr, const OmniTabEntry *full_table,
+                                                   const int lane)
+{
+    const int ns = k - 1;                       // segment starts per pixel: 0 .. k - 2
+    const int ppw = 64 / ns;                    // candidates per trip
+    const int grp = lane / ns;
+    const int l0 = lane - grp * ns;
+    for (int c0 = 0; c0 < nc; c0 += ppw) {
+        const int cand = c0 + grp;
+        const bool lact = grp < ppw && cand < nc;
+        const int slot = lact ? cand : 0;       // idle lanes read along in candidate 0
+        const Pack<T, 4> *src = reinterpret_cast<const Pack<T, 4> *>(img) + slot * KMAX;
+        Accum<T> A;
+        A.reset();
+        Sweep sw;                               // (of the one segment this lane sweeps: l stays)
+        sw.begin(true);
+        int nx = -1;                            // stop
+        Pack<T, 4> qn = src[l0];
+        for (int i = 0; i < k; ++i) {           // the lane's date is l0 + i
+            const Pack<T, 4> q = qn;
+            const int t = l0 + i;
+            qn = src[t + 1 < k ? t + 1 : k - 1];
+            const bool on = lact && t < k;
+            if (on) A.step(q.v[0], q.v[1], q.v[2], q.v[3]);
+            const int jj = i + 1;               // wave-uniform
+            const bool last = (t == k - 1);
+            const bool need = on && sw.need(jj, last);
+            const bool fires = test_f32(need, A, jj, nlooks, alpha, scr, full_table);
+            sw.note(fires, t);
+            if (last && fires) nx = sw.fire_at;              // the global test of ts[l0:] fired (jj >= 2 here)
+        }
+        const int nxt[1] = {nx};
+        follow_starts_chain<1>(nxt, ns, ns, grp, lact && l0 == 0, rows + slot * KMAX);
+    }
+}
+
 
 typedef __attribute__((address_space(3))) unsigned char lds_u8_t;
 typedef __attribute__((address_space(1))) const unsigned char glb_u8_t;
