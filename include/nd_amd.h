@@ -81,6 +81,7 @@ extern "C" {
 #define ND_AMD_KERNEL_GATHER_ROWS     25  /* nd_amd_gather_rows */
 #define ND_AMD_KERNEL_CHANGE_SEGMENTS 26  /* nd_amd_change_segments */
 #define ND_AMD_KERNEL_RASTERIZE       27  /* nd_amd_rasterize_polygons, the whole call (clear, fill, resolve) */
+#define ND_AMD_KERNEL_RESAMPLE        28  /* nd_amd_resample and nd_amd_resample_nearest */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -107,6 +108,8 @@ extern "C" {
 #define ND_AMD_I64 2
 /* crossings of one (polygon, row) a wave keeps in its LDS list; rows with more take the per-pixel walk */
 #define ND_AMD_RASTERIZE_MAX_CROSSINGS 256
+/* nd_amd_resample: the longest run of taps an axis table may hold */
+#define ND_AMD_RESAMPLE_MAX_TAPS 256
 
 #define ND_AMD_COREG_MAX_UPSAMPLING 128
 #define ND_AMD_COREG_MAX_VARS       16
@@ -928,6 +931,102 @@ int nd_amd_rasterize_polygons(const double *verts,          /* (nverts, 2) pixel
                               int64_t npolys, int64_t nlayers, int64_t ny, int64_t nx,
                               void *out, int64_t stride_l, int64_t stride_y, int64_t stride_x,  /* elements */
                               void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* ------------------------------------------------------------------------
+ * Resampling onto another rotation-free grid -- the native step under
+ * nd.warp.Resample, Reprojection (within one coordinate system) and
+ * Alignment (nd/warp.py:872-1097, rasterio.warp.reproject).  GDAL is not
+ * reproduced bit for bit; THE DEFINITION BELOW IS THIS PROJECT'S.  It is the
+ * convention of Pillow's resize and of torch's interpolate(antialias=True):
+ * the kernel is stretched by the down-sampling ratio, clipped at the raster's
+ * edge and renormalised.
+ *
+ * A grid is a rotation-free transform (a, 0, c, 0, e, f), a ≠ 0 and e ≠ 0 of
+ * either sign, and a size.  Everything on the host is float64, bracketed as
+ * written.  Per axis (x shown; y alike with e, f, rows), for a source of n
+ * samples with (a_s, c_s) and an output of m samples with (a_d, c_d):
+ *
+ *     ρ   = |a_d / a_s|
+ *     u_j = ((c_d + a_d * (j + 0.5)) − c_s) / a_s     centre of output sample j in source pixel units
+ *     output sample j is inside  iff  0 ≤ u_j < n     (false for NaN)
+ *
+ * The taps of an inside sample are a contiguous run of source indices:
+ *
+ * - nearest: the one tap floor(u_j), weight 1.
+ * - bilinear (R = 1) and cubic (R = 2): s = max(ρ, 1); the taps are
+ *   x = max(0, floor(u − R s + 0.5)) … min(n, floor(u + R s + 0.5)) − 1 with
+ *   the raw weight φ((x + 0.5 − u) / s).  Bilinear: φ(d) = 1 − |d| for
+ *   |d| < 1, else 0.  Cubic is Keys's kernel with a = −0.5:
+ *   ((a + 2)|d| − (a + 3))|d|² + 1 for |d| < 1,
+ *   (((|d| − 5)|d| + 8)|d| − 4) a for 1 ≤ |d| < 2, else 0.
+ * - average: lo = u − ρ/2, hi = u + ρ/2; the taps are
+ *   x = max(0, floor(lo)) … min(n, ceil(hi)) − 1 with the raw weight
+ *   min(x + 1, hi) − max(x, lo).
+ *
+ * Taps of weight exactly 0 are trimmed from both ends of the run (zeros inside
+ * stay), the weights are divided by their sum, added in tap order, and a run
+ * left empty makes the sample outside.
+ *
+ * Per output pixel (i, j), T the data's type:
+ *
+ *     if row i and column j are both inside:
+ *         acc = 0.0
+ *         for r over the row taps, ascending:
+ *             h = 0.0
+ *             for q over the column taps, ascending:  h = h + wx_q * double(src[r, q])
+ *             acc = acc + wy_r * h
+ *         out[i, j] = T(acc)                           (one rounding, no fma)
+ *     else:
+ *         out[i, j] = fill
+ *
+ * No value is special-cased: a NaN or inf under a tap enters the sum as it is,
+ * under an interior zero weight too.  nd_amd_resample_nearest copies the
+ * element's bits, out[i, j] = src[floor(v_i), floor(u_j)], for elements of 1,
+ * 2, 4 and 8 bytes: NaN payloads and -0.0 survive, integers keep their type.
+ *
+ * The tables of an axis of m output samples, device memory: start[m] and
+ * count[m] int32 (count 0 = outside), weights[taps][m] float64, tap-major,
+ * `taps` the longest run.  The kernels do no coordinate arithmetic.  An entry
+ * whose run does not lie inside the source extent, or is longer than `taps`,
+ * gives fill: nothing outside the stated extent is read whatever the tables
+ * hold.  nd_amd_resample_check_table says whether a table has such entries
+ * (ND_AMD_EINVAL, "count / start out of range"); it synchronises, the other
+ * two entries do not.
+ *
+ * The data are a batch of nplanes images with an inner axis of length `inner`;
+ * src_strides / dst_strides are 4 host values in elements for (plane, y, x,
+ * inner).  inner = 1 is a planar stack; inner = k with stride 1 is the
+ * reference's (y, x, time) layout.  Lanes run along whichever of x and the
+ * inner axis has the smaller stride in the destination; the result is written
+ * in the layout the strides state, without a transpose pass.
+ * ND_AMD_EINVAL before any HIP call for null pointers, a bad dtype or element
+ * size, negative sizes, strides or tap counts; ND_AMD_EUNSUPPORTED for more
+ * than ND_AMD_RESAMPLE_MAX_TAPS taps on an axis, for rasters of 2^31 pixels
+ * or more per plane on either side and for nplanes * inner of 2^31 or more;
+ * ND_AMD_OK for an empty destination.
+ * ---------------------------------------------------------------------- */
+int nd_amd_resample(const void *src, void *dst, int dtype,             /* ND_AMD_F32 or ND_AMD_F64          */
+                    int64_t nplanes, int64_t inner,
+                    int64_t src_ny, int64_t src_nx, const int64_t *src_strides,
+                    int64_t dst_ny, int64_t dst_nx, const int64_t *dst_strides,
+                    const int32_t *start_y, const int32_t *count_y,     /* dst_ny each                       */
+                    const double *weights_y, int taps_y,               /* (taps_y, dst_ny)                  */
+                    const int32_t *start_x, const int32_t *count_x,     /* dst_nx each                       */
+                    const double *weights_x, int taps_x,               /* (taps_x, dst_nx)                  */
+                    double fill, void *hip_stream);
+
+int nd_amd_resample_nearest(const void *src, void *dst, int elem_size, /* 1, 2, 4 or 8 bytes                */
+                            int64_t nplanes, int64_t inner,
+                            int64_t src_ny, int64_t src_nx, const int64_t *src_strides,
+                            int64_t dst_ny, int64_t dst_nx, const int64_t *dst_strides,
+                            const int32_t *start_y, const int32_t *count_y,
+                            const int32_t *start_x, const int32_t *count_x,
+                            const void *fill,                          /* one host element                  */
+                            void *hip_stream);
+
+int nd_amd_resample_check_table(const int32_t *start, const int32_t *count, int64_t m, /* output samples    */
+                                int64_t n, int taps,                   /* source samples, rows of weights   */
+                                void *hip_stream);
 
 #ifdef __cplusplus
 }

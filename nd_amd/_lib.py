@@ -22,7 +22,7 @@ KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose',
                 17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean',
                 21: 'classify_knn', 22: 'classify_linear', 23: 'kmeans_step', 24: 'feature_moments',
-                25: 'gather_rows', 26: 'change_segments', 27: 'rasterize'}
+                25: 'gather_rows', 26: 'change_segments', 27: 'rasterize', 28: 'resample'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 STRUCT_DIAG, STRUCT_C2, STRUCT_C3 = 0, 1, 2
 
@@ -46,11 +46,13 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_classify_knn', 'nd_amd_classify_linear',
            'nd_amd_kmeans_fit_workspace_bytes', 'nd_amd_kmeans_step', 'nd_amd_feature_moments',
            'nd_amd_gather_rows',
-           'nd_amd_rasterize_workspace_bytes', 'nd_amd_rasterize_polygons')
+           'nd_amd_rasterize_workspace_bytes', 'nd_amd_rasterize_polygons',
+           'nd_amd_resample', 'nd_amd_resample_nearest', 'nd_amd_resample_check_table')
 CLASSIFY_BLOCK_ROWS, CLASSIFY_MAX_FEATURES = 1024, 1024
 CLASSIFY_KNN_MAX_K, CLASSIFY_KNN_MAX_FEATURES, CLASSIFY_KNN_TILE = 32, 128, 8
 KMEANS_FIT_MAX_ACC = 4096
 RASTERIZE_MAX_CROSSINGS = 256
+RESAMPLE_MAX_TAPS = 256
 LINKS = {'none': 0, 'softmax': 1, 'ovr': 2}
 LINEAR_OUTPUTS = {'predict': 0, 'decision_function': 1, 'predict_proba': 2}
 
@@ -195,6 +197,13 @@ def lib():
     L.nd_amd_rasterize_polygons.restype = i32
     L.nd_amd_rasterize_polygons.argtypes = ([vp] * 7 + [i32, vp] + [i64] * 4 + [vp] + [i64] * 3
                                             + [vp, C.c_size_t, vp])
+    grid = [i64, i64, i64, i64, pi64, i64, i64, pi64]     # nplanes, inner, source size and strides, destination
+    L.nd_amd_resample.restype = i32
+    L.nd_amd_resample.argtypes = [vp, vp, i32] + grid + [vp, vp, vp, i32] * 2 + [dbl, vp]
+    L.nd_amd_resample_nearest.restype = i32
+    L.nd_amd_resample_nearest.argtypes = [vp, vp, i32] + grid + [vp] * 4 + [vp, vp]
+    L.nd_amd_resample_check_table.restype = i32
+    L.nd_amd_resample_check_table.argtypes = [vp, vp, i64, i64, i32, vp]
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

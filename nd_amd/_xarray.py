@@ -1,7 +1,8 @@
 """
 nd_amd/_xarray.py -- optional xarray accessors mirroring nd/_xarray.py:135-161 for the algorithms
 this package provides: `ds.nd_amd.change_omnibus(...)`, `ds.nd_amd.nlmeans(...)`,
-`ds.nd_amd.boxcar(...)`, `ds.nd_amd.convolve(...)`, `ds.nd_amd.gaussian(...)`, `ds.nd_amd.to_rgb(...)`.
+`ds.nd_amd.boxcar(...)`, `ds.nd_amd.convolve(...)`, `ds.nd_amd.gaussian(...)`, `ds.nd_amd.to_rgb(...)`,
+`ds.nd_amd.resample(...)`, `ds.nd_amd.reproject(...)`.
 
 Registered only when xarray is importable (it is not installed in the build or GPU images); the
 accessor name differs from the reference's (`nd`, `filter`) so both can be loaded side by side.
@@ -19,6 +20,8 @@ _METHODS = {
     'boxcar': ('filters', 'boxcar'),
     'convolve': ('filters', 'convolution'),
     'gaussian': ('filters', 'gaussian'),
+    'resample': ('warp', 'resample'),
+    'reproject': ('warp', 'reproject'),
 }
 
 
@@ -49,8 +52,8 @@ def register():
     """Attach the `nd_amd` accessor to xarray Datasets and DataArrays; False without xarray."""
     if xr is None:
         return False
-    from . import change, filters
-    modules = {'change': change, 'filters': filters}
+    from . import change, filters, warp
+    modules = {'change': change, 'filters': filters, 'warp': warp}
     namespace = {'__init__': lambda accessor, obj: setattr(accessor, '_obj', obj)}
     for name, (module, function) in _METHODS.items():
         namespace[name] = _forward(getattr(modules[module], function))

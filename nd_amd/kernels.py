@@ -1567,3 +1567,235 @@ def rasterize_polygons(verts, ring_offsets, poly_offsets, values, ny, nx, layer=
         _record([table.verts, table.ring_offsets, table.poly_offsets, table.row_work, table.boxes, lay, vals, ws,
                  out], dev)
     return out
+
+
+# ---------------------------------------------------------------------------
+# stacks brought onto another rotation-free grid (nd/warp.py:872-1097; include/nd_amd.h nd_amd_resample)
+# ---------------------------------------------------------------------------
+RESAMPLE_MAX_TAPS = _lib.RESAMPLE_MAX_TAPS
+RESAMPLE_METHODS = ('nearest', 'bilinear', 'cubic', 'average')
+# raw runs the table builder is willing to lay out before it gives up (the entry serves RESAMPLE_MAX_TAPS)
+_RESAMPLE_TABLE_CAP = 16 * RESAMPLE_MAX_TAPS
+
+
+class AxisTable:
+    """The taps of one axis: start and count int32 (m), count 0 = outside; weights float64 (taps, m), tap-major.
+    numpy arrays as resample_axis returns them, ROCm tensors after .to(device)."""
+
+    def __init__(self, n, m, method, start, count, weights):
+        self.n, self.m, self.method = int(n), int(m), method
+        self.start, self.count, self.weights = start, count, weights
+        self.taps = int(weights.shape[0])
+
+    @property
+    def device(self):
+        return self.start.device if torch.is_tensor(self.start) else None
+
+    def to(self, device):
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if self.device == device:
+            return self
+        up = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device)   # noqa: E731
+        return AxisTable(self.n, self.m, self.method, up(self.start), up(self.count), up(self.weights))
+
+
+def _resample_phi(method, d):
+    d = np.abs(d)
+    if method == 'bilinear':
+        return np.where(d < 1.0, 1.0 - d, 0.0)
+    a = -0.5
+    near = ((a + 2.0) * d - (a + 3.0)) * (d * d) + 1.0
+    far = (((d - 5.0) * d + 8.0) * d - 4.0) * a
+    return np.where(d < 1.0, near, np.where(d < 2.0, far, 0.0))
+
+
+def resample_axis(n, m, src, dst, method):
+    """The tap table of one axis (README.md "Resampling and reprojection" has the definition): n source samples on
+    src = (a_s, c_s), m output samples on dst = (a_d, c_d), the (a, c) / (e, f) terms of the two transforms.
+    method: 'nearest', 'bilinear', 'cubic' or 'average'.  -> AxisTable of numpy arrays; float64 throughout, every
+    operation bracketed as the definition writes it, so that the table equals a scalar evaluation bit for bit."""
+    if method not in RESAMPLE_METHODS:
+        raise ValueError('method must be one of %s, got %r' % (RESAMPLE_METHODS, method))
+    n, m = int(n), int(m)
+    if n < 0 or m < 0 or n >= 2 ** 31 or m >= 2 ** 31:
+        raise ValueError('axis lengths must lie in [0, 2^31), got n=%d m=%d' % (n, m))
+    a_s, c_s, a_d, c_d = float(src[0]), float(src[1]), float(dst[0]), float(dst[1])
+    if not (np.isfinite(a_s) and np.isfinite(a_d)) or a_s == 0.0 or a_d == 0.0:
+        raise ValueError('a grid needs a finite pixel size other than 0, got source %r destination %r'
+                         % ((a_s, c_s), (a_d, c_d)))
+    rho = abs(a_d / a_s)
+    with np.errstate(all='ignore'):
+        u = ((c_d + a_d * (np.arange(m, dtype=np.float64) + 0.5)) - c_s) / a_s
+        inside = (u >= 0.0) & (u < n)
+        u = np.where(inside, u, 0.0)
+        if method == 'nearest':
+            return AxisTable(n, m, method, np.floor(u).astype(np.int32), inside.astype(np.int32),
+                             inside.astype(np.float64)[None, :])
+        if method == 'average':
+            lo, hi = u - rho / 2.0, u + rho / 2.0
+            x0 = np.maximum(0.0, np.floor(lo))
+            x1 = np.minimum(float(n), np.ceil(hi))
+        else:
+            R = 1.0 if method == 'bilinear' else 2.0
+            s = max(rho, 1.0)
+            x0 = np.maximum(0.0, np.floor(u - R * s + 0.5))
+            x1 = np.minimum(float(n), np.floor(u + R * s + 0.5))
+        x1 = np.where(inside, x1, x0)
+        K = int(np.max(x1 - x0)) if m else 0
+        if K > _RESAMPLE_TABLE_CAP:
+            raise ValueError('%d taps on an axis: at most %d are served' % (K, RESAMPLE_MAX_TAPS))
+        raw = np.zeros((max(K, 1), m), np.float64)
+        for t in range(K):
+            x = x0 + t
+            if method == 'average':
+                w = np.minimum(x + 1.0, hi) - np.maximum(x, lo)
+            else:
+                w = _resample_phi(method, (x + 0.5 - u) / s)
+            raw[t] = np.where(x < x1, w, 0.0)
+        # zeros trimmed from both ends of the run, zeros inside kept
+        some = raw != 0.0
+        first = np.argmax(some, axis=0)
+        last = raw.shape[0] - 1 - np.argmax(some[::-1], axis=0)
+        count = np.where(some.any(axis=0), last - first + 1, 0).astype(np.int32)
+        T = max(int(count.max()) if m else 0, 1)
+        cols = np.arange(m)
+        run = np.zeros((T, m), np.float64)
+        total = np.zeros(m, np.float64)
+        for t in range(T):
+            run[t] = raw[np.minimum(first + t, raw.shape[0] - 1), cols]
+            total = np.where(t < count, total + run[t], total)
+        weights = np.where(np.arange(T)[:, None] < count[None, :], run / total[None, :], 0.0)
+    start = np.where(count > 0, x0 + first, 0.0).astype(np.int32)
+    return AxisTable(n, m, method, start, count, weights)
+
+
+def _resample_axes(dims, ndim):
+    dims = tuple(dims)
+    if len(dims) != ndim or len(set(dims)) != ndim or 'y' not in dims or 'x' not in dims:
+        raise ValueError("dims must name the tensor's %d axes, 'y' and 'x' among them, got %r" % (ndim, dims))
+    if ndim > 4:
+        raise ValueError('at most two axes besides y and x are served, got dims %r' % (dims,))
+    return dims.index('y'), dims.index('x'), [d for d in range(ndim) if dims[d] not in ('y', 'x')]
+
+
+def _empty_like_strides(t, shape):
+    """an uninitialised tensor of `shape` whose axes are ordered in memory as t's are"""
+    order = sorted(range(t.dim()), key=lambda d: (-t.stride(d), d))
+    inv = [order.index(d) for d in range(t.dim())]
+    return torch.empty([shape[d] for d in order], dtype=t.dtype, device=t.device).permute(*inv)
+
+
+def resample(planes, table_y, table_x, dims=('time', 'y', 'x'), fill=None, out=None):
+    """Bring images onto another grid (include/nd_amd.h has the definition).  planes: one ROCm tensor or a list of
+    same-shaped ones of one dtype, with the axes `dims` names: y, x and up to two more in any order and with any
+    non-negative strides (crops of larger tensors included).  (time, y, x) and (y, x, time) data are read where
+    they lie and the result has the same memory order.  table_y / table_x: the AxisTables of resample_axis; numpy
+    tables are uploaded once for all planes of the call, tables already on the device are used as they are.  Where
+    both tables are 'nearest' the elements are copied bit for bit (1, 2, 4 or 8 bytes: bool, integers and floats
+    keep their type); otherwise float32 and float64 are served and integers are computed and returned as float64.
+    fill: the value outside the source, NaN by default for floating data and 0 for integers.  out: a tensor (or
+    list) of the result's shape and type, any strides.  -> a tensor, or a list where a list was given."""
+    single = torch.is_tensor(planes)
+    planes = [planes] if single else list(planes)
+    if not planes:
+        return []
+    p0 = planes[0]
+    for t in planes:
+        if not torch.is_tensor(t):
+            raise TypeError('planes must be torch tensors, got %r' % type(t))
+        if not t.is_cuda:
+            raise ValueError('planes must live on a ROCm device (got %s); nd_amd has no CPU path' % t.device)
+        if t.shape != p0.shape or t.dtype != p0.dtype or t.device != p0.device:
+            raise ValueError('the planes of one call share shape, dtype and device')
+    for tb in (table_y, table_x):
+        if not isinstance(tb, AxisTable):
+            raise TypeError('table_y and table_x are the AxisTables resample_axis returns')
+    dev = p0.device
+    ay, ax, extra = _resample_axes(dims, p0.dim())
+    if (table_y.n, table_x.n) != (p0.shape[ay], p0.shape[ax]):
+        raise ValueError('the tables were built for a (%d, %d) source, the planes are (%d, %d)'
+                         % (table_y.n, table_x.n, p0.shape[ay], p0.shape[ax]))
+    nearest = table_y.method == 'nearest' and table_x.method == 'nearest'
+    if nearest:
+        if p0.element_size() not in (1, 2, 4, 8):
+            raise TypeError('nearest serves elements of 1, 2, 4 and 8 bytes, got %s' % p0.dtype)
+    elif p0.dtype not in _DT:
+        if p0.is_floating_point() or p0.is_complex():
+            raise TypeError('the weighted methods serve float32, float64 and integers, got %s' % p0.dtype)
+        planes = [t.to(torch.float64) for t in planes]
+        p0 = planes[0]
+    shape = list(p0.shape)
+    shape[ay], shape[ax] = table_y.m, table_x.m
+    if out is None:
+        outs = [_empty_like_strides(p0, shape) for _ in planes]
+    else:
+        outs = [out] if torch.is_tensor(out) else list(out)
+        if len(outs) != len(planes):
+            raise ValueError('out must hold one tensor per plane')
+        for o, t in zip(outs, planes):
+            if (not torch.is_tensor(o) or list(o.shape) != shape or o.dtype != p0.dtype or o.device != dev):
+                raise ValueError('out must be %s of %s on %s' % (tuple(shape), p0.dtype, dev))
+            if any(s == 0 and n > 1 for s, n in zip(o.stride(), shape)):
+                raise ValueError('an expanded out (stride 0) is not served')
+            if _may_overlap(o, t):
+                raise ValueError('out must not overlap its source')
+    if fill is None:
+        fill = float('nan') if (p0.is_floating_point() or p0.is_complex()) else 0
+    if p0.numel() == 0 and outs[0].numel() > 0:
+        raise ValueError('an empty source has nothing to resample')
+    # the inner axis is the extra one closer in the destination; a second one is the batch
+    o0 = outs[0]
+    extra = sorted(extra, key=lambda d: -o0.stride(d))
+    plane_ax = extra[0] if len(extra) == 2 else None
+    inner_ax = extra[-1] if extra else None
+    nplanes = p0.shape[plane_ax] if plane_ax is not None else 1
+    inner = p0.shape[inner_ax] if inner_ax is not None else 1
+
+    def strides(t):
+        return _lib.i64_array([t.stride(plane_ax) if plane_ax is not None else 0, t.stride(ay), t.stride(ax),
+                               t.stride(inner_ax) if inner_ax is not None else 0])
+
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        ty, tx = table_y.to(dev), table_x.to(dev)
+        if nearest:
+            from ._device import _TORCH2NP
+            if p0.dtype in _TORCH2NP:
+                fill_bytes = np.array(fill).astype(_TORCH2NP[p0.dtype]).tobytes()
+            elif fill == 0:
+                fill_bytes = bytes(p0.element_size())
+            else:
+                raise TypeError('a fill other than 0 for %s elements is not served' % p0.dtype)
+            fill_buf = C.create_string_buffer(fill_bytes, len(fill_bytes))
+        for t, o in zip(planes, outs):
+            args = [nplanes, inner, p0.shape[ay], p0.shape[ax], strides(t), table_y.m, table_x.m, strides(o)]
+            if nearest:
+                _lib.check(L.nd_amd_resample_nearest(
+                    _ptr(t), _ptr(o), p0.element_size(), *args, _ptr(ty.start), _ptr(ty.count), _ptr(tx.start),
+                    _ptr(tx.count), C.cast(fill_buf, C.c_void_p), _stream_ptr(dev)))
+            else:
+                _lib.check(L.nd_amd_resample(
+                    _ptr(t), _ptr(o), _DT[p0.dtype], *args, _ptr(ty.start), _ptr(ty.count), _ptr(ty.weights), ty.taps,
+                    _ptr(tx.start), _ptr(tx.count), _ptr(tx.weights), tx.taps, float(fill), _stream_ptr(dev)))
+        _record(planes + outs + [ty.start, ty.count, ty.weights, tx.start, tx.count, tx.weights], dev)
+    return outs[0] if single else outs
+
+
+def resample_check_table(table, device=None):
+    """Raise NdAmdError unless every run of the table lies inside its axis (nd_amd_resample_check_table;
+    synchronises).  resample_axis builds tables that pass; this is for tables made elsewhere."""
+    dev = table.device or _lib_device(device)
+    with torch.cuda.device(dev):
+        t = table.to(dev)
+        _lib.check(_lib.lib().nd_amd_resample_check_table(_ptr(t.start), _ptr(t.count), t.m, t.n, t.taps,
+                                                          _stream_ptr(dev)))
+
+
+def _lib_device(device=None):
+    if device is not None:
+        return torch.device(device)
+    if not torch.cuda.is_available():
+        raise RuntimeError('nd_amd needs a ROCm GPU: the compute path is HIP only')
+    return torch.device('cuda', torch.cuda.current_device())
