@@ -82,6 +82,7 @@ extern "C" {
 #define ND_AMD_KERNEL_CHANGE_SEGMENTS 26  /* nd_amd_change_segments */
 #define ND_AMD_KERNEL_RASTERIZE       27  /* nd_amd_rasterize_polygons, the whole call (clear, fill, resolve) */
 #define ND_AMD_KERNEL_RESAMPLE        28  /* nd_amd_resample and nd_amd_resample_nearest */
+#define ND_AMD_KERNEL_SPECKLE         29  /* nd_amd_speckle_lee and nd_amd_speckle_multitemporal, the whole call */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -1027,6 +1028,90 @@ int nd_amd_resample_nearest(const void *src, void *dst, int elem_size, /* 1, 2, 
 int nd_amd_resample_check_table(const int32_t *start, const int32_t *count, int64_t m, /* output samples    */
                                 int64_t n, int taps,                   /* source samples, rows of weights   */
                                 void *hip_stream);
+
+/* ----------------------------------------------------------------------
+ * Speckle filters on detected (intensity) images: the local-statistics
+ * filter of Lee 1980 / Kuan et al. 1985 and the temporal filter of Quegan &
+ * Yu 2001.  The reference has no counterpart; the definition is this
+ * project's, and tests/speckle_ref.py restates it in numpy.
+ *
+ * Everything is float64, bracketed as written, no fma.  T is the data's type.
+ *
+ * Window sums.  A plane has ny x nx samples, w is odd, R = w / 2 (integer),
+ * N = double(w * w).  The border rule is scipy's 'reflect' (half-sample
+ * symmetric), extended periodically so that windows larger than the plane
+ * are defined:
+ *
+ *     refl(i, n):  p = i mod 2n (non-negative);  p if p < n else 2n - 1 - p
+ *
+ * The sums are separable; each window's sum is formed fresh, taps ascending,
+ * rows after columns:
+ *
+ *     h1[r, j] = 0;  for d = -R .. R:  h1[r, j] = h1[r, j] + double(x[r, refl(j + d, nx)])
+ *     h2[r, j] likewise over  double(x) * double(x)
+ *     S1[i, j] = 0;  for d = -R .. R:  S1[i, j] = S1[i, j] + h1[refl(i + d, ny), j]      (S2 from h2)
+ *
+ * No running sums, and no value is special-cased: a NaN, inf, zero or
+ * negative sample enters the sums as it is.
+ *
+ * nd_amd_speckle_lee, per plane, cu2 = 1 / looks computed by the caller:
+ *
+ *     m = S1 / N
+ *     v = S2 / N - m * m
+ *     q = ((m * m) * cu2) / v
+ *     b = 1 - q                        ND_AMD_SPECKLE_LEE   (Lee 1980 in the form of Lopes et al. 1990)
+ *     b = (1 - q) / (1 + cu2)          ND_AMD_SPECKLE_KUAN  (Kuan et al. 1985)
+ *     b = b  if (v > 0 and b > 0)  else 0              (a comparison with NaN is false)
+ *     out = T(m + b * (double(x) - m))                 (one rounding)
+ *
+ * nd_amd_speckle_multitemporal, per pixel over the k dates in order and the
+ * nvar variables (1 .. ND_AMD_SPECKLE_MAX_VARIABLES) in the order given:
+ *
+ *     r = 0
+ *     for t = 0 .. k-1:  for c = 0 .. nvar-1:  m[c,t] = S1[c,t] / N;  r = r + double(x[c,t]) / m[c,t]
+ *     out[c,t] = T((m[c,t] * r) / double(k * nvar))
+ *
+ * A zero local mean divides as it does.  With k * nvar <=
+ * ND_AMD_SPECKLE_HOT_MAX_PLANES the call is one launch that keeps every m in
+ * registers (one read, one write of the stack); beyond, pass 1 leaves r in the
+ * workspace (ny * nx float64; nd_amd_speckle_multitemporal_workspace_bytes,
+ * 0 where none is needed) and pass 2 forms m again.  Both give the same bits;
+ * k * nvar alone decides.
+ *
+ * Strides are 3 host values in elements for (plane or date, y, x), any
+ * non-negative values: crops and (y, x, time) data are read where they lie
+ * (the latter uncoalesced: not served natively, transpose with
+ * nd_amd_relayout_planar for speed).  The variables of a joint call share
+ * sizes and strides.  src and dst must not overlap.  A block owns a tile of
+ * ND_AMD_SPECKLE_TILE_Y x ND_AMD_SPECKLE_TILE_X outputs
+ * (ND_AMD_SPECKLE_HOT_TILE_Y rows in the one-launch multitemporal form).
+ * ND_AMD_EINVAL before any HIP call for null pointers, a bad dtype or method,
+ * negative sizes or strides, w < 1, cu2 not positive and finite, nvar < 1;
+ * ND_AMD_EUNSUPPORTED for an even w or w > ND_AMD_SPECKLE_MAX_W, more than
+ * ND_AMD_SPECKLE_MAX_VARIABLES variables and planes of 2^31 pixels or more;
+ * ND_AMD_EWORKSPACE for a missing or short workspace; ND_AMD_OK for an empty
+ * stack.
+ * ---------------------------------------------------------------------- */
+#define ND_AMD_SPECKLE_LEE  0
+#define ND_AMD_SPECKLE_KUAN 1
+#define ND_AMD_SPECKLE_MAX_W 31
+#define ND_AMD_SPECKLE_MAX_VARIABLES 4
+#define ND_AMD_SPECKLE_HOT_MAX_PLANES 32
+#define ND_AMD_SPECKLE_TILE_Y 32
+#define ND_AMD_SPECKLE_TILE_X 64
+#define ND_AMD_SPECKLE_HOT_TILE_Y 8
+
+int nd_amd_speckle_lee(const void *src, void *dst, int dtype,          /* ND_AMD_F32 or ND_AMD_F64          */
+                       int64_t nplanes, int64_t ny, int64_t nx,
+                       const int64_t *src_strides, const int64_t *dst_strides,
+                       int w, double cu2, int method, void *hip_stream);
+
+size_t nd_amd_speckle_multitemporal_workspace_bytes(int64_t ny, int64_t nx, int64_t k, int nvar);
+
+int nd_amd_speckle_multitemporal(const void *const *src, void *const *dst, int nvar,   /* nvar host pointers */
+                                 int dtype, int64_t k, int64_t ny, int64_t nx,
+                                 const int64_t *src_strides, const int64_t *dst_strides,
+                                 int w, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -22,7 +22,7 @@ KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose',
                 17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean',
                 21: 'classify_knn', 22: 'classify_linear', 23: 'kmeans_step', 24: 'feature_moments',
-                25: 'gather_rows', 26: 'change_segments', 27: 'rasterize', 28: 'resample'}
+                25: 'gather_rows', 26: 'change_segments', 27: 'rasterize', 28: 'resample', 29: 'speckle'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 STRUCT_DIAG, STRUCT_C2, STRUCT_C3 = 0, 1, 2
 
@@ -47,12 +47,17 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_kmeans_fit_workspace_bytes', 'nd_amd_kmeans_step', 'nd_amd_feature_moments',
            'nd_amd_gather_rows',
            'nd_amd_rasterize_workspace_bytes', 'nd_amd_rasterize_polygons',
-           'nd_amd_resample', 'nd_amd_resample_nearest', 'nd_amd_resample_check_table')
+           'nd_amd_resample', 'nd_amd_resample_nearest', 'nd_amd_resample_check_table',
+           'nd_amd_speckle_lee', 'nd_amd_speckle_multitemporal_workspace_bytes', 'nd_amd_speckle_multitemporal')
 CLASSIFY_BLOCK_ROWS, CLASSIFY_MAX_FEATURES = 1024, 1024
 CLASSIFY_KNN_MAX_K, CLASSIFY_KNN_MAX_FEATURES, CLASSIFY_KNN_TILE = 32, 128, 8
 KMEANS_FIT_MAX_ACC = 4096
 RASTERIZE_MAX_CROSSINGS = 256
 RESAMPLE_MAX_TAPS = 256
+SPECKLE_METHODS = {'lee': 0, 'kuan': 1}
+# include/nd_amd.h: ND_AMD_SPECKLE_MAX_W, _MAX_VARIABLES, _HOT_MAX_PLANES, _TILE_Y, _TILE_X, _HOT_TILE_Y
+SPECKLE_MAX_W, SPECKLE_MAX_VARIABLES, SPECKLE_HOT_MAX_PLANES = 31, 4, 32
+SPECKLE_TILE_Y, SPECKLE_TILE_X, SPECKLE_HOT_TILE_Y = 32, 64, 8
 LINKS = {'none': 0, 'softmax': 1, 'ovr': 2}
 LINEAR_OUTPUTS = {'predict': 0, 'decision_function': 1, 'predict_proba': 2}
 
@@ -204,6 +209,13 @@ def lib():
     L.nd_amd_resample_nearest.argtypes = [vp, vp, i32] + grid + [vp] * 4 + [vp, vp]
     L.nd_amd_resample_check_table.restype = i32
     L.nd_amd_resample_check_table.argtypes = [vp, vp, i64, i64, i32, vp]
+    L.nd_amd_speckle_lee.restype = i32
+    L.nd_amd_speckle_lee.argtypes = [vp, vp, i32, i64, i64, i64, pi64, pi64, i32, dbl, i32, vp]
+    L.nd_amd_speckle_multitemporal_workspace_bytes.restype = C.c_size_t
+    L.nd_amd_speckle_multitemporal_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    L.nd_amd_speckle_multitemporal.restype = i32
+    L.nd_amd_speckle_multitemporal.argtypes = [C.POINTER(vp), C.POINTER(vp), i32, i32, i64, i64, i64, pi64, pi64,
+                                               i32, vp, C.c_size_t, vp]
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

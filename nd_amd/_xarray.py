@@ -2,7 +2,7 @@
 nd_amd/_xarray.py -- optional xarray accessors mirroring nd/_xarray.py:135-161 for the algorithms
 this package provides: `ds.nd_amd.change_omnibus(...)`, `ds.nd_amd.nlmeans(...)`,
 `ds.nd_amd.boxcar(...)`, `ds.nd_amd.convolve(...)`, `ds.nd_amd.gaussian(...)`, `ds.nd_amd.to_rgb(...)`,
-`ds.nd_amd.resample(...)`, `ds.nd_amd.reproject(...)`.
+`ds.nd_amd.resample(...)`, `ds.nd_amd.reproject(...)`, `ds.nd_amd.lee(...)`, `ds.nd_amd.multitemporal(...)`.
 
 Registered only when xarray is importable (it is not installed in the build or GPU images); the
 accessor name differs from the reference's (`nd`, `filter`) so both can be loaded side by side.
@@ -20,6 +20,8 @@ _METHODS = {
     'boxcar': ('filters', 'boxcar'),
     'convolve': ('filters', 'convolution'),
     'gaussian': ('filters', 'gaussian'),
+    'lee': ('filters', 'lee'),
+    'multitemporal': ('filters', 'multitemporal'),
     'resample': ('warp', 'resample'),
     'reproject': ('warp', 'reproject'),
 }

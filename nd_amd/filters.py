@@ -9,6 +9,8 @@ nd_amd/filters.py -- the reference's filter classes (nd/filters.py) with the ari
   NLMeansFilter      nd/filters.py:388-466 -> nd_amd_nlmeans3d
   GaussianFilter     nd/filters.py:308-378 -> scipy.ndimage.gaussian_filter restated as one
                      nd_amd_correlate1d pass per filtered axis
+  LeeFilter          extension (no reference counterpart): Lee / Kuan local statistics -> nd_amd_speckle_lee
+  MultitemporalFilter  extension: Quegan & Yu 2001 over all dates -> nd_amd_speckle_multitemporal
 
 Arrays may be numpy (copied to the device and back: the drop-in case) or torch ROCm tensors
 (device-resident pipelines, no host copies).
@@ -23,7 +25,8 @@ from .algorithm import Algorithm, parallelize, wrap_algorithm
 from .io import assemble_complex, disassemble_complex
 
 __all__ = ['Filter', 'ConvolutionFilter', 'convolution', 'BoxcarFilter', 'boxcar',
-           'GaussianFilter', 'gaussian', 'NLMeansFilter', 'nlmeans', '_expand_kernel']
+           'GaussianFilter', 'gaussian', 'NLMeansFilter', 'nlmeans', 'LeeFilter', 'lee',
+           'MultitemporalFilter', 'multitemporal', 'multitemporal_looks', '_expand_kernel']
 
 
 def _expand_kernel(kernel, kernel_dims, new_dims):
@@ -498,3 +501,229 @@ class NLMeansFilter(Filter):
 
 
 nlmeans = wrap_algorithm(NLMeansFilter, 'nlmeans')
+
+
+# ---- adaptive speckle filters ----------------------------------------------------------------
+
+multitemporal_looks = kernels.multitemporal_looks
+
+
+def _is_integer(values):
+    if _device.is_tensor(values):
+        return not (values.is_floating_point() or values.is_complex())
+    return np.asarray(values).dtype.kind in 'iub'
+
+
+def _as_float64(values):
+    return values.to(torch.float64) if _device.is_tensor(values) else np.asarray(values).astype(np.float64)
+
+
+def _replace_values(da, values):
+    """`da` with other values (possibly of another dtype), everything else kept."""
+    from . import xr_lite
+    if _adapter.namespace(da) is xr_lite:
+        return xr_lite.DataArray(values, da.dims, da.coords, da.attrs, da.name)
+    return da.copy(deep=False, data=values)
+
+
+class _SpeckleFilter(Filter):
+    """What LeeFilter and MultitemporalFilter share: they filter intensities, so a complex variable is an error
+    (raised before Filter.apply would split it into two real halves and filter those), and integers are computed
+    and returned as float64."""
+
+    window_dims = ()
+
+    def apply(self, ds, inplace=False, *, njobs=1, devices=None):
+        self._check(ds)
+        return Filter.apply(self, ds, inplace=inplace, njobs=njobs, devices=devices)
+
+    apply.__doc__ = Filter.apply.__doc__
+
+    def _touched(self, ds):
+        if _adapter.is_dataarray(ds):
+            return [ds]
+        return [ds[n] for n in _adapter.get_vars_for_dims(ds, self.dims)]
+
+    def _check(self, ds):
+        for v in self._touched(ds):
+            if _adapter.iscomplexobj(v.values):
+                raise TypeError('%s filters intensities, variable %r is complex: filter |z|^2 or the covariance '
+                                'diagonal, or split it knowingly with io.disassemble_complex'
+                                % (type(self).__name__, v.name))
+
+    def _buffer(self, dim):
+        """Rows of context a chunk needs on each side along `dim`: half the window."""
+        return self.w // 2 if dim in self.window_dims else 0
+
+    def _run(self, da):
+        src = _as_float64(da.values) if _is_integer(da.values) else da.values
+        blank = torch.empty_like(src) if _device.is_tensor(src) else np.empty_like(src)
+        self._filter(src, self._axes_in(tuple(da.dims)), output=blank)
+        return _replace_values(da, blank)
+
+    def _apply_array(self, da):
+        return self._run(da)
+
+    def _apply_each(self, ds):
+        out = ds.copy(deep=False)
+        names = _adapter.get_vars_for_dims(ds, self.dims)
+        for name in ds.data_vars:
+            out[name] = self._run(ds[name]) if name in names else ds[name].copy(deep=True)
+        return out
+
+    @staticmethod
+    def _on_device(arr, output, run):
+        """run(t, out_t) with `arr` on the device and a device output; host in means host out."""
+        dev = _device.device_of(arr, output)
+        with torch.cuda.device(dev):
+            t = _device.to_device(arr, dev)
+            out_t = output if _device.is_tensor(output) else torch.empty_like(t)
+            run(t, out_t)
+            if out_t is not output:
+                _device.write_back(out_t, output)
+
+
+def _pixel_major_through_planar(t, out_t, axes_yx, run):
+    """(y, x, time) data that the transpose kernels take: filter a planar copy (lanes along x) and transpose the
+    result back.  -> False where the data is not of that kind and nothing was done."""
+    if t.dim() != 3 or tuple(axes_yx) != (0, 1) or t.numel() < (1 << 16):
+        return False
+    planar = torch.empty((t.shape[2], t.shape[0], t.shape[1]), dtype=t.dtype, device=t.device)
+    if not kernels.relayout_planar(t, planar):
+        return False
+    done = run(planar)
+    if not kernels.relayout_pixel_major(done, out_t):
+        out_t.copy_(done.permute(1, 2, 0))
+    return True
+
+
+class LeeFilter(_SpeckleFilter):
+    """The local-statistics speckle filter of Lee (1980) and Kuan et al. (1985) over a `w` x `w` window, per
+    variable and per plane (README "Speckle filters" has the definition).  An extension: the reference has none.
+
+    dims    the two window dimensions (default ('y', 'x'))
+    w       odd window width, 1 to 31
+    looks   equivalent number of looks of the intensities, any positive real
+    method  'lee': b = 1 - Cu^2 / Cx^2;  'kuan': the same divided by 1 + Cu^2
+
+    The output feeds Classifier and to_rgb.  It is no longer gamma distributed with `looks` looks: OmnibusTest
+    keeps taking the unfiltered (or multilooked) stack."""
+
+    def __init__(self, dims=('y', 'x'), w=7, looks=1, method='lee'):
+        self.dims = tuple(dims)
+        if len(self.dims) != 2:
+            raise ValueError('LeeFilter works on two window dimensions, got %r' % (self.dims,))
+        self.window_dims = self.dims
+        self.w = kernels.speckle_window(w)
+        if not float(looks) > 0 or not np.isfinite(1.0 / float(looks)):
+            raise ValueError('looks must be positive, got %r' % (looks,))
+        if method not in ('lee', 'kuan'):
+            raise ValueError("method must be 'lee' or 'kuan', got %r" % (method,))
+        self.looks, self.method = float(looks), method
+
+    def _parallel_dimension(self, ds):
+        return _split_dimension(self, ds)
+
+    def _filter(self, arr, axes, output):
+        names = ['d%d' % d for d in range(np.ndim(arr))]
+        names[axes[0]], names[axes[1]] = 'y', 'x'
+
+        def run(t, out_t):
+            def planar(p):
+                return kernels.speckle_lee(p, self.w, self.looks, self.method, dims=('time', 'y', 'x'))
+            if not _pixel_major_through_planar(t, out_t, axes, planar):
+                kernels.speckle_lee(t, self.w, self.looks, self.method, out=out_t, dims=names)
+
+        self._on_device(arr, output, run)
+
+
+lee = wrap_algorithm(LeeFilter, 'lee')
+
+
+class MultitemporalFilter(_SpeckleFilter):
+    """The multitemporal speckle filter of Quegan & Yu (2001): every date is replaced by its `w` x `w` local
+    mean times the average over all dates of the ratio of the date to its local mean.  It trades the time axis
+    for looks without losing spatial resolution (README "Speckle filters" has the definition).  An extension.
+
+    dims    the two window dimensions (default ('y', 'x'))
+    w       odd window width, 1 to 31
+    time    name of the date dimension; variables without it pass through
+    joint   True: one ratio average over all (up to 4) variables that carry `time` and `dims`, which must share
+            type, shape and dims.  False: one variable at a time.
+
+    multitemporal_looks(looks, k, w, variables) is the ENL of the output in homogeneous speckle.  The output is
+    no longer gamma distributed and its dates are correlated: OmnibusTest keeps taking the unfiltered stack."""
+
+    def __init__(self, dims=('y', 'x'), w=7, time='time', joint=False):
+        self.window_dims = tuple(dims)
+        if len(self.window_dims) != 2 or time in self.window_dims:
+            raise ValueError('MultitemporalFilter works on two window dimensions and `time`, got %r and %r'
+                             % (self.window_dims, time))
+        self.time = time
+        self.dims = self.window_dims + (time,)       # `_axes_in` hands `_filter` the time axis as well
+        self.w = kernels.speckle_window(w)
+        self.joint = bool(joint)
+        self.per_variable = not self.joint
+
+    def _parallel_dimension(self, ds):
+        """The longer window dimension, never `time`: a chunk in time would change the average over the dates."""
+        return _largest_dim(ds, self.window_dims)
+
+    def _check(self, ds):
+        if self.time not in ds.dims:
+            raise KeyError('MultitemporalFilter needs the dimension %r; the data has %s'
+                           % (self.time, tuple(ds.dims)))
+        _SpeckleFilter._check(self, ds)
+        touched = self._touched(ds)
+        for v in touched:
+            if len(v.dims) != 3:
+                raise NotImplementedError('variable %r has dims %s: (time, y, x) in any order is served'
+                                          % (v.name, tuple(v.dims)))
+        if self.joint and not _adapter.is_dataarray(ds):
+            if len(touched) > kernels.SPECKLE_MAX_VARIABLES:
+                raise NotImplementedError('joint=True over %d variables: at most %d are served'
+                                          % (len(touched), kernels.SPECKLE_MAX_VARIABLES))
+            v0 = touched[0] if touched else None
+            for v in touched:
+                if (tuple(v.dims) != tuple(v0.dims) or tuple(v.shape) != tuple(v0.shape)
+                        or _device.np_dtype(v.values) != _device.np_dtype(v0.values)):
+                    raise NotImplementedError('joint=True needs variables of one type, shape and dims; %r and %r '
+                                              'differ' % (v0.name, v.name))
+
+    def _names(self, axes, ndim):
+        names = [None] * ndim
+        names[axes[0]], names[axes[1]], names[axes[2]] = 'y', 'x', 'time'
+        return names
+
+    def _filter(self, arr, axes, output):
+        names = self._names(axes, np.ndim(arr))
+
+        def run(t, out_t):
+            def planar(p):
+                return kernels.speckle_multitemporal(p, self.w, dims=('time', 'y', 'x'))
+            if not _pixel_major_through_planar(t, out_t, axes[:2], planar):
+                kernels.speckle_multitemporal(t, self.w, dims=names, out=out_t)
+
+        self._on_device(arr, output, run)
+
+    def _apply_stacked(self, ds):
+        """joint=True: the variables' tensors go to the kernel where they lie, nothing is stacked."""
+        names = _adapter.get_vars_for_dims(ds, self.dims)
+        out = ds.copy(deep=False)
+        if names:
+            v0 = ds[names[0]]
+            dims = self._names(self._axes_in(tuple(v0.dims)), 3)
+            values = [ds[n].values for n in names]
+            dev = _device.device_of(*values)
+            with torch.cuda.device(dev):
+                planes = [_device.to_device(v, dev) for v in values]
+                done = kernels.speckle_multitemporal(planes, self.w, dims=dims)
+                for n, v, t in zip(names, values, done):
+                    out[n] = _replace_values(ds[n], t if _device.is_tensor(v) else _device.to_host(t))
+        for n in ds.data_vars:
+            if n not in names:
+                out[n] = ds[n].copy(deep=True)
+        return out
+
+
+multitemporal = wrap_algorithm(MultitemporalFilter, 'multitemporal')

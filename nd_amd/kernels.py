@@ -1793,6 +1793,178 @@ def resample_check_table(table, device=None):
                                                           _stream_ptr(dev)))
 
 
+# ---------------------------------------------------------------------------
+# speckle filters (include/nd_amd.h "Speckle filters"; tests/speckle_ref.py restates them)
+# ---------------------------------------------------------------------------
+SPECKLE_MAX_W = _lib.SPECKLE_MAX_W
+SPECKLE_MAX_VARIABLES = _lib.SPECKLE_MAX_VARIABLES
+SPECKLE_HOT_MAX_PLANES = _lib.SPECKLE_HOT_MAX_PLANES
+SPECKLE_TILE = (_lib.SPECKLE_TILE_Y, _lib.SPECKLE_TILE_X)          # outputs a block owns: rows, columns
+SPECKLE_HOT_TILE = (_lib.SPECKLE_HOT_TILE_Y, _lib.SPECKLE_TILE_X)  # the same in the one-launch multitemporal form
+
+
+def speckle_window(w):
+    """w as an int if it is an odd window of 1 ... SPECKLE_MAX_W samples, ValueError otherwise."""
+    if isinstance(w, bool) or int(w) != w:
+        raise ValueError('w must be an odd integer from 1 to %d, got %r' % (SPECKLE_MAX_W, w))
+    w = int(w)
+    if w < 1 or w % 2 == 0 or w > SPECKLE_MAX_W:
+        raise ValueError('w must be an odd integer from 1 to %d, got %d' % (SPECKLE_MAX_W, w))
+    return w
+
+
+def multitemporal_looks(looks, k, w, variables=1):
+    """Equivalent number of looks of MultitemporalFilter's output in homogeneous speckle of `looks` looks
+    (Quegan & Yu 2001): M N L / (M + N - 1) with M = k * variables planes and N = w * w window samples."""
+    m, n = float(k * variables), float(w * w)
+    return m * n * float(looks) / (m + n - 1.0)
+
+
+def _speckle_data(t, name):
+    if not torch.is_tensor(t):
+        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    if not t.is_cuda:
+        raise ValueError('%s must live on a ROCm device (got %s); nd_amd has no CPU path' % (name, t.device))
+    if t.is_complex():
+        raise TypeError('%s is complex: the speckle filters work on intensities' % name)
+    if t.dtype not in _DT:
+        if t.is_floating_point():
+            raise TypeError('%s must be float32, float64 or an integer type, got %s' % (name, t.dtype))
+        t = t.to(torch.float64)                       # integers are computed and returned as float64
+    return t
+
+
+def _speckle_out(out, like, name='out'):
+    if out is None:
+        return _empty_like_strides(like, list(like.shape))
+    if (not torch.is_tensor(out) or out.shape != like.shape or out.dtype != like.dtype
+            or out.device != like.device):
+        raise ValueError('%s must be %s of %s on %s' % (name, tuple(like.shape), like.dtype, like.device))
+    if any(s == 0 and n > 1 for s, n in zip(out.stride(), out.shape)):
+        raise ValueError('an expanded %s (stride 0) is not served' % name)
+    if _may_overlap(out, like):
+        raise ValueError('%s must not overlap its source' % name)
+    return out
+
+
+def _speckle_plane_limit(ny, nx):
+    if ny * nx >= 2 ** 31:
+        raise NotImplementedError('planes of 2^31 pixels or more are not served (%d x %d)' % (ny, nx))
+
+
+def speckle_lee(inp, w, looks, method='lee', out=None, dims=None):
+    """The local-statistics speckle filter of Lee / Kuan over a w x w window of every (y, x) plane of `inp`
+    (include/nd_amd.h has the definition).  inp: a ROCm tensor of float32 or float64 (integers are computed and
+    returned as float64) whose axes `dims` names, 'y' and 'x' among them -- by default ('y', 'x') for two axes
+    and ('time', 'y', 'x') for three; any strides, crops of larger tensors included.  looks: the ENL of the
+    intensities, any positive real.  method: 'lee' or 'kuan'.  out: a tensor of the input's shape and type, any
+    strides, not overlapping it.  -> out"""
+    w = speckle_window(w)
+    if method not in _lib.SPECKLE_METHODS:
+        raise ValueError("method must be 'lee' or 'kuan', got %r" % (method,))
+    if not float(looks) > 0 or not np.isfinite(1.0 / float(looks)):
+        raise ValueError('looks must be positive, got %r' % (looks,))
+    cu2 = 1.0 / float(looks)
+    inp = _speckle_data(inp, 'inp')
+    if dims is None:
+        dims = {2: ('y', 'x'), 3: ('time', 'y', 'x')}.get(inp.dim())
+        if dims is None:
+            raise ValueError('dims must name the %d axes of inp' % inp.dim())
+    dims = tuple(dims)
+    if len(dims) != inp.dim() or len(set(dims)) != len(dims) or 'y' not in dims or 'x' not in dims:
+        raise ValueError("dims must name the tensor's %d axes, 'y' and 'x' among them, got %r" % (inp.dim(), dims))
+    ay, ax = dims.index('y'), dims.index('x')
+    ny, nx = inp.shape[ay], inp.shape[ax]
+    _speckle_plane_limit(ny, nx)
+    out = _speckle_out(out, inp)
+    dev = inp.device
+    # the batch axis of a call is the last axis besides y and x; axes before it are walked on the host
+    rest = [d for d in range(inp.dim()) if d not in (ay, ax)]
+    order = rest + [ay, ax]
+    src, dst = inp.permute(*order), out.permute(*order)
+    if not rest:
+        src, dst = src[None], dst[None]
+    lead = src.shape[:-3]
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        for idx in np.ndindex(*lead):
+            s, d = src[idx], dst[idx]
+            _lib.check(L.nd_amd_speckle_lee(_ptr(s), _ptr(d), _DT[inp.dtype], s.shape[0], ny, nx,
+                                            _lib.i64_array(s.stride()), _lib.i64_array(d.stride()), w, cu2,
+                                            _lib.SPECKLE_METHODS[method], _stream_ptr(dev)))
+        _record([inp, out], dev)
+    return out
+
+
+def speckle_multitemporal(planes, w, dims=('time', 'y', 'x'), out=None):
+    """The multitemporal speckle filter of Quegan & Yu 2001 over a w x w window and all dates (include/nd_amd.h
+    has the definition).  planes: one ROCm tensor with the three axes `dims` names, or a list of up to
+    SPECKLE_MAX_VARIABLES of them, which are filtered jointly, in the list's order within a date; float32 or
+    float64 (integers are computed and returned as float64), any strides.  Up to SPECKLE_HOT_MAX_PLANES
+    planes (dates x variables) are filtered in one launch, more in two passes with the same result.
+    out: a tensor (or list) of the inputs' shape and type.  -> a tensor, or a list where a list was given."""
+    w = speckle_window(w)
+    single = torch.is_tensor(planes)
+    planes = [planes] if single else list(planes)
+    if not planes:
+        return []
+    planes = [_speckle_data(t, 'planes[%d]' % i) for i, t in enumerate(planes)]
+    p0 = planes[0]
+    dims = tuple(dims)
+    if sorted(dims) != ['time', 'x', 'y'] or p0.dim() != 3:
+        raise ValueError("dims must be a permutation of ('time', 'y', 'x') naming the three axes of the data")
+    if len(planes) > SPECKLE_MAX_VARIABLES:
+        raise NotImplementedError('%d variables: at most %d are filtered jointly'
+                                  % (len(planes), SPECKLE_MAX_VARIABLES))
+    for t in planes:
+        if t.shape != p0.shape or t.dtype != p0.dtype or t.device != p0.device:
+            raise NotImplementedError('variables filtered jointly share shape, type and device')
+    at, ay, ax = dims.index('time'), dims.index('y'), dims.index('x')
+    k, ny, nx = p0.shape[at], p0.shape[ay], p0.shape[ax]
+    _speckle_plane_limit(ny, nx)
+    if out is None:
+        outs = [None] * len(planes)
+    else:
+        outs = [out] if torch.is_tensor(out) else list(out)
+        if len(outs) != len(planes):
+            raise ValueError('out must hold one tensor per variable')
+
+    def same_strides(ts):
+        return all(a == b for t in ts for a, b, n in zip(t.stride(), ts[0].stride(), t.shape) if n > 1)
+
+    # one set of strides per call: variables that lie differently in memory are packed first
+    if not same_strides(planes):
+        planes = [t.contiguous() for t in planes]
+        p0 = planes[0]
+    outs = [_speckle_out(o, t, 'out[%d]' % i) for i, (o, t) in enumerate(zip(outs, planes))]
+    given = outs
+    if not same_strides(outs):
+        outs = [torch.empty_like(p0, memory_format=torch.contiguous_format) for _ in planes]
+    for o in outs:
+        for t in planes:
+            if _may_overlap(o, t):
+                raise ValueError('out must not overlap a source')
+    dev = p0.device
+    nvar = len(planes)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = int(L.nd_amd_speckle_multitemporal_workspace_bytes(ny, nx, k, nvar))
+        work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+        src = (C.c_void_p * nvar)(*[t.data_ptr() for t in planes])
+        dst = (C.c_void_p * nvar)(*[o.data_ptr() for o in outs])
+
+        def strides(t):
+            return _lib.i64_array([t.stride(at), t.stride(ay), t.stride(ax)])
+
+        _lib.check(L.nd_amd_speckle_multitemporal(src, dst, nvar, _DT[p0.dtype], k, ny, nx, strides(p0),
+                                                  strides(outs[0]), w, _ptr(work), nbytes, _stream_ptr(dev)))
+        _record(planes + outs + [work], dev)
+        for g, o in zip(given, outs):
+            if g is not o:
+                g.copy_(o)
+    return given[0] if single else given
+
+
 def _lib_device(device=None):
     if device is not None:
         return torch.device(device)
