@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "classify_common.hpp"
+#include "dispatch.hpp"
 
 using namespace nd_amd;
 
@@ -632,21 +633,6 @@ static int grid_for(int64_t rows)
     return (int)(b < 8192 ? b : 8192);
 }
 
-template <typename T, int NREG>
-static void launch_forest(int nc_slot, int grid, hipStream_t st, const void *const *tab, int nfeat, const RowDims &R,
-                          int64_t rows, const int4 *nodes, const double *values, const int32_t *roots, int ntrees,
-                          const double *classes, int nclasses, const double *mean, const double *scale,
-                          double *labels, double *proba)
-{
-#define ND_FOREST(NC)                                                                                          \
-    hipLaunchKernelGGL((classify_forest_kernel<T, NREG, NC>), dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, \
-                       nodes, values, roots, ntrees, classes, nclasses, mean, scale, labels, proba)
-    if (nc_slot == 2) ND_FOREST(2);
-    else if (nc_slot == 4) ND_FOREST(4);
-    else ND_FOREST(8);
-#undef ND_FOREST
-}
-
 }  // namespace
 
 extern "C" size_t nd_amd_classify_workspace_bytes(int nfeat)
@@ -685,22 +671,22 @@ extern "C" int nd_amd_classify_forest(const void *const *feat, int nfeat, int dt
     hipStream_t st = (hipStream_t)hip_stream;
     ND_HIP_CHECK(hipMemcpyAsync(workspace, feat, (size_t)nfeat * sizeof(void *), hipMemcpyHostToDevice, st));
     const void *const *tab = (const void *const *)workspace;
-    const int slot = nclasses <= 2 ? 2 : (nclasses <= 4 ? 4 : 8);
     const int grid = grid_for(rows);
     const int4 *nd = (const int4 *)nodes;
     {
         KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_FOREST, st);
-#define ND_ARGS slot, grid, st, tab, nfeat, R, rows, nd, values, roots, ntrees, classes, nclasses, mean, scale, labels, proba
-        if (dtype == ND_AMD_F32) {
-            if (nfeat <= 4) launch_forest<float, 4>(ND_ARGS);
-            else if (nfeat <= 8) launch_forest<float, 8>(ND_ARGS);
-            else launch_forest<float, 0>(ND_ARGS);
-        } else {
-            if (nfeat <= 4) launch_forest<double, 4>(ND_ARGS);
-            else if (nfeat <= 8) launch_forest<double, 8>(ND_ARGS);
-            else launch_forest<double, 0>(ND_ARGS);
-        }
-#undef ND_ARGS
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            auto features = [&](auto NREG) {
+                auto launch = [&](auto NC) {
+                    hipLaunchKernelGGL((classify_forest_kernel<T, decltype(NREG)::value, decltype(NC)::value>), dim3(grid),
+                                       dim3(BLOCK), 0, st, tab, nfeat, R, rows, nd, values, roots, ntrees, classes, nclasses,
+                                       mean, scale, labels, proba);
+                };
+                if (!pick_le<2, 4>(nclasses, launch)) launch(int_c<8>{});
+            };
+            if (!pick_le<4, 8>(nfeat, features)) features(int_c<0>{});
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;
@@ -733,19 +719,14 @@ extern "C" int nd_amd_classify_kmeans(const void *const *feat, int nfeat, int dt
     const int grid = grid_for(rows);
     {
         KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_KMEANS, st);
-#define ND_KMEANS(T, NREG)                                                                                      \
-    hipLaunchKernelGGL((classify_kmeans_kernel<T, NREG>), dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, \
-                       centers, k, mean, scale, labels)
-        if (dtype == ND_AMD_F32) {
-            if (nfeat <= 4) ND_KMEANS(float, 4);
-            else if (nfeat <= 8) ND_KMEANS(float, 8);
-            else ND_KMEANS(float, 0);
-        } else {
-            if (nfeat <= 4) ND_KMEANS(double, 4);
-            else if (nfeat <= 8) ND_KMEANS(double, 8);
-            else ND_KMEANS(double, 0);
-        }
-#undef ND_KMEANS
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            auto launch = [&](auto NREG) {
+                hipLaunchKernelGGL((classify_kmeans_kernel<T, decltype(NREG)::value>), dim3(grid), dim3(BLOCK), 0, st, tab, nfeat,
+                                   R, rows, centers, k, mean, scale, labels);
+            };
+            if (!pick_le<4, 8>(nfeat, launch)) launch(int_c<0>{});
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;
@@ -777,12 +758,11 @@ extern "C" int nd_amd_classify_select(const void *const *feat, int nfeat, int dt
     const int64_t nblocks = ceil_div(rows, ND_AMD_CLASSIFY_BLOCK_ROWS);
     {
         KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_GATHER, st);
-        if (dtype == ND_AMD_F32)
-            hipLaunchKernelGGL(classify_select_kernel<float>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat,
-                               R, rows, labels, mask, block_offsets);
-        else
-            hipLaunchKernelGGL(classify_select_kernel<double>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat,
-                               R, rows, labels, mask, block_offsets);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            hipLaunchKernelGGL(classify_select_kernel<T>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat, R, rows,
+                               labels, mask, block_offsets);
+        });
         hipLaunchKernelGGL(classify_scan_kernel, dim3(1), dim3(BLOCK), 0, st, block_offsets, nblocks, count);
     }
     ND_HIP_CHECK(hipGetLastError());
@@ -812,12 +792,11 @@ extern "C" int nd_amd_classify_gather(const void *const *feat, int nfeat, int dt
     const int64_t nblocks = ceil_div(rows, ND_AMD_CLASSIFY_BLOCK_ROWS);
     {
         KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_GATHER, st);
-        if (dtype == ND_AMD_F32)
-            hipLaunchKernelGGL(classify_gather_kernel<float>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat,
-                               R, rows, labels, mask, block_offsets, (float *)X, y);
-        else
-            hipLaunchKernelGGL(classify_gather_kernel<double>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat,
-                               R, rows, labels, mask, block_offsets, (double *)X, y);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            hipLaunchKernelGGL(classify_gather_kernel<T>, dim3((unsigned)nblocks), dim3(BLOCK), 0, st, tab, nfeat, R, rows,
+                               labels, mask, block_offsets, (T *)X, y);
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;
@@ -871,19 +850,15 @@ extern "C" int nd_amd_class_stats(const void *var, int dtype, const int64_t *siz
     unsigned long long *c = (unsigned long long *)count, *nn = (unsigned long long *)nan_count;
     {
         KernelTimer timer(ND_AMD_KERNEL_CLASS_MEAN, st);
-#define ND_STATS(T, MODE)                                                                                     \
-    hipLaunchKernelGGL((class_stats_kernel<T, MODE>), dim3(grid), dim3(BLOCK), 0, st, (const T *)var, R, rows, \
-                       labels, nclasses, sum, c, nn)
-        if (dtype == ND_AMD_F32) {
-            if (nclasses <= STATS_REG_CLASSES) ND_STATS(float, 0);
-            else if (nclasses <= STATS_LDS_CLASSES) ND_STATS(float, 1);
-            else ND_STATS(float, 2);
-        } else {
-            if (nclasses <= STATS_REG_CLASSES) ND_STATS(double, 0);
-            else if (nclasses <= STATS_LDS_CLASSES) ND_STATS(double, 1);
-            else ND_STATS(double, 2);
-        }
-#undef ND_STATS
+        const int mode = nclasses <= STATS_REG_CLASSES ? 0 : (nclasses <= STATS_LDS_CLASSES ? 1 : 2);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            auto launch = [&](auto MODE) {
+                hipLaunchKernelGGL((class_stats_kernel<T, decltype(MODE)::value>), dim3(grid), dim3(BLOCK), 0, st, (const T *)var,
+                                   R, rows, labels, nclasses, sum, c, nn);
+            };
+            if (!pick_eq<0, 1>(mode, launch)) launch(int_c<2>{});
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;
@@ -907,12 +882,11 @@ extern "C" int nd_amd_class_fill(const void *var, void *out, int dtype, const in
     const int grid = grid_for(rows);
     {
         KernelTimer timer(ND_AMD_KERNEL_CLASS_MEAN, st);
-        if (dtype == ND_AMD_F32)
-            hipLaunchKernelGGL(class_fill_kernel<float>, dim3(grid), dim3(BLOCK), 0, st, (const float *)var,
-                               (float *)out, R, rows, labels, nclasses, (const float *)fill);
-        else
-            hipLaunchKernelGGL(class_fill_kernel<double>, dim3(grid), dim3(BLOCK), 0, st, (const double *)var,
-                               (double *)out, R, rows, labels, nclasses, (const double *)fill);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            hipLaunchKernelGGL(class_fill_kernel<T>, dim3(grid), dim3(BLOCK), 0, st, (const T *)var, (T *)out, R, rows, labels,
+                               nclasses, (const T *)fill);
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;
@@ -924,50 +898,6 @@ static int knn_block_rows(int nfeat, size_t elem)
     int r = BLOCK;
     while (r > 64 && (size_t)r * nfeat * elem > (size_t)KNN_LDS_BYTES) r >>= 1;
     return r;
-}
-
-template <typename T, int NF>
-static void launch_knn(int cap, int grid, int block, size_t lds, hipStream_t st, const void *const *tab, int nfeat,
-                       const RowDims &R, int64_t rows, const double *train, const int32_t *target, int ntrain, int k,
-                       const double *classes, int nclasses, const double *mean, const double *scale, double *labels,
-                       double *proba)
-{
-#define ND_KNN(CAP)                                                                                              \
-    hipLaunchKernelGGL((classify_knn_kernel<T, NF, CAP>), dim3(grid), dim3(block), lds, st, tab, nfeat, R, rows, \
-                       train, target, ntrain, k, classes, nclasses, mean, scale, labels, proba)
-    if (cap <= 1) ND_KNN(1);
-    else if (cap <= 2) ND_KNN(2);
-    else if (cap <= 4) ND_KNN(4);
-    else if (cap <= 8) ND_KNN(8);
-    else if (cap <= 16) ND_KNN(16);
-    else ND_KNN(32);
-#undef ND_KNN
-}
-
-template <typename T>
-static void launch_knn_features(int nfeat, int cap, int64_t rows, hipStream_t st, const void *const *tab,
-                                const RowDims &R, const double *train, const int32_t *target, int ntrain, int k,
-                                const double *classes, int nclasses, const double *mean, const double *scale,
-                                double *labels, double *proba)
-{
-#define ND_ARGS st, tab, nfeat, R, rows, train, target, ntrain, k, classes, nclasses, mean, scale, labels, proba
-    const int grid = grid_for(rows);
-    switch (nfeat) {
-    case 1: launch_knn<T, 1>(cap, grid, BLOCK, 0, ND_ARGS); break;
-    case 2: launch_knn<T, 2>(cap, grid, BLOCK, 0, ND_ARGS); break;
-    case 3: launch_knn<T, 3>(cap, grid, BLOCK, 0, ND_ARGS); break;
-    case 4: launch_knn<T, 4>(cap, grid, BLOCK, 0, ND_ARGS); break;
-    case 5: launch_knn<T, 5>(cap, grid, BLOCK, 0, ND_ARGS); break;
-    case 6: launch_knn<T, 6>(cap, grid, BLOCK, 0, ND_ARGS); break;
-    case 7: launch_knn<T, 7>(cap, grid, BLOCK, 0, ND_ARGS); break;
-    case 8: launch_knn<T, 8>(cap, grid, BLOCK, 0, ND_ARGS); break;
-    default: {
-        const int block = knn_block_rows(nfeat, sizeof(T));
-        const int64_t b = ceil_div(rows, block);
-        launch_knn<T, 0>(cap, (int)(b < 8192 ? b : 8192), block, (size_t)block * nfeat * sizeof(T), ND_ARGS);
-    }
-    }
-#undef ND_ARGS
 }
 
 extern "C" int nd_amd_classify_knn(const void *const *feat, int nfeat, int dtype, const int64_t *sizes,
@@ -1006,12 +936,27 @@ extern "C" int nd_amd_classify_knn(const void *const *feat, int nfeat, int dtype
     const void *const *tab = (const void *const *)workspace;
     {
         KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_KNN, st);
-        if (dtype == ND_AMD_F32)
-            launch_knn_features<float>(nfeat, k, rows, st, tab, R, train, target, ntrain, k, classes, nclasses, mean,
-                                       scale, labels, proba);
-        else
-            launch_knn_features<double>(nfeat, k, rows, st, tab, R, train, target, ntrain, k, classes, nclasses, mean,
-                                        scale, labels, proba);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            // up to eight features stay in registers; more are staged in LDS (NF = 0), in blocks of fewer rows
+            auto features = [&](auto NF) {
+                int grid = grid_for(rows), block = BLOCK;
+                size_t lds = 0;
+                if constexpr (decltype(NF)::value == 0) {
+                    block = knn_block_rows(nfeat, sizeof(T));
+                    const int64_t b = ceil_div(rows, block);
+                    grid = (int)(b < 8192 ? b : 8192);
+                    lds = (size_t)block * nfeat * sizeof(T);
+                }
+                auto launch = [&](auto CAP) {
+                    hipLaunchKernelGGL((classify_knn_kernel<T, decltype(NF)::value, decltype(CAP)::value>), dim3(grid), dim3(block),
+                                       lds, st, tab, nfeat, R, rows, train, target, ntrain, k, classes, nclasses, mean, scale,
+                                       labels, proba);
+                };
+                if (!pick_le<1, 2, 4, 8, 16>(k, launch)) launch(int_c<32>{});
+            };
+            if (!pick_eq<1, 2, 3, 4, 5, 6, 7, 8>(nfeat, features)) features(int_c<0>{});
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;
@@ -1054,21 +999,14 @@ extern "C" int nd_amd_classify_linear(const void *const *feat, int nfeat, int dt
     const int grid = grid_for(rows);
     {
         KernelTimer timer(ND_AMD_KERNEL_CLASSIFY_LINEAR, st);
-#define ND_LINEAR(T, NC)                                                                                        \
-    hipLaunchKernelGGL((classify_linear_kernel<T, NC>), dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, coef, \
-                       intercept, ncoef, classes, link, output, mean, scale, out)
-        if (dtype == ND_AMD_F32) {
-            if (ncoef <= 1) ND_LINEAR(float, 1);
-            else if (ncoef <= 2) ND_LINEAR(float, 2);
-            else if (ncoef <= 4) ND_LINEAR(float, 4);
-            else ND_LINEAR(float, 8);
-        } else {
-            if (ncoef <= 1) ND_LINEAR(double, 1);
-            else if (ncoef <= 2) ND_LINEAR(double, 2);
-            else if (ncoef <= 4) ND_LINEAR(double, 4);
-            else ND_LINEAR(double, 8);
-        }
-#undef ND_LINEAR
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            auto launch = [&](auto NC) {
+                hipLaunchKernelGGL((classify_linear_kernel<T, decltype(NC)::value>), dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R,
+                                   rows, coef, intercept, ncoef, classes, link, output, mean, scale, out);
+            };
+            if (!pick_le<1, 2, 4>(ncoef, launch)) launch(int_c<8>{});
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;

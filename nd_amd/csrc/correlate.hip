@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace nd_amd {
 
@@ -369,44 +370,41 @@ __global__ void __launch_bounds__(256) correlate_tiled_kernel(const TiledArgs<T>
     }
 }
 
-template <typename T, int KW>
-static void launch_tiled(const TiledArgs<T> &a, bool box, int64_t nblocks, size_t lds,
-                         hipStream_t stream)
+// Windows of up to 15 x 15.  KHB: the register-array class of the window's height (5 rows, or kSmallKH).
+template <typename T>
+static void launch_tiled(const TiledArgs<T> &a, int kw, bool box, int64_t nblocks, size_t lds, hipStream_t stream)
 {
     const dim3 grid((unsigned)nblocks), block(256);
-    if (a.kh <= 5) {
-        if (box)
-            hipLaunchKernelGGL((correlate_tiled_kernel<T, KW, true, 5>), grid, block, lds, stream, a);
-        else
-            hipLaunchKernelGGL((correlate_tiled_kernel<T, KW, false, 5>), grid, block, lds, stream, a);
-    } else {
-        if (box)
-            hipLaunchKernelGGL((correlate_tiled_kernel<T, KW, true, kSmallKH>), grid, block, lds, stream, a);
-        else
-            hipLaunchKernelGGL((correlate_tiled_kernel<T, KW, false, kSmallKH>), grid, block, lds, stream, a);
-    }
+    pick(box, [&](auto BOX) {
+        auto width = [&](auto KW) {
+            auto launch = [&](auto KHB) {
+                hipLaunchKernelGGL((correlate_tiled_kernel<T, decltype(KW)::value, decltype(BOX)::value, decltype(KHB)::value>),
+                                   grid, block, lds, stream, a);
+            };
+            if (!pick_le<5>(a.kh, launch)) launch(int_c<kSmallKH>{});
+        };
+        if (!pick_eq<1, 3, 5, 7, 9, 11, 13>(kw, width)) width(int_c<15>{});
+    });
 }
 
 // Windows of 17 .. 31 columns (any height up to 31), and the taller-than-15 windows of fewer columns run as
 // 17 wide with absent columns: one register-array class (31 rows), an LDS image of up to 79 KB (two blocks per
 // CU).  Before round 6 every window beyond 15 x 15 took the per-element kernel: BoxcarFilter(w=17) on
-// 8 x 2048^2 13.4 ms against 0.43 ms for w = 15.
-template <typename T, int KW>
-static bool launch_tiled_big(const TiledArgs<T> &a, bool box, int64_t nblocks, size_t lds, hipStream_t stream)
+// 8 x 2048^2 13.4 ms against 0.43 ms for w = 15.  False, and nothing launched, if the LDS limit cannot be raised.
+template <typename T>
+static bool launch_tiled_big(const TiledArgs<T> &a, int kw, bool box, int64_t nblocks, size_t lds, hipStream_t stream)
 {
     const dim3 grid((unsigned)nblocks), block(256);
-    if (box) {
-        static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&correlate_tiled_kernel<T, KW, true, kMaxKH>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e != hipSuccess) return false;
-        hipLaunchKernelGGL((correlate_tiled_kernel<T, KW, true, kMaxKH>), grid, block, lds, stream, a);
-    } else {
-        static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&correlate_tiled_kernel<T, KW, false, kMaxKH>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        if (e != hipSuccess) return false;
-        hipLaunchKernelGGL((correlate_tiled_kernel<T, KW, false, kMaxKH>), grid, block, lds, stream, a);
-    }
-    return true;
+    bool ok = false;
+    pick(box, [&](auto BOX) {
+        auto launch = [&](auto KW) {
+            constexpr auto kernel = &correlate_tiled_kernel<T, decltype(KW)::value, decltype(BOX)::value, kMaxKH>;
+            ok = allow_dynamic_lds(kernel, lds) == hipSuccess;
+            if (ok) hipLaunchKernelGGL(kernel, grid, block, lds, stream, a);
+        };
+        if (!pick_eq<17, 19, 21, 23, 25, 27, 29>(kw, launch)) launch(int_c<31>{});
+    });
+    return ok;
 }
 
 // -----------------------------------------------------------------------------------------
@@ -722,15 +720,14 @@ int try_roll<float>(const void *in, void *out, const int64_t dims[4], const int6
     if (nblocks > 0x7fffffffLL) return 0;
     KernelTimer timer(ND_AMD_KERNEL_BOXCAR_TILED, stream);
     const dim3 grid((unsigned)nblocks), block(256);
-    if (K == 3) {
-        if (box) hipLaunchKernelGGL((correlate_roll_kernel<3, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((correlate_roll_kernel<3, false>), grid, block, 0, stream, a);
-    } else if (K == 5) {
-        if (box) hipLaunchKernelGGL((correlate_roll_kernel<5, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((correlate_roll_kernel<5, false>), grid, block, 0, stream, a);
-    } else {
-        hipLaunchKernelGGL((correlate_roll_kernel<7, true>), grid, block, 0, stream, a);
-    }
+    pick(box, [&](auto BOX) {
+        auto launch = [&](auto KK) {
+            // (7 x 7 with 49 scalar weights was left to the LDS form above: no such instantiation)
+            if constexpr (decltype(BOX)::value || decltype(KK)::value != 7)
+                hipLaunchKernelGGL((correlate_roll_kernel<decltype(KK)::value, decltype(BOX)::value>), grid, block, 0, stream, a);
+        };
+        if (!pick_eq<3, 5>(K, launch)) launch(int_c<7>{});
+    });
     return 1;
 }
 
@@ -829,34 +826,9 @@ static int try_tiled(const void *in, void *out, const int64_t dims[4], const int
     const size_t lds = (size_t)(kTileY + kh - 1) * 4 * twq * sizeof(double) +
                        (size_t)((kTileY + kh - 1) + (kTileX + kw - 1)) * sizeof(int);
     if (lds > (big ? 96 : 64) * 1024) return 0;
-    if (big) {
-        KernelTimer timer(ND_AMD_KERNEL_BOXCAR_TILED, stream);
-        bool ok = false;
-        switch (kw) {
-        case 17: ok = launch_tiled_big<T, 17>(a, box, nblocks, lds, stream); break;
-        case 19: ok = launch_tiled_big<T, 19>(a, box, nblocks, lds, stream); break;
-        case 21: ok = launch_tiled_big<T, 21>(a, box, nblocks, lds, stream); break;
-        case 23: ok = launch_tiled_big<T, 23>(a, box, nblocks, lds, stream); break;
-        case 25: ok = launch_tiled_big<T, 25>(a, box, nblocks, lds, stream); break;
-        case 27: ok = launch_tiled_big<T, 27>(a, box, nblocks, lds, stream); break;
-        case 29: ok = launch_tiled_big<T, 29>(a, box, nblocks, lds, stream); break;
-        default: ok = launch_tiled_big<T, 31>(a, box, nblocks, lds, stream); break;
-        }
-        return ok ? 1 : 0;
-    }
-    {
-        KernelTimer timer(ND_AMD_KERNEL_BOXCAR_TILED, stream);
-        switch (kw) {
-        case 1: launch_tiled<T, 1>(a, box, nblocks, lds, stream); break;
-        case 3: launch_tiled<T, 3>(a, box, nblocks, lds, stream); break;
-        case 5: launch_tiled<T, 5>(a, box, nblocks, lds, stream); break;
-        case 7: launch_tiled<T, 7>(a, box, nblocks, lds, stream); break;
-        case 9: launch_tiled<T, 9>(a, box, nblocks, lds, stream); break;
-        case 11: launch_tiled<T, 11>(a, box, nblocks, lds, stream); break;
-        case 13: launch_tiled<T, 13>(a, box, nblocks, lds, stream); break;
-        default: launch_tiled<T, 15>(a, box, nblocks, lds, stream); break;
-        }
-    }
+    KernelTimer timer(ND_AMD_KERNEL_BOXCAR_TILED, stream);
+    if (big) return launch_tiled_big<T>(a, (int)kw, box, nblocks, lds, stream) ? 1 : 0;
+    launch_tiled<T>(a, (int)kw, box, nblocks, lds, stream);
     return 1;
 }
 
@@ -1340,32 +1312,16 @@ static int correlate1d_impl(const void *in, void *out, const int64_t dims[4], co
         if (fits) {
             KernelTimer timer(ND_AMD_KERNEL_CORRELATE1D, stream);
             const dim3 grid((unsigned)nb), block(256);
-#define ND_LAUNCH_1D(AX, NWC)                                                                                       \
-    do {                                                                                                            \
-        if (lds > 64 * 1024) {                                                                                      \
-            static const hipError_t e_ = hipFuncSetAttribute(                                                       \
-                reinterpret_cast<const void *>(&correlate1d_tiled_kernel<T, AX, NWC>),                              \
-                hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);                                            \
-            ND_HIP_CHECK(e_);                                                                                       \
-        }                                                                                                           \
-        hipLaunchKernelGGL((correlate1d_tiled_kernel<T, AX, NWC>), grid, block, lds, stream, t);                    \
-    } while (0)
-            if (along_x) {
-                if (nwc == 9) ND_LAUNCH_1D(true, 9);
-                else if (nwc == 17) ND_LAUNCH_1D(true, 17);
-                else if (nwc == 25) ND_LAUNCH_1D(true, 25);
-                else if (nwc == 31) ND_LAUNCH_1D(true, 31);
-                else if (nwc == 65) ND_LAUNCH_1D(true, 65);
-                else ND_LAUNCH_1D(true, kT1MaxW);
-            } else {
-                if (nwc == 9) ND_LAUNCH_1D(false, 9);
-                else if (nwc == 17) ND_LAUNCH_1D(false, 17);
-                else if (nwc == 25) ND_LAUNCH_1D(false, 25);
-                else if (nwc == 31) ND_LAUNCH_1D(false, 31);
-                else if (nwc == 65) ND_LAUNCH_1D(false, 65);
-                else ND_LAUNCH_1D(false, kT1MaxW);
-            }
-#undef ND_LAUNCH_1D
+            hipError_t e = hipSuccess;
+            auto launch = [&](auto NWC) {
+                pick(along_x, [&](auto AX) {
+                    constexpr auto kernel = &correlate1d_tiled_kernel<T, decltype(AX)::value, decltype(NWC)::value>;
+                    if (lds > 64 * 1024) e = allow_dynamic_lds(kernel, lds);
+                    if (e == hipSuccess) hipLaunchKernelGGL(kernel, grid, block, lds, stream, t);
+                });
+            };
+            if (!pick_eq<9, 17, 25, 31, 65>(nwc, launch)) launch(int_c<kT1MaxW>{});
+            ND_HIP_CHECK(e);
             ND_HIP_CHECK(hipGetLastError());
             return ND_AMD_OK;
         }
@@ -1744,34 +1700,20 @@ extern "C" int nd_amd_correlate1d_yx(const void *in, void *out, int dtype, const
     {
         KernelTimer timer(ND_AMD_KERNEL_CORRELATE1D, stream);
         const dim3 grid((unsigned)nblocks), block(256);
-        if (dtype == ND_AMD_F64) {
-            Corr2PassArgs<double> a;
-            a.in = static_cast<const double *>(in);
-            a.out = static_cast<double *>(out);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            Corr2PassArgs<T> a;
+            a.in = static_cast<const T *>(in);
+            a.out = static_cast<T *>(out);
             fill(a);
-#define ND_YX64(RR)                                                                                  \
-    case RR: hipLaunchKernelGGL((correlate1d_yx_kernel<double, RR, false>), grid, block, 0, stream, a); break;
-            switch (R) {
-                ND_YX64(1) ND_YX64(2) ND_YX64(3) ND_YX64(4) ND_YX64(5) ND_YX64(6)
-            default: hipLaunchKernelGGL((correlate1d_yx_kernel<double, 8, false>), grid, block, 0, stream, a); break;
-            }
-#undef ND_YX64
-        } else {
-            Corr2PassArgs<float> a;
-            a.in = static_cast<const float *>(in);
-            a.out = static_cast<float *>(out);
-            fill(a);
-            // measured on 24 x 4096 x 4096: the float64 window wins from radius 6 (sigma 1.5: 0.90 -> 0.85 ms,
-            // sigma 2: 1.14 -> 0.98 ms) and loses below (registers: 118 vs 82 at radius 4)
-#define ND_YX(RR)                                                                                  \
-    case RR: hipLaunchKernelGGL((correlate1d_yx_kernel<float, RR, false>), grid, block, 0, stream, a); break;
-            switch (R) {
-                ND_YX(1) ND_YX(2) ND_YX(3) ND_YX(4) ND_YX(5)
-            case 6: hipLaunchKernelGGL((correlate1d_yx_kernel<float, 6, true>), grid, block, 0, stream, a); break;
-            default: hipLaunchKernelGGL((correlate1d_yx_kernel<float, 8, true>), grid, block, 0, stream, a); break;
-            }
-#undef ND_YX
-        }
+            auto launch = [&](auto RR) {
+                // float32, measured on 24 x 4096 x 4096: the float64 window wins from radius 6 (sigma 1.5: 0.90 ->
+                // 0.85 ms, sigma 2: 1.14 -> 0.98 ms) and loses below (registers: 118 vs 82 at radius 4)
+                constexpr bool DWIN = !decltype(F64)::value && decltype(RR)::value >= 6;
+                hipLaunchKernelGGL((correlate1d_yx_kernel<T, decltype(RR)::value, DWIN>), grid, block, 0, stream, a);
+            };
+            if (!pick_eq<1, 2, 3, 4, 5, 6>(R, launch)) launch(int_c<8>{});
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "classify_common.hpp"
+#include "dispatch.hpp"
 
 using namespace nd_amd;
 
@@ -360,19 +361,14 @@ extern "C" int nd_amd_kmeans_step(const void *const *feat, int nfeat, int dtype,
     const int nd = k * nfeat + 1, ni = k + 1;
     {
         KernelTimer timer(ND_AMD_KERNEL_KMEANS_STEP, st);
-#define ND_STEP(T, NREG)                                                                                          \
-    hipLaunchKernelGGL((kmeans_step_kernel<T, NREG>), dim3(grid), dim3(WAVE), lds, st, w.tab, nfeat, R, rows, centers, \
-                       k, mean, scale, labels, w.dpart, w.ipart)
-        if (dtype == ND_AMD_F32) {
-            if (nfeat <= 4) ND_STEP(float, 4);
-            else if (nfeat <= 8) ND_STEP(float, 8);
-            else ND_STEP(float, 0);
-        } else {
-            if (nfeat <= 4) ND_STEP(double, 4);
-            else if (nfeat <= 8) ND_STEP(double, 8);
-            else ND_STEP(double, 0);
-        }
-#undef ND_STEP
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            auto launch = [&](auto NREG) {
+                hipLaunchKernelGGL((kmeans_step_kernel<T, decltype(NREG)::value>), dim3(grid), dim3(WAVE), lds, st, w.tab, nfeat, R,
+                                   rows, centers, k, mean, scale, labels, w.dpart, w.ipart);
+            };
+            if (!pick_le<4, 8>(nfeat, launch)) launch(int_c<0>{});
+        });
         hipLaunchKernelGGL(fit_fold_kernel, dim3((unsigned)ceil_div(nd + ni, BLOCK)), dim3(BLOCK), 0, st, w.dpart, nd,
                            w.ipart, ni, grid, sums, inertia, counts, changed);
     }
@@ -408,12 +404,11 @@ extern "C" int nd_amd_feature_moments(const void *const *feat, int nfeat, int dt
             double *out = pass == 0 ? fmean : fvar;
             if (grid > 0) {
                 const double *center = pass == 0 ? nullptr : fmean;
-                if (dtype == ND_AMD_F32)
-                    hipLaunchKernelGGL(feature_moments_kernel<float>, dim3(grid), dim3(WAVE), lds, st, w.tab, nfeat, R,
-                                       rows, center, mean, scale, w.dpart, w.ipart);
-                else
-                    hipLaunchKernelGGL(feature_moments_kernel<double>, dim3(grid), dim3(WAVE), lds, st, w.tab, nfeat, R,
-                                       rows, center, mean, scale, w.dpart, w.ipart);
+                pick(dtype == ND_AMD_F64, [&](auto F64) {
+                    using T = std::conditional_t<decltype(F64)::value, double, float>;
+                    hipLaunchKernelGGL(feature_moments_kernel<T>, dim3(grid), dim3(WAVE), lds, st, w.tab, nfeat, R, rows, center,
+                                       mean, scale, w.dpart, w.ipart);
+                });
             }
             // with no block the fold writes zeros, and the division below NaN
             hipLaunchKernelGGL(fit_fold_kernel, dim3(fblocks), dim3(BLOCK), 0, st, w.dpart, nfeat, w.ipart, 1, grid, out,
@@ -453,12 +448,11 @@ extern "C" int nd_amd_gather_rows(const void *const *feat, int nfeat, int dtype,
     const int grid = (int)(b < 8192 ? b : 8192);
     {
         KernelTimer timer(ND_AMD_KERNEL_GATHER_ROWS, st);
-        if (dtype == ND_AMD_F32)
-            hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, index, m,
-                               mean, scale, (float *)X, valid);
-        else
-            hipLaunchKernelGGL(gather_rows_kernel<double>, dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, index, m,
-                               mean, scale, (double *)X, valid);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(grid), dim3(BLOCK), 0, st, tab, nfeat, R, rows, index, m, mean, scale,
+                               (T *)X, valid);
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace nd_amd {
 
@@ -877,59 +878,37 @@ static bool launch_stream3(const NlmTiledArgs &a, int64_t nb, hipStream_t stream
     // measured the same to 1 % -- the kernel is bound by VALU issue, not by latency
     // (profiles/r02_nlmeans_window_pmc.txt)
     const dim3 grid((unsigned)nb);
-#define ND_S3(RR)                                                                                          \
-    hipLaunchKernelGGL((nlmeans_window_stream3_kernel<RR, 2, 4>), grid, dim3(512), lds(RR), stream, a); \
-    return true
-    switch (a.r1) {
-    case 1: ND_S3(1);
-    case 2: ND_S3(2);
-    case 3: ND_S3(3);
-    case 4: ND_S3(4);
-    case 5: ND_S3(5);
-    default: return false;
-    }
-#undef ND_S3
+    return pick_eq<1, 2, 3, 4, 5>(a.r1, [&](auto R) {
+        hipLaunchKernelGGL((nlmeans_window_stream3_kernel<decltype(R)::value, 2, 4>), grid, dim3(512), lds(decltype(R)::value),
+                           stream, a);
+    });
 }
 
 // Dynamic LDS beyond the default 64 KB limit (up to kBigLds of the CU's 160 KB: one block per CU
-// then -- still tens of times faster than the generic kernel the request would otherwise fall to)
+// then -- still tens of times faster than the generic kernel the request would otherwise fall to).
+// A launch of 256 threads with `lds` bytes; false, and nothing launched, if the limit cannot be raised: the
+// form is then not applicable.
 constexpr size_t kBigLds = 150 * 1024;
-#define ND_LAUNCH_LDS(KERNEL, GRID, BLOCK, LDS, STREAM, ARGS)                                          \
-    do {                                                                                              \
-        if ((LDS) > 64 * 1024)                                                                        \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&KERNEL),                        \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS));        \
-        hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, ARGS);                                   \
-    } while (0)
-
-template <int R1>
-static void launch_roll(const NlmTiledArgs &a, int64_t nb, size_t lds, hipStream_t stream)
+template <class Kernel>
+static bool launch_lds(Kernel *kernel, int64_t nb, size_t lds, hipStream_t stream, const NlmTiledArgs &a)
 {
-    // square windows up to 11 x 11 get the fully unrolled row loop
-    if (R1 >= 1 && R1 <= 5 && a.r0 == R1) {
-        ND_LAUNCH_LDS((nlmeans_window_roll_kernel<R1, (R1 >= 1 && R1 <= 5) ? R1 : -1>),
-                      dim3((unsigned)nb), dim3(256), lds, stream, a);
-    } else {
-        ND_LAUNCH_LDS((nlmeans_window_roll_kernel<R1, -1>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-    }
+    if (lds > 64 * 1024 && allow_dynamic_lds(kernel, lds) != hipSuccess) return false;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), lds, stream, a);
+    return true;
 }
 
 static bool launch_roll_r1(const NlmTiledArgs &a, int64_t nb, size_t lds, hipStream_t stream)
 {
-    switch (a.r1) {
-    case 0: launch_roll<0>(a, nb, lds, stream); return true;
-    case 1: launch_roll<1>(a, nb, lds, stream); return true;
-    case 2: launch_roll<2>(a, nb, lds, stream); return true;
-    case 3: launch_roll<3>(a, nb, lds, stream); return true;
-    case 4: launch_roll<4>(a, nb, lds, stream); return true;
-    case 5: launch_roll<5>(a, nb, lds, stream); return true;
-    case 6: launch_roll<6>(a, nb, lds, stream); return true;
-    case 7: launch_roll<7>(a, nb, lds, stream); return true;
-    case 8: launch_roll<8>(a, nb, lds, stream); return true;
-    case 9: launch_roll<9>(a, nb, lds, stream); return true;
-    case 10: launch_roll<10>(a, nb, lds, stream); return true;
-    default: return false;
-    }
+    bool ok = false;
+    pick_eq<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10>(a.r1, [&](auto R) {
+        constexpr int R1 = decltype(R)::value;
+        // square windows up to 11 x 11 get the fully unrolled row loop
+        constexpr int SQ = (R1 >= 1 && R1 <= 5) ? R1 : -1;
+        pick(a.r0 == R1, [&](auto S) {
+            ok = launch_lds(&nlmeans_window_roll_kernel<R1, decltype(S)::value ? SQ : -1>, nb, lds, stream, a);
+        });
+    });
+    return ok;
 }
 
 // ---- patch_mode 1: sliding patch-row sums ---------------------------------------------------
@@ -1503,61 +1482,43 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
     }
 }
 
-template <int F, int V>
-static void launch_patch2(const NlmTiledArgs &a, int64_t nslices, size_t lds, hipStream_t stream)
+// patches of 3 x 3, 5 x 5 and 7 x 7 (f = 1, 2, 3), one to four variables; false if nothing was launched
+static bool launch_patch2(const NlmTiledArgs &a, int f, int64_t nslices, size_t lds, hipStream_t stream)
 {
-    constexpr int TYW = Patch2Rows<V>::TYW;
     const int64_t nb = (int64_t)a.tiles_x * a.tiles_y * nslices;
-    const bool mc = a.r1 + 2 * Patch2Geom<F>::HL + (a.r1 & 1) <= kPatch2Margin;    // as the host sized the tile
-    if (a.n_eff >= 0) {
-        if (mc) {
-            ND_LAUNCH_LDS((nlmeans_patch2_kernel<F, V, TYW, true, kPatch2Margin>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-        } else {
-            ND_LAUNCH_LDS((nlmeans_patch2_kernel<F, V, TYW, true, 0>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-        }
-    } else {
-        if (mc) {
-            ND_LAUNCH_LDS((nlmeans_patch2_kernel<F, V, TYW, false, kPatch2Margin>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-        } else {
-            ND_LAUNCH_LDS((nlmeans_patch2_kernel<F, V, TYW, false, 0>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-        }
-    }
+    bool ok = false;
+    auto patch = [&](auto FF) {
+        constexpr int F = decltype(FF)::value;
+        const bool mc = a.r1 + 2 * Patch2Geom<F>::HL + (a.r1 & 1) <= kPatch2Margin;    // as the host sized the tile
+        pick_eq<1, 2, 3, 4>(a.nvars, [&](auto VV) {
+            constexpr int V = decltype(VV)::value, TYW = Patch2Rows<V>::TYW;
+            pick(a.n_eff >= 0, [&](auto NEFF) {
+                pick(mc, [&](auto MC) {
+                    ok = launch_lds(&nlmeans_patch2_kernel<F, V, TYW, decltype(NEFF)::value, decltype(MC)::value ? kPatch2Margin : 0>,
+                                    nb, lds, stream, a);
+                });
+            });
+        });
+    };
+    if (!pick_eq<1, 2>(f, patch)) patch(int_c<3>{});
+    return ok;
 }
 
-template <int F>
-static bool launch_patch2_v(const NlmTiledArgs &a, int64_t nslices, size_t lds, hipStream_t stream)
+// patches of up to 11 x 11 (f = 0 .. 5), one to four variables; false if nothing was launched
+static bool launch_patch(const NlmTiledArgs &a, int f, int64_t nslices, size_t lds, hipStream_t stream)
 {
-    switch (a.nvars) {
-    case 1: launch_patch2<F, 1>(a, nslices, lds, stream); return true;
-    case 2: launch_patch2<F, 2>(a, nslices, lds, stream); return true;
-    case 3: launch_patch2<F, 3>(a, nslices, lds, stream); return true;
-    case 4: launch_patch2<F, 4>(a, nslices, lds, stream); return true;
-    }
-    return false;
-}
-
-template <int F, int V>
-static void launch_patch(const NlmTiledArgs &a, int64_t nslices, size_t lds, hipStream_t stream)
-{
-    constexpr int TYW = (V == 1) ? 16 : 8;
     const int64_t nb = (int64_t)a.tiles_x * a.tiles_y * nslices;
-    if (a.n_eff >= 0) {
-        ND_LAUNCH_LDS((nlmeans_patch_kernel<F, V, TYW, true>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-    } else {
-        ND_LAUNCH_LDS((nlmeans_patch_kernel<F, V, TYW, false>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-    }
-}
-
-template <int F>
-static bool launch_patch_v(const NlmTiledArgs &a, int64_t nslices, size_t lds, hipStream_t stream)
-{
-    switch (a.nvars) {
-    case 1: launch_patch<F, 1>(a, nslices, lds, stream); return true;
-    case 2: launch_patch<F, 2>(a, nslices, lds, stream); return true;
-    case 3: launch_patch<F, 3>(a, nslices, lds, stream); return true;
-    case 4: launch_patch<F, 4>(a, nslices, lds, stream); return true;
-    }
-    return false;
+    bool ok = false;
+    auto patch = [&](auto FF) {
+        pick_eq<1, 2, 3, 4>(a.nvars, [&](auto VV) {
+            constexpr int F = decltype(FF)::value, V = decltype(VV)::value, TYW = (V == 1) ? 16 : 8;
+            pick(a.n_eff >= 0, [&](auto NEFF) {
+                ok = launch_lds(&nlmeans_patch_kernel<F, V, TYW, decltype(NEFF)::value>, nb, lds, stream, a);
+            });
+        });
+    };
+    if (!pick_eq<0, 1, 2, 3, 4>(f, patch)) patch(int_c<5>{});
+    return ok;
 }
 
 // Try a tiled form; 1 = launched, 0 = not applicable.
@@ -1882,39 +1843,29 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
 
 constexpr int kPatch3RMax = 4;
 
-template <int F, int FZ, int V, int TYW>
-static int launch_patch3(const NlmTiledArgs &a, int64_t nb, size_t lds, hipStream_t stream)
+// patches of (2 fz + 1) planes x (2 f + 1)^2 with f, fz in {0, 1}, tiles of 4 tyw rows (tyw = 4 or 2); false if
+// nothing was launched
+static bool launch_patch3(const NlmTiledArgs &a, int f, int fz, int tyw, int64_t nb, size_t lds, hipStream_t stream)
 {
-    if (a.n_eff >= 0) {
-        if (lds > 64 * 1024)
-            ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&nlmeans_patch3_kernel<F, FZ, V, true, kPatch3RMax, TYW>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((nlmeans_patch3_kernel<F, FZ, V, true, kPatch3RMax, TYW>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-    } else {
-        if (lds > 64 * 1024)
-            ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&nlmeans_patch3_kernel<F, FZ, V, false, kPatch3RMax, TYW>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((nlmeans_patch3_kernel<F, FZ, V, false, kPatch3RMax, TYW>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-    }
-    return ND_AMD_OK;
-}
-
-template <int F, int FZ, int TYW>
-static int launch_patch3_v(const NlmTiledArgs &a, int64_t nb, size_t lds, hipStream_t stream)
-{
-    // (the 8-row tiles exist for the plane counts that need them: three and four variables)
-    if constexpr (TYW == 4) {
-        switch (a.nvars) {
-        case 1: return launch_patch3<F, FZ, 1, TYW>(a, nb, lds, stream);
-        case 2: return launch_patch3<F, FZ, 2, TYW>(a, nb, lds, stream);
-        case 3: return launch_patch3<F, FZ, 3, TYW>(a, nb, lds, stream);
-        default: return launch_patch3<F, FZ, 4, TYW>(a, nb, lds, stream);
-        }
-    } else {
-        if (a.nvars == 3) return launch_patch3<F, FZ, 3, TYW>(a, nb, lds, stream);
-        if (a.nvars == 4) return launch_patch3<F, FZ, 4, TYW>(a, nb, lds, stream);
-        return ND_AMD_EUNSUPPORTED;
-    }
+    bool ok = false;
+    pick_eq<0, 1>(f, [&](auto FF) {
+        pick_eq<0, 1>(fz, [&](auto FZ) {
+            pick(tyw == 4, [&](auto T4) {
+                auto vars = [&](auto VV) {
+                    constexpr int V = decltype(VV)::value, TYW = decltype(T4)::value ? 4 : 2;
+                    // (the 8-row tiles exist for the plane counts that need them: three and four variables)
+                    if constexpr (TYW == 4 || V >= 3)
+                        pick(a.n_eff >= 0, [&](auto NEFF) {
+                            ok = launch_lds(&nlmeans_patch3_kernel<decltype(FF)::value, decltype(FZ)::value, V,
+                                                                   decltype(NEFF)::value, kPatch3RMax, TYW>,
+                                            nb, lds, stream, a);
+                        });
+                };
+                if (!pick_eq<1, 2, 3>(a.nvars, vars)) vars(int_c<4>{});
+            });
+        });
+    });
+    return ok;
 }
 
 static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[3], int64_t nvars,
@@ -1997,33 +1948,20 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
         const size_t lds = (size_t)(2 * rz + 1) * rows * cols * (f64 ? sizeof(double) : sizeof(float)) +
                            (rows + cols) * sizeof(int);
         if (nb > 0x7fffffffLL) return 0;
-        if (f64) {
-            if (lds > kBigLds) return 0;
-            KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-#define ND_LAUNCH_WIN64(R)                                                                                     \
-    do {                                                                                                      \
-        if (lds > 64 * 1024)                                                                                  \
-            ND_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&nlmeans_window_kernel<double, R>), \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));           \
-        hipLaunchKernelGGL((nlmeans_window_kernel<double, R>), dim3((unsigned)nb), dim3(256), lds, stream, a); \
-    } while (0)
-            if (a.r1 <= 4)
-                ND_LAUNCH_WIN64(4);
-            else if (a.r1 <= 10)
-                ND_LAUNCH_WIN64(10);
-            else
-                ND_LAUNCH_WIN64(16);
-#undef ND_LAUNCH_WIN64
-            return 1;
-        }
-        if (lds > 64 * 1024) return 0;
+        // (float32 stays within the default limit; float64 may take up to kBigLds)
+        if (lds > (f64 ? kBigLds : 64 * 1024)) return 0;
         KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-        if (a.r1 <= 4)
-            hipLaunchKernelGGL((nlmeans_window_kernel<float, 4>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-        else if (a.r1 <= 10)
-            hipLaunchKernelGGL((nlmeans_window_kernel<float, 10>), dim3((unsigned)nb), dim3(256), lds, stream, a);
-        else
-            hipLaunchKernelGGL((nlmeans_window_kernel<float, 16>), dim3((unsigned)nb), dim3(256), lds, stream, a);
+        hipError_t e = hipSuccess;
+        pick(f64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            auto launch = [&](auto R) {
+                constexpr auto kernel = &nlmeans_window_kernel<T, decltype(R)::value>;
+                if (lds > 64 * 1024) e = allow_dynamic_lds(kernel, lds);
+                if (e == hipSuccess) hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), lds, stream, a);
+            };
+            if (!pick_le<4, 10>(a.r1, launch)) launch(int_c<16>{});
+        });
+        ND_HIP_CHECK(e);
         return 1;
     }
     // true patch distances (patch_mode 1, or f = 0 in either mode: the loops run once)
@@ -2055,16 +1993,7 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
         const int64_t nb3 = (int64_t)a.tiles_x * a.tiles_y * nsl;
         if (lds3 > kBigLds || nb3 > 0x7fffffffLL) return 0;
         KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-        int rc3 = ND_AMD_OK;
-#define ND_P3(F_, FZ_)                                                                     \
-    (tyw == 4 ? launch_patch3_v<F_, FZ_, 4>(a, nb3, lds3, stream) : launch_patch3_v<F_, FZ_, 2>(a, nb3, lds3, stream))
-        if (Fp == 0 && FZz == 0) rc3 = ND_P3(0, 0);
-        else if (Fp == 1 && FZz == 0) rc3 = ND_P3(1, 0);
-        else if (Fp == 1 && FZz == 1) rc3 = ND_P3(1, 1);
-        else if (Fp == 0 && FZz == 1) rc3 = ND_P3(0, 1);
-        else return 0;
-#undef ND_P3
-        return rc3 == ND_AMD_OK ? 1 : 0;
+        return launch_patch3(a, Fp, (int)FZz, tyw, nb3, lds3, stream) ? 1 : 0;
     }
     const uint32_t F0 = (patch_mode == 1) ? f[A0] : 0u, F1 = (patch_mode == 1) ? f[A1] : 0u;
     if (patch_mode == 0 && (f[A0] != 0 || f[A1] != 0)) return 0;
@@ -2083,13 +2012,7 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
         a.tiles_y = (int)ceil_div(ey, 4 * tyw2);
         if (lds2 <= kBigLds && (int64_t)a.tiles_x * a.tiles_y * nsl <= 0x7fffffffLL) {
             KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-            bool ok2 = false;
-            switch (F0) {
-            case 1: ok2 = launch_patch2_v<1>(a, nsl, lds2, stream); break;
-            case 2: ok2 = launch_patch2_v<2>(a, nsl, lds2, stream); break;
-            default: ok2 = launch_patch2_v<3>(a, nsl, lds2, stream); break;
-            }
-            if (ok2) return 1;
+            if (launch_patch2(a, (int)F0, nsl, lds2, stream)) return 1;
         }
     }
     const int tyw = (nvars == 1) ? 16 : 8;
@@ -2101,16 +2024,7 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
     if (lds > kBigLds) return 0;
     if ((int64_t)a.tiles_x * a.tiles_y * nsl > 0x7fffffffLL) return 0;
     KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-    bool ok = false;
-    switch (F0) {
-    case 0: ok = launch_patch_v<0>(a, nsl, lds, stream); break;
-    case 1: ok = launch_patch_v<1>(a, nsl, lds, stream); break;
-    case 2: ok = launch_patch_v<2>(a, nsl, lds, stream); break;
-    case 3: ok = launch_patch_v<3>(a, nsl, lds, stream); break;
-    case 4: ok = launch_patch_v<4>(a, nsl, lds, stream); break;
-    default: ok = launch_patch_v<5>(a, nsl, lds, stream); break;
-    }
-    return ok ? 1 : 0;
+    return launch_patch(a, (int)F0, nsl, lds, stream) ? 1 : 0;
 }
 
 template <typename T>
@@ -2210,15 +2124,10 @@ static int nlmeans_impl(const void *arr, void *out, const int64_t N[3], int64_t 
     }
     {
         KernelTimer timer(ND_AMD_KERNEL_NLMEANS, stream);
-        if (nvars <= 1)
-            hipLaunchKernelGGL((nlmeans_generic_kernel<T, 1>), dim3((unsigned)nblocks), dim3(256),
-                               0, stream, a);
-        else if (nvars <= 4)
-            hipLaunchKernelGGL((nlmeans_generic_kernel<T, 4>), dim3((unsigned)nblocks), dim3(256),
-                               0, stream, a);
-        else
-            hipLaunchKernelGGL((nlmeans_generic_kernel<T, 16>), dim3((unsigned)nblocks),
-                               dim3(256), 0, stream, a);
+        auto launch = [&](auto VMAX) {
+            hipLaunchKernelGGL((nlmeans_generic_kernel<T, decltype(VMAX)::value>), dim3((unsigned)nblocks), dim3(256), 0, stream, a);
+        };
+        if (!pick_le<1, 4>((int)nvars, launch)) launch(int_c<16>{});
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;

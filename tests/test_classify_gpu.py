@@ -263,6 +263,38 @@ def test_twelve_features_with_a_scaler(device, dtype, layout):
     assert len(np.unique(lv[keep])) == 5
 
 
+@pytest.mark.parametrize('dtype', cases.DTYPES)
+@pytest.mark.parametrize('nfeat,ncls', [(4, 5), (5, 8), (8, 9), (9, 2), (3, 3)])
+def test_feature_and_class_counts_at_the_bounds_of_the_forms(device, nfeat, ncls, dtype):
+    """4 features are the last of the first register form, 5 the first and 8 the last of the second, 9 the first
+    read from memory; 2, 4 and 8 classes are the last of a class-count form and 3, 5 and 9 the first of the next
+    (4 classes: check_array_forest).  One variable per feature: the forest bit for bit against the restatement,
+    k-means labels equal outside the 1e-12 near-ties."""
+    from tests import kmeans_fit_ref as kf
+    data = kf.stack(nfeat, (1, 12, 25), 3, dtype, seed=nfeat, nan=False)
+    data['v00'][0, 5, 7] = np.nan
+    X, shape = ref.build_X(kf.variables(data), ('time', 'y', 'x'))
+    assert X.shape == (300, nfeat) and X.dtype == dtype
+    keep = ~np.isnan(X).any(axis=1)
+    Xp = X[keep]
+    model = classify.ForestModel(*cases.array_forest(Xp, ncls, seed=nfeat))
+    assert set(model.feature[model.feature >= 0]) == set(range(nfeat))
+    proba = ref.forest_proba(Xp, model.feature, model.threshold, model.left, model.right, model.value,
+                             model.tree_offsets)
+    ds = dataset(data, 'tyx', device)
+    pv = host(classify.predict_forest(ds, model, (), 'predict_proba').values).reshape(keep.size, -1)
+    lv = host(classify.predict_forest(ds, model, (), 'predict').values).reshape(-1)
+    assert pv.shape[1] == ncls and np.isnan(pv[~keep]).all() and np.isnan(lv[~keep]).all()
+    assert pv[keep].tobytes() == proba.tobytes()
+    np.testing.assert_array_equal(lv[keep], ref.forest_predict(proba, model.classes))
+    centers = Xp[[5, 100, 200, 290]].astype(np.float64) * 1.0625
+    ok = ref.kmeans_gap(Xp, centers) >= 1e-12
+    assert (~ok).mean() <= 1e-4
+    got = host(classify.predict_kmeans(ds, classify.KMeansModel(centers)).values).reshape(-1)
+    assert np.isnan(got[~keep]).all()
+    np.testing.assert_array_equal(got[keep][ok], ref.kmeans_labels(Xp, centers)[ok])
+
+
 def test_classifier_reuses_the_packed_model(device):
     pytest.importorskip('sklearn')
     from sklearn.ensemble import RandomForestClassifier

@@ -131,7 +131,9 @@ def test_knn_row_counts_off_the_wave_and_block(device, rows, dtype):
     knn_check(device, X, train, rng.integers(0, 3, 50), [1, 2, 3], 3)
 
 
-@pytest.mark.parametrize('ntrain,k', [(1, 1), (5, 5), (TILE, TILE), (TILE + 1, 3), (2 * TILE + 1, 16), (100, 32)])
+# (k = 2, 4, 8, 16 are the last of a neighbour-list size, 3, 5, 9 and 17 the first of the next)
+@pytest.mark.parametrize('ntrain,k', [(1, 1), (5, 5), (TILE, TILE), (TILE + 1, 3), (2 * TILE + 1, 16), (100, 32),
+                                      (40, 2), (40, 4), (40, 9), (40, 17)])
 @pytest.mark.parametrize('nfeat', [3, 9])
 def test_knn_training_sizes_around_the_tile(device, ntrain, k, nfeat):
     rng = np.random.default_rng(ntrain * 100 + k)
@@ -274,9 +276,10 @@ def test_linear_row_counts_off_the_wave_and_block(device, rows, dtype):
 
 
 @pytest.mark.parametrize('link', ['softmax', 'ovr', 'none'])
-@pytest.mark.parametrize('ncoef', [1, 2, 8, 9, 11])
+@pytest.mark.parametrize('ncoef', [1, 2, 3, 4, 5, 8, 9, 11])
 def test_linear_class_counts_around_the_passes(device, ncoef, link):
-    """1 is the binary form; 8 fills one pass, 9 and 11 need a second with the running maximum"""
+    """1 is the binary form; 2 and 4 are the last of an accumulator count, 3 and 5 the first of the next; 8 fills
+    one pass, 9 and 11 need a second with the running maximum"""
     rng = np.random.default_rng(ncoef)
     X = speckle(rng, 130, 5, np.float64) - 4.0
     X[3, 0] = np.nan

@@ -175,6 +175,19 @@ def test_tiled_edges_and_tiny_planes(device):
 
 
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_tiled_kernel_on_both_sides_of_its_size_classes(device, dtype):
+    """The tiled kernel's instantiations are picked by width (odd 1 .. 15, then 17 .. 31), by height (up to 5 rows,
+    up to 15, up to 31) and by boxcar or weights: windows of 15 and 17 columns, 5 and 6 rows, 15 and 16 rows, and
+    31 x 31, each as a boxcar and with random weights, on planes of more than one tile -- bit-equal to scipy."""
+    import scipy.ndimage as ndi
+    rng = np.random.default_rng(1517)
+    a = rng.normal(size=(2, 40, 140)).astype(dtype)
+    for kshape in [(1, 5, 15), (1, 6, 15), (1, 5, 17), (1, 6, 17), (1, 15, 15), (1, 16, 15), (1, 31, 31)]:
+        for k in (np.ones(kshape) / np.prod(kshape), rng.normal(size=kshape)):
+            np.testing.assert_array_equal(_gpu_convolve(a, k, device), ndi.convolve(a, k), err_msg=str(kshape))
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_windows_of_17_to_31_in_the_tiled_kernel(device, dtype):
     """Windows beyond 15 x 15 (round 6: BoxcarFilter(w=17) took the per-element kernel, 30 x the time of w = 15):
     every width class 17 .. 31, boxcars and random weights, taller-than-15 windows of few columns (run 17 wide with

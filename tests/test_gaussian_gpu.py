@@ -83,6 +83,25 @@ def test_long_kernels_in_the_tiled_1d_kernel(device, dtype):
     assert time.perf_counter() - t0 < 5e-3
 
 
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_tiled_1d_kernel_on_both_sides_of_its_size_classes(device, dtype):
+    """The tiled 1-D kernel is instantiated for up to 9, 17, 25, 31, 65 and 97 taps: the last count of each class
+    and the first of the next, along x and along y (from 32 taps on, the tile along y takes more than 64 KB of
+    LDS), general kernels on planes of more than one tile -- bit-equal to scipy."""
+    import torch
+    import scipy.ndimage as ndi
+    from nd_amd import kernels
+    rng = np.random.default_rng(965)
+    a = rng.normal(size=(2, 40, 140)).astype(dtype)
+    t = torch.from_numpy(a).to(device)
+    for n in (9, 10, 17, 18, 25, 26, 31, 32, 65, 66):
+        w = rng.normal(size=n)
+        for axis in (1, 2):
+            out = torch.empty_like(t)
+            kernels.correlate1d(t, w, axis, out)
+            np.testing.assert_array_equal(out.cpu().numpy(), ndi.correlate1d(a, w, axis=axis), err_msg=str((n, axis)))
+
+
 def test_gaussian_filter_class(device):
     """nd/tests/test_gaussian_filter.py:10-27 re-stated."""
     import scipy.ndimage as ndi

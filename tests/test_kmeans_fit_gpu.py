@@ -98,6 +98,20 @@ def test_kmeans_step_is_the_restatement(device, nfeat, k):
                     check_step(lay, X, centers, (labels + 1) % k, mean, scale)
 
 
+@pytest.mark.parametrize('nfeat', [4, 5, 8])
+def test_kmeans_step_feature_counts_at_the_bounds_of_the_register_forms(device, nfeat):
+    """4 features are the last of the first register form, 5 the first and 8 the last of the second (9, the first
+    read through LDS, is in FEATURES): one variable per feature, both data types, with the scaler"""
+    for dtype in cases.DTYPES:
+        data, X = reference(nfeat, SMALL, (), dtype)
+        assert X.shape[1] == nfeat
+        lay = table(data, (), 'tyx', device)
+        mean, scale = scaler_of(X)
+        centers = kf.draw_init(ref.scale(X, mean, scale), 3, seed=nfeat)
+        labels, _, _ = check_step(lay, X, centers, np.full(X.shape[0], -1), mean, scale)
+        check_step(lay, X, centers, (labels + 1) % 3, mean, scale)
+
+
 def test_kmeans_step_at_the_accumulator_limit_and_past_the_grid(device):
     """k * (features + 1) = 4080 of 4096 accumulators; and a stack of more batches than the grid has blocks, where
     a block walks several batches"""

@@ -180,6 +180,32 @@ def test_apply_over_two_devices_equals_one(oracle):
     np.testing.assert_array_equal(ch.values.cpu().numpy(), want)
 
 
+@needs2
+def test_filters_beyond_64_kb_of_lds_on_the_second_device(oracle):
+    """The dynamic-LDS limit belongs to a device's function object: a kernel that needs more than 64 KB runs first
+    on device 0, then on device 1, and both must give the CPU result bit for bit (the oracle's convolve for the
+    window, scipy's correlate1d -- the expectation of the 1-D filter tests -- for the line filter)."""
+    import scipy.ndimage as ndi
+    import torch
+    from nd_amd import kernels
+    rng = np.random.default_rng(31)
+    a = rng.normal(size=(2, 40, 70)).astype(np.float32)
+    box = np.ones((1, 31, 31)) / 961.0             # 62 staged rows of 1280 B plus the index maps: about 79 KB
+    want_box = oracle.convolve(a, box)
+    # correlate1d along y stages (32 + class - 1) rows of 128 doubles and a 4-byte map entry per row, 1028 B a
+    # row: 31 taps (class 31) are 62 rows = 63 736 B; 32 taps, the smallest count beyond 64 KB, take the class
+    # of 65: 96 rows = 98 688 B
+    w = rng.normal(size=32)
+    want_line = ndi.correlate1d(a, w, axis=1)
+    for idx in (0, 1):
+        t = torch.from_numpy(a).to(torch.device('cuda', idx))
+        got_box = kernels.convolve(t, box)
+        got_line = kernels.correlate1d(t, w, 1, torch.empty_like(t))
+        torch.cuda.synchronize(idx)
+        np.testing.assert_array_equal(got_box.cpu().numpy(), want_box, err_msg='device %d' % idx)
+        np.testing.assert_array_equal(got_line.cpu().numpy(), want_line, err_msg='device %d' % idx)
+
+
 def test_devices_argument_with_one_device_is_todays_path(oracle, device):
     """devices=[0] (and njobs=2 on a one-GPU box) degrade to the single-device result."""
     from nd_amd import xr_lite

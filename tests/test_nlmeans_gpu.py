@@ -60,7 +60,9 @@ def test_oracle_random(oracle, device, dtype, patch_mode):
                                   ((24, 25, 1, 1), (4, 4, 0), (2, 2, 0), 0.3, 0.4, -1),
                                   ((9, 8, 4, 3), (1, 2, 1), (0, 0, 0), 0.2, 0.6, -1),
                                   ((10, 11, 2, 4), (2, 2, 0), (1, 1, 0), 1.0, 3.0, 4.0),
-                                  ((1, 16, 16, 2), (0, 2, 2), (0, 1, 1), 0.5, 0.5, -1)]:
+                                  ((1, 16, 16, 2), (0, 2, 2), (0, 1, 1), 0.5, 0.5, -1),
+                                  # five variables: the per-pixel kernel's form for more than four
+                                  ((9, 8, 2, 5), (1, 2, 1), (1, 1, 0), 0.4, 0.6, -1)]:
         a = rng.gamma(4.0, 0.25, shape).astype(dtype)
         want = np.empty_like(a)
         oracle.pixelwise_nlmeans_3d(a, want, r, f, s, h, ne, neff_policy=0, njobs=8,
@@ -134,6 +136,47 @@ def test_tiled_kernels_planar_layout(oracle, device, patch_mode, case):
     np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
     if patch_mode == 0 and max(f) > 0 and ne < 0:
         np.testing.assert_array_equal(got, want)        # unit weights: bit-exact sums
+
+
+def _planar_case(oracle, device, a, r, f, ne, patch_mode):
+    """(y, x, time, var) view of planar memory through the tiled kernels -> (device result, oracle result)"""
+    want = np.empty_like(a)
+    oracle.pixelwise_nlmeans_3d(a, want, r, f, 0.5, 0.5, ne, neff_policy=0, njobs=8, patch_mode=patch_mode)
+    got = _gpu_nlm(a, r, f, 0.5, 0.5, ne, device, patch_mode=patch_mode, neff_policy=0, permute=(3, 2, 0, 1))
+    return got, want
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_window_kernels_on_both_sides_of_their_radius_classes(oracle, device, dtype):
+    """Unit-weight window sums.  float32 with up to 10 rows either side runs in the register-window kernel, one
+    instantiation per column radius 0 .. 10 (0, 5 | 6: the last unrolled square window and the first that is not,
+    10 | 11: the last of the list and the first window left to the plain kernel); float32 beyond, and float64
+    always, run in the plain window kernel, instantiated for column radii up to 4, 10 and 16.  The float64 window
+    of 23 x 33 takes more than 64 KB of LDS.  float32 sums are the reference's bit for bit."""
+    rng = np.random.default_rng(1016)
+    a = rng.gamma(4.0, 0.25, (40, 70, 1, 2)).astype(dtype)
+    for r0, r1 in [(2, 0), (5, 5), (2, 5), (2, 6), (2, 10), (2, 11), (2, 16), (11, 4), (11, 5), (11, 10), (11, 16)]:
+        got, want = _planar_case(oracle, device, a, (r0, r1, 0), (1, 1, 0), -1, 0)
+        np.testing.assert_allclose(got, want, rtol=RTOL, atol=0, err_msg=str((r0, r1)))
+        if dtype == np.float32:
+            np.testing.assert_array_equal(got, want, err_msg=str((r0, r1)))
+
+
+@pytest.mark.parametrize('nvars', [1, 2, 3, 4])
+def test_patch_kernels_every_patch_size(oracle, device, nvars):
+    """Signed mode, patches of 1 x 1 to 11 x 11 (f = 0 .. 5) of one to four variables, with and without n_eff: f = 0,
+    4 and 5 run in the one-column-per-lane kernel, f = 1 .. 3 in the two-column kernel (in the one-column kernel
+    too where test_one_column_patch_kernel_forced runs this test).  Column radii of 15 and more leave the
+    two-column kernel's constant-pitch tile (a margin of 16 columns holds r + 2, or r + 4 for f = 3, rounded up to
+    even): r = (2, 14) and (2, 15) for f = 1, 2, (2, 12) and (2, 13) for f = 3."""
+    rng = np.random.default_rng(50 + nvars)
+    a = rng.gamma(4.0, 0.25, (24, 70, 1, nvars)).astype(np.float32)
+    cases = [((2, 3, 0), f, ne) for f in range(6) for ne in (-1, 12.0)]
+    cases += [((2, r1, 0), f, ne) for f, r1, ne in ((1, 14, -1), (1, 15, 30.0), (2, 14, 30.0), (2, 15, -1), (3, 12, -1),
+                                                    (3, 13, 30.0))]
+    for r, f, ne in cases:
+        got, want = _planar_case(oracle, device, a, r, (f, f, 0), ne, 1)
+        np.testing.assert_allclose(got, want, rtol=RTOL, atol=0, err_msg=str((r, f, ne)))
 
 
 def test_tiled_halo_tile_equals_untiled(device):
@@ -413,7 +456,7 @@ def test_one_column_patch_kernel_forced(tmp_path):
     env = dict(os.environ, ND_AMD_NLM_PATCH1='1')
     with open(tmp_path / 'log', 'w') as fo:
         p = subprocess.run([sys.executable, '-m', 'pytest', os.path.abspath(__file__), '-q', '-x', '-p', 'no:cacheprovider',
-                            '-k', 'nodata or oracle_random or halo or tiny_weights or planar_layout'],
+                            '-k', 'nodata or oracle_random or halo or tiny_weights or planar_layout or every_patch_size'],
                            env=env, stdout=fo, stderr=subprocess.STDOUT, stdin=subprocess.DEVNULL, timeout=900,
                            cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     log = (tmp_path / 'log').read_text()
@@ -431,6 +474,8 @@ def test_one_column_patch_kernel_forced(tmp_path):
     (4, 7, 30, 100, (2, 3, 3), (1, 1, 1), 0.5, 0.5, -1),       # two dates either side, 4 variables: 8-row tiles
     (3, 6, 26, 90, (2, 2, 2), (0, 1, 1), 0.4, 0.5, 20.0),      # ... 3 variables, n_eff
     (2, 4, 20, 64, (1, 1, 1), (1, 0, 0), 0.4, 0.5, -1),        # patch along time only
+    (2, 4, 20, 64, (1, 2, 2), (0, 0, 0), 0.4, 0.5, 12.0),      # no patch at all: single-pixel distances
+    (3, 7, 26, 90, (2, 2, 2), (1, 1, 1), 0.4, 0.5, -1),        # seven planes of 3 variables: 8-row tiles
 ])
 def test_signed_mode_search_along_time_tiled_kernel(oracle, device, case):
     """patch_mode 1 with a search (and patch) extent along time on (time, y, x) arrays: nlmeans_patch3_kernel
