@@ -33,6 +33,7 @@
 // k % 4 == 0 and a 4-byte aligned span; anything else takes per-lane byte accesses.  No block-wide barrier:
 // a wave only reads the image it wrote (LDS operations of a wave complete in order).
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace nd_amd {
 
@@ -262,42 +263,26 @@ static int change_segments_impl(const void *const planes[], int64_t ny, int64_t 
     }
     g.change = change;
     g.direction = direction;
-    const bool flat = (sx == 1) && (sy == nx);                 // rows back to back: one long row
-    g.nx = flat ? ny * nx : nx;
+    RowWalk rw;
+    if (const int rc = row_walk("nd_amd_change_segments", ny, nx, sy, sx, false, kCsThreads, &rw)) return rc;
+    g.nx = rw.nx;
     g.sy = sy;
     g.sx = sx;
     g.st = st;
     g.k = k;
-    g.blocks_per_row = ceil_div(g.nx, kCsThreads);
-    const int64_t nblocks = g.blocks_per_row * (flat ? 1 : ny);
-    if (nblocks > 0x7fffffffLL) {
-        set_error("nd_amd_change_segments: raster too large for one launch");
-        return ND_AMD_EUNSUPPORTED;
-    }
-    const dim3 grid((unsigned)nblocks), block(kCsThreads);
+    g.blocks_per_row = rw.blocks_per_row;
+    const dim3 grid((unsigned)rw.nblocks()), block(kCsThreads);
     KernelTimer timer(ND_AMD_KERNEL_CHANGE_SEGMENTS, stream);
-    if (direction && means)
-        hipLaunchKernelGGL((change_segments_kernel<T, P, true, true>), grid, block, 0, stream, g);
-    else if (direction)
-        hipLaunchKernelGGL((change_segments_kernel<T, P, true, false>), grid, block, 0, stream, g);
-    else
-        hipLaunchKernelGGL((change_segments_kernel<T, P, false, true>), grid, block, 0, stream, g);
+    pick(direction != nullptr, [&](auto D) {
+        pick(means != nullptr, [&](auto M) {
+            // (the entry point admits no call that asks for neither)
+            if constexpr (decltype(D)::value || decltype(M)::value)
+                hipLaunchKernelGGL((change_segments_kernel<T, P, decltype(D)::value, decltype(M)::value>), grid,
+                                   block, 0, stream, g);
+        });
+    });
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;
-}
-
-template <typename T>
-static int change_segments_p(int nplanes, const void *const planes[], int64_t ny, int64_t nx, int64_t k, int64_t sy,
-                             int64_t sx, int64_t st, const uint8_t *change, int8_t *direction, void *const means[],
-                             hipStream_t stream)
-{
-    switch (nplanes) {
-    case 1: return change_segments_impl<T, 1>(planes, ny, nx, k, sy, sx, st, change, direction, means, stream);
-    case 2: return change_segments_impl<T, 2>(planes, ny, nx, k, sy, sx, st, change, direction, means, stream);
-    case 3: return change_segments_impl<T, 3>(planes, ny, nx, k, sy, sx, st, change, direction, means, stream);
-    case 4: return change_segments_impl<T, 4>(planes, ny, nx, k, sy, sx, st, change, direction, means, stream);
-    default: return change_segments_impl<T, 9>(planes, ny, nx, k, sy, sx, st, change, direction, means, stream);
-    }
 }
 
 }  // namespace nd_amd
@@ -308,10 +293,8 @@ extern "C" int nd_amd_change_segments(const void *const planes[], int nplanes, i
                                       int64_t nx, int64_t k, int64_t stride_y, int64_t stride_x, int64_t stride_t,
                                       const uint8_t *change, int8_t *direction, void *const means[], void *hip_stream)
 {
-    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
-        set_error("nd_amd_change_segments: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", dtype);
-        return ND_AMD_EINVAL;
-    }
+    constexpr const char *entry = "nd_amd_change_segments";
+    if (const int rc = check_dtype(entry, dtype)) return rc;
     if (structure != ND_AMD_STRUCT_DIAG && structure != ND_AMD_STRUCT_C2 && structure != ND_AMD_STRUCT_C3) {
         set_error("nd_amd_change_segments: structure must be ND_AMD_STRUCT_DIAG, _C2 or _C3, got %d", structure);
         return ND_AMD_EINVAL;
@@ -325,33 +308,28 @@ extern "C" int nd_amd_change_segments(const void *const planes[], int nplanes, i
                   nplanes);
         return ND_AMD_EINVAL;
     }
-    if (ny < 0 || nx < 0 || k < 0) {
-        set_error("nd_amd_change_segments: negative shape");
-        return ND_AMD_EINVAL;
-    }
+    bool empty;
+    if (const int rc = check_shape(entry, ny, nx, k, &empty)) return rc;
     if (!direction && !means) {
         set_error("nd_amd_change_segments: neither direction nor means is asked for");
         return ND_AMD_EINVAL;
     }
-    if (ny == 0 || nx == 0 || k == 0) return ND_AMD_OK;
-    if (!planes || !change) {
-        set_error("nd_amd_change_segments: null data pointer");
-        return ND_AMD_EINVAL;
-    }
-    for (int p = 0; p < nplanes; ++p) {
-        if (!planes[p]) {
-            set_error("nd_amd_change_segments: plane %d is null", p);
-            return ND_AMD_EINVAL;
-        }
-        if (means && !means[p]) {
+    if (empty) return ND_AMD_OK;
+    if (const int rc = check_planes(entry, planes, nplanes, change)) return rc;
+    for (int p = 0; means && p < nplanes; ++p)
+        if (!means[p]) {
             set_error("nd_amd_change_segments: means plane %d is null", p);
             return ND_AMD_EINVAL;
         }
-    }
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return change_segments_p<float>(nplanes, planes, ny, nx, k, stride_y, stride_x, stride_t, change, direction,
-                                        means, stream);
-    return change_segments_p<double>(nplanes, planes, ny, nx, k, stride_y, stride_x, stride_t, change, direction,
-                                     means, stream);
+    int rc = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        auto run = [&](auto P) {
+            rc = change_segments_impl<T, decltype(P)::value>(planes, ny, nx, k, stride_y, stride_x, stride_t,
+                                                             change, direction, means, stream);
+        };
+        if (!pick_eq<1, 2, 3, 4>(nplanes, run)) run(int_c<9>{});     // (nine planes: C3, checked above)
+    });
+    return rc;
 }

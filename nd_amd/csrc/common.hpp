@@ -8,11 +8,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "../../include/nd_amd.h"
+#include "entry_args.hpp"   // set_error, ceil_div, the entry checks and grid helpers (host only, no HIP)
 
 namespace nd_amd {
-
-void set_error(const char *fmt, ...);
 
 #define ND_HIP_CHECK(expr)                                                        \
     do {                                                                          \
@@ -31,8 +29,6 @@ struct KernelTimer {
     int slot;
     hipStream_t stream;
 };
-
-static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Lets `kernel` be launched with `bytes` of dynamic LDS (a launch beyond 64 KB needs the attribute raised first).
 // It belongs to the CURRENT device's function object, so callers set it on every launch that needs it.

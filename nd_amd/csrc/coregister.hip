@@ -20,6 +20,7 @@
 #include <tuple>
 
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace nd_amd {
 
@@ -493,13 +494,11 @@ static int coreg_shifts_impl(const void *c11, int64_t k, int64_t ny, int64_t nx,
     const int mi = (R + 15) / 16;
     const int MI = mi > 5 ? 4 : mi;            // region columns per block: 16 MI
     const dim3 gx((unsigned)ceil_div(R, 16 * MI), (unsigned)ceil_div(ny, DX_ROWS), (unsigned)k);
-    switch (MI) {
-    case 1: hipLaunchKernelGGL((coreg_dft_x_kernel<T, 1>), gx, dim3(256), 0, stream, F, ref, tb, A, B, ny, nx, nh, R); break;
-    case 2: hipLaunchKernelGGL((coreg_dft_x_kernel<T, 2>), gx, dim3(256), 0, stream, F, ref, tb, A, B, ny, nx, nh, R); break;
-    case 3: hipLaunchKernelGGL((coreg_dft_x_kernel<T, 3>), gx, dim3(256), 0, stream, F, ref, tb, A, B, ny, nx, nh, R); break;
-    case 4: hipLaunchKernelGGL((coreg_dft_x_kernel<T, 4>), gx, dim3(256), 0, stream, F, ref, tb, A, B, ny, nx, nh, R); break;
-    default: hipLaunchKernelGGL((coreg_dft_x_kernel<T, 5>), gx, dim3(256), 0, stream, F, ref, tb, A, B, ny, nx, nh, R); break;
-    }
+    auto dft_x = [&](auto M) {
+        hipLaunchKernelGGL((coreg_dft_x_kernel<T, decltype(M)::value>), gx, dim3(256), 0, stream, F, ref, tb, A,
+                           B, ny, nx, nh, R);
+    };
+    if (!pick_eq<1, 2, 3, 4>(MI, dft_x)) dft_x(int_c<5>{});
     ND_HIP_CHECK(hipGetLastError());
     double *mag = reinterpret_cast<double *>(ws + L.mag);
     hipLaunchKernelGGL(coreg_dft_y_kernel, dim3((unsigned)R, (unsigned)k), dim3(256), 0, stream, tb, A, B, mag, ny, R);
@@ -903,11 +902,13 @@ extern "C" int nd_amd_coregister_shifts(const void *c11, int dtype, int64_t k, i
         return ND_AMD_EWORKSPACE;
     }
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return coreg_shifts_impl<float>(c11, k, ny, nx, stride_t, stride_y, stride_x, reference, upsampling, shifts,
-                                        status, workspace, stream);
-    return coreg_shifts_impl<double>(c11, k, ny, nx, stride_t, stride_y, stride_x, reference, upsampling, shifts,
-                                     status, workspace, stream);
+    int rc = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        rc = coreg_shifts_impl<T>(c11, k, ny, nx, stride_t, stride_y, stride_x, reference, upsampling, shifts,
+                                  status, workspace, stream);
+    });
+    return rc;
 }
 
 extern "C" size_t nd_amd_warp_translate_workspace_bytes(int dtype, int nvars, int64_t k, int64_t nr, int64_t nc,
@@ -960,7 +961,10 @@ extern "C" int nd_amd_warp_translate(const void *const *in, void *const *out, in
         return ND_AMD_EWORKSPACE;
     }
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return warp_impl<float>(in, out, nvars, k, nr, nc, layout, shifts, reference, workspace, stream);
-    return warp_impl<double>(in, out, nvars, k, nr, nc, layout, shifts, reference, workspace, stream);
+    int rc = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        rc = warp_impl<T>(in, out, nvars, k, nr, nc, layout, shifts, reference, workspace, stream);
+    });
+    return rc;
 }

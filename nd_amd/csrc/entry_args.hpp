@@ -1,0 +1,121 @@
+// nd_amd/csrc/entry_args.hpp -- what the change-detection entries (nd_amd_omnibus_c2 / _c2_ml / _c2_pixel_major,
+// _c3 / _c3_pixel_major, _diag, nd_amd_change_segments) decide alike, written once: which arguments are
+// acceptable, how a raster is walked in rows, and how many blocks walk a sharded candidate list.  Plain C++:
+// no HIP header and no device symbol, so every unit may include it (common.hpp does) and a CPU checks it
+// (tools/check_entry_args.cpp, tests/test_host_logic.py).
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/nd_amd.h"
+
+namespace nd_amd {
+
+void set_error(const char *fmt, ...);
+
+static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- entry checks: ND_AMD_OK to go on, or the code to return with the message set.  `entry` is the entry
+// point's name.  An entry keeps what only it checks between these calls.  Every refusal here is ND_AMD_EINVAL
+// except the pixel index's ND_AMD_EUNSUPPORTED, so among the checks only their place relative to that one and
+// to the empty raster's ND_AMD_OK can change a return code (tests/test_host_logic.py pins both).
+static inline int check_dtype(const char *entry, int dtype)
+{
+    if (dtype == ND_AMD_F32 || dtype == ND_AMD_F64) return ND_AMD_OK;
+    set_error("%s: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", entry, dtype);
+    return ND_AMD_EINVAL;
+}
+
+// A negative dimension is refused; *empty says that there is nothing to write.  The entry returns ND_AMD_OK on
+// it where it always did: behind the checks that it makes on an empty raster too, before the pointers are looked at.
+static inline int check_shape(const char *entry, int64_t ny, int64_t nx, int64_t k, bool *empty)
+{
+    *empty = ny == 0 || nx == 0 || k == 0;
+    if (ny >= 0 && nx >= 0 && k >= 0) return ND_AMD_OK;
+    set_error("%s: negative shape (%lld, %lld, %lld)", entry, (long long)ny, (long long)nx, (long long)k);
+    return ND_AMD_EINVAL;
+}
+
+static inline int check_planes(const char *entry, const void *const planes[], int n, const void *change)
+{
+    if (!planes || !change) {
+        set_error("%s: null data pointer", entry);
+        return ND_AMD_EINVAL;
+    }
+    for (int p = 0; p < n; ++p)
+        if (!planes[p]) {
+            set_error("%s: plane %d is null", entry, p);
+            return ND_AMD_EINVAL;
+        }
+    return ND_AMD_OK;
+}
+
+static inline int check_looks(const char *entry, uint32_t n_looks)
+{
+    if (n_looks >= 1) return ND_AMD_OK;
+    set_error("%s: n_looks must be >= 1", entry);
+    return ND_AMD_EINVAL;
+}
+
+// pixels are listed by 32-bit index, 0xffffffff being the list's "none"
+static inline int check_pixel_index(const char *entry, int64_t ny, int64_t nx)
+{
+    if (ny * nx < 0xffffffffLL) return ND_AMD_OK;
+    set_error("%s: raster of %lld pixels exceeds the 32-bit pixel index", entry, (long long)(ny * nx));
+    return ND_AMD_EUNSUPPORTED;
+}
+
+// the pixel-major entries: a variable's dates lie 1 (real) or 2 (one half of an interleaved complex array) apart
+static inline int check_date_strides(const char *entry, const int64_t *date_stride, int n)
+{
+    if (!date_stride) {
+        set_error("%s: date_stride is null", entry);
+        return ND_AMD_EINVAL;
+    }
+    for (int v = 0; v < n; ++v)
+        if (date_stride[v] != 1 && date_stride[v] != 2) {
+            set_error("%s: date strides must be 1 or 2, got %lld for variable %d", entry, (long long)date_stride[v], v);
+            return ND_AMD_EINVAL;
+        }
+    return ND_AMD_OK;
+}
+
+// ---- grids
+// Blocks per shard that walk a candidate list of at most `listed` entries spread over `shards` shards, a block
+// taking `per_block` entries at a time and striding through its shard's list: enough for one turn each, at most
+// `cap` (what the chip holds; the blocks then take more turns), and never none -- zero blocks is a failed launch.
+static inline int64_t shard_blocks(int64_t listed, int64_t shards, int64_t per_block, int64_t cap)
+{
+    const int64_t n = ceil_div(ceil_div(listed, shards), per_block);
+    return n > cap ? cap : (n < 1 ? 1 : n);
+}
+
+// How a launch walks a raster: row by row, or -- rows back to back (stride_x == 1, stride_y == nx), and always
+// for pixel-major input (force_flat) -- as ONE row of ny * nx pixels, so that no block is cut short at a row's
+// end.  blocks_per_row blocks of px_per_block pixels cover a row; block b serves row b / blocks_per_row.
+struct RowWalk {
+    bool flat;
+    int64_t nx, nrows, blocks_per_row;
+    int64_t nblocks() const { return blocks_per_row * nrows; }
+};
+
+// the same rows in blocks of another width; ND_AMD_EUNSUPPORTED beyond the 2^31 - 1 blocks of one launch
+// (only a strided raster of 2^31 rows and more gets there)
+static inline int row_blocks(const char *entry, RowWalk *w, int64_t px_per_block)
+{
+    w->blocks_per_row = ceil_div(w->nx, px_per_block);
+    if (w->nblocks() <= 0x7fffffffLL) return ND_AMD_OK;
+    set_error("%s: raster too large for one launch (%lld blocks)", entry, (long long)w->nblocks());
+    return ND_AMD_EUNSUPPORTED;
+}
+
+static inline int row_walk(const char *entry, int64_t ny, int64_t nx, int64_t sy, int64_t sx, bool force_flat,
+                           int64_t px_per_block, RowWalk *w)
+{
+    w->flat = force_flat || (sx == 1 && sy == nx);
+    w->nx = w->flat ? ny * nx : nx;
+    w->nrows = w->flat ? 1 : ny;
+    return row_blocks(entry, w, px_per_block);
+}
+
+}  // namespace nd_amd

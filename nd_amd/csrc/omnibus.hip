@@ -3192,18 +3192,17 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
                                         (uintptr_t)c22) & 15) == 0 &&
                          ((sy * (int64_t)es) % 16 == 0) && ((st * (int64_t)es) % 16 == 0);
     // pixel-major inputs are walked as one flat row of pixels as well
-    const bool flat = ((sx == 1) && (sy == nx)) || pm_ids != nullptr;
-    g.nx = flat ? npix : nx;
-    g.nrows = flat ? 1 : ny;
     unsigned long long *const hand_ws = reinterpret_cast<unsigned long long *>(ws + w.off_hand);
     const int ppt = retain ? 1 : (aligned ? VPPT : 1);
-    g.blocks_per_row = ceil_div(g.nx, retain ? (int64_t)kRetainThreads : (int64_t)kGlobalThreads * ppt);
-    const int64_t nblocks = g.blocks_per_row * g.nrows;
-    if (nblocks > 0x7fffffffLL) {
-        set_error("nd_amd_omnibus_c2: raster too large for one launch (%lld blocks)",
-                  (long long)nblocks);
-        return ND_AMD_EUNSUPPORTED;
-    }
+    RowWalk rw;
+    if (const int rc = row_walk("nd_amd_omnibus_c2", ny, nx, sy, sx, pm_ids != nullptr,
+                                retain ? (int64_t)kRetainThreads : (int64_t)kGlobalThreads * ppt, &rw))
+        return rc;
+    const bool flat = rw.flat;
+    g.nx = rw.nx;
+    g.nrows = rw.nrows;
+    g.blocks_per_row = rw.blocks_per_row;
+    const int64_t nblocks = rw.nblocks();
     // returns true when the sample was taken (the kernels launched next may then be gated)
     auto take_sample = [&]() -> bool {
         const int64_t sblocks_total = ceil_div(npix, (int64_t)kRetainThreads);
@@ -3262,10 +3261,8 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         d.seg = seg;
         d.dump = dump;
         d.dump_cap = dump_cap;
-        int64_t per_shard_d = ceil_div(ceil_div(npix_listed, (int64_t)kShards), 64);
-        if (per_shard_d > 32) per_shard_d = 32;     // 4096 waves: two rounds of what the chip holds
-        if (per_shard_d < 1) per_shard_d = 1;
-        const dim3 gridd((unsigned)(per_shard_d * kShards)), blockd(64);
+        // (at most 4096 waves: two rounds of what the chip holds)
+        const dim3 gridd((unsigned)(shard_blocks(npix_listed, kShards, 64, 32) * kShards)), blockd(64);
         const DenseScreen scr = make_dense_screen<T>(htab, (int)k, n_looks);
         const StreamScreen<32> ssd = make_stream_screen<T, 32>(htab, scr, (int)k, n_looks);
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_DENSE, sq);
@@ -3339,10 +3336,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
             });
         };
         // kShards x (blocks per shard); a shard's blocks stride through its list
-        int64_t per_shard = ceil_div(ceil_div(npix_listed, kShards), 64);
-        if (per_shard > 64) per_shard = 64;
-        if (per_shard < 1) per_shard = 1;
-        const int64_t sblocks = per_shard * kShards;
+        const int64_t sblocks = shard_blocks(npix_listed, kShards, 64, 64) * kShards;
         static const int mode_env = env_int("ND_AMD_SEARCH_MODE", -1);     // 0 LDS image, 1 from memory, 3 chain form
         // The register form serves the series lengths of dense_search, as long as the screen can
         // decide tests at all (it cannot where omega2 leaves [0, 1], e.g. single-look data: every
@@ -3402,7 +3396,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         //  DESIGN-EXPERIMENTS.md, round 6)
         const bool from_dump = split_ok && dump_cap > 0;
         const int mode = (mode_env == 0 || mode_env == 1) ? mode_env : ((use_lds && !behind && !from_dump) ? 0 : 1);
-        const int64_t xblocks = behind ? (per_shard > 16 ? 16 : per_shard) * kShards : sblocks;
+        const int64_t xblocks = behind ? shard_blocks(npix_listed, kShards, 64, 16) * kShards : sblocks;
         // behind the time-split pass A the dump is BLOCKED (64 series interleaved date by date): the lockstep sweep
         // is its only reader; what the dump could not hold is gathered from the planes by the from-memory form
         // (ND_AMD_SEARCH_MODE / ND_AMD_SEARCH_PXW do not apply to this path)
@@ -3422,10 +3416,7 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         const int pxw = pxw_env ? pxw_env : (lds_bytes > 48 * 1024 ? 16 : 64);
         if (mode == 0 && use_lds && !behind && (pxw == 32 || pxw == 16)) {
             const size_t lds_n = (size_t)k * 4 * (size_t)pxw * sizeof(T) + scr_bytes;
-            int64_t ps = ceil_div(ceil_div(npix_listed, kShards), (int64_t)pxw);
-            if (ps > 256) ps = 256;
-            if (ps < 1) ps = 1;
-            const dim3 gn((unsigned)(ps * kShards));
+            const dim3 gn((unsigned)(shard_blocks(npix_listed, kShards, pxw, 256) * kShards));
             hipError_t e = hipSuccess;
             pick_eq<32, 16>(pxw, [&](auto P) {      // (8 per wave measured the same: the gather's sector traffic bounds it)
                 if (lds_n > 64 * 1024) e = allow_image_lds(P, lds_n);
@@ -3823,12 +3814,9 @@ static int omnibus_c2_impl(const void *c11, const void *c12re, const void *c12im
         g.gate_mode = 0;
     } else if (split_ok) {
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
-        g.blocks_per_row = ceil_div(g.nx, (int64_t)64);
-        const int64_t nbs = g.blocks_per_row * g.nrows;
-        if (nbs > 0x7fffffffLL) {
-            set_error("nd_amd_omnibus_c2: raster too large for one launch (%lld blocks)", (long long)nbs);
-            return ND_AMD_EUNSUPPORTED;
-        }
+        if (const int rc = row_blocks("nd_amd_omnibus_c2", &rw, 64)) return rc;     // a wave's pixels per block
+        g.blocks_per_row = rw.blocks_per_row;
+        const int64_t nbs = rw.nblocks();
         // rounding band of the re-associated sums: 3 (5 k + 8) u (see the kernel), u = half an ulp of T
         const float rel = 3.f * (5.f * (float)k + 8.f) * (sizeof(T) == 4 ? 5.9604645e-08f : 1.1102230e-16f);
         const dim3 grid((unsigned)nbs);
@@ -3902,6 +3890,21 @@ extern "C" int nd_amd_omnibus_c2_uses_wave_search(int dtype, int64_t k, int64_t 
     return omni_c2_wave_search(dtype, k, stride_x, alpha, n_looks, stats != 0) ? 1 : 0;
 }
 
+// the planar and the pixel-major entry end alike: float32 or float64 of omnibus_c2_impl
+static int omnibus_c2_run(int dtype, const void *const pl[4], int64_t ny, int64_t nx, int64_t k, int64_t sy,
+                          int64_t sx, int64_t st, uint32_t n_looks, double alpha, uint8_t *change, void *z_out,
+                          void *p_out, void *workspace, size_t workspace_bytes, void *hip_stream,
+                          const int64_t *pm_ids)
+{
+    int rc = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        rc = omnibus_c2_impl<T>(pl[0], pl[1], pl[2], pl[3], ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out,
+                                p_out, workspace, workspace_bytes, static_cast<hipStream_t>(hip_stream), pm_ids);
+    });
+    return rc;
+}
+
 extern "C" int nd_amd_omnibus_c2(const void *c11, const void *c12re, const void *c12im,
                                  const void *c22, int dtype, int64_t ny, int64_t nx, int64_t k,
                                  int64_t stride_y, int64_t stride_x, int64_t stride_t,
@@ -3909,37 +3912,21 @@ extern "C" int nd_amd_omnibus_c2(const void *c11, const void *c12re, const void 
                                  void *p_out, void *workspace, size_t workspace_bytes,
                                  void *hip_stream)
 {
-    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
-        set_error("nd_amd_omnibus_c2: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", dtype);
-        return ND_AMD_EINVAL;
-    }
-    if (ny < 0 || nx < 0 || k < 0) {
-        set_error("nd_amd_omnibus_c2: negative shape (%lld, %lld, %lld)", (long long)ny,
-                  (long long)nx, (long long)k);
-        return ND_AMD_EINVAL;
-    }
-    if (ny == 0 || nx == 0 || k == 0) return ND_AMD_OK;   // nothing to write
-    if (!c11 || !c12re || !c12im || !c22 || !change) {
-        set_error("nd_amd_omnibus_c2: null data pointer");
-        return ND_AMD_EINVAL;
-    }
-    if (n_looks == 0) {
-        set_error("nd_amd_omnibus_c2: n_looks must be >= 1");
-        return ND_AMD_EINVAL;
-    }
-    if (ny * nx >= 0xffffffffLL || k > 0x3fffffff) {
-        set_error("nd_amd_omnibus_c2: raster of %lld pixels exceeds the 32-bit pixel index",
-                  (long long)(ny * nx));
+    constexpr const char *entry = "nd_amd_omnibus_c2";
+    const void *const pl[4] = {c11, c12re, c12im, c22};
+    if (const int rc = check_dtype(entry, dtype)) return rc;
+    bool empty;
+    if (const int rc = check_shape(entry, ny, nx, k, &empty)) return rc;
+    if (empty) return ND_AMD_OK;   // nothing to write
+    if (const int rc = check_planes(entry, pl, 4, change)) return rc;
+    if (const int rc = check_looks(entry, n_looks)) return rc;
+    if (const int rc = check_pixel_index(entry, ny, nx)) return rc;
+    if (k > 0x3fffffff) {
+        set_error("nd_amd_omnibus_c2: k = %lld exceeds the supported number of dates", (long long)k);
         return ND_AMD_EUNSUPPORTED;
     }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return omnibus_c2_impl<float>(c11, c12re, c12im, c22, ny, nx, k, stride_y, stride_x,
-                                      stride_t, n_looks, alpha, change, z_out, p_out, workspace,
-                                      workspace_bytes, stream);
-    return omnibus_c2_impl<double>(c11, c12re, c12im, c22, ny, nx, k, stride_y, stride_x,
-                                   stride_t, n_looks, alpha, change, z_out, p_out, workspace,
-                                   workspace_bytes, stream);
+    return omnibus_c2_run(dtype, pl, ny, nx, k, stride_y, stride_x, stride_t, n_looks, alpha, change, z_out,
+                          p_out, workspace, workspace_bytes, hip_stream, nullptr);
 }
 
 extern "C" size_t nd_amd_omnibus_c2_ml_workspace_bytes(int dtype, int64_t ny, int64_t nx, int64_t k, int ml)
@@ -3955,31 +3942,27 @@ extern "C" int nd_amd_omnibus_c2_ml(const void *c11, const void *c12re, const vo
                                     uint8_t *change, void *z_out, void *p_out, void *workspace,
                                     size_t workspace_bytes, void *hip_stream)
 {
-    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
-        set_error("nd_amd_omnibus_c2_ml: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", dtype);
+    constexpr const char *entry = "nd_amd_omnibus_c2_ml";
+    const void *const pl[4] = {c11, c12re, c12im, c22};
+    if (const int rc = check_dtype(entry, dtype)) return rc;
+    bool empty;
+    if (const int rc = check_shape(entry, ny, nx, k, &empty)) return rc;
+    if (ml < 1) {
+        set_error("nd_amd_omnibus_c2_ml: bad window (ml = %d)", ml);
         return ND_AMD_EINVAL;
     }
-    if (ny < 0 || nx < 0 || k < 0 || ml < 1) {
-        set_error("nd_amd_omnibus_c2_ml: bad shape or window (%lld, %lld, %lld; ml = %d)", (long long)ny,
-                  (long long)nx, (long long)k, ml);
-        return ND_AMD_EINVAL;
-    }
-    if (ny == 0 || nx == 0 || k == 0) return ND_AMD_OK;
-    if (!c11 || !c12re || !c12im || !c22 || !change) {
-        set_error("nd_amd_omnibus_c2_ml: null data pointer");
-        return ND_AMD_EINVAL;
-    }
+    if (empty) return ND_AMD_OK;
+    if (const int rc = check_planes(entry, pl, 4, change)) return rc;
+    if (const int rc = check_pixel_index(entry, ny, nx)) return rc;
     OmniMlPlan p;
-    if (ny * nx >= 0xffffffffLL ||
-        !omni_ml_plan(ny, nx, k, stride_y, stride_x, stride_t, ml, dtype, &p)) {
+    if (!omni_ml_plan(ny, nx, k, stride_y, stride_x, stride_t, ml, dtype, &p)) {
         set_error("nd_amd_omnibus_c2_ml: fused multilooking covers float32, x-contiguous planes, ml = 3 or 5, "
                   "2 <= k <= 24 (multilook with nd_amd_correlate and call nd_amd_omnibus_c2 otherwise)");
         return ND_AMD_EUNSUPPORTED;
     }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     return omnibus_c2_impl<float>(c11, c12re, c12im, c22, ny, nx, k, stride_y, stride_x, stride_t,
                                   (uint32_t)(ml * ml), alpha, change, z_out, p_out, workspace,
-                                  workspace_bytes, stream, nullptr, &p);
+                                  workspace_bytes, static_cast<hipStream_t>(hip_stream), nullptr, &p);
 }
 
 extern "C" int nd_amd_omnibus_c2_pixel_major(const void *c11, const void *c12re, const void *c12im,
@@ -3989,43 +3972,25 @@ extern "C" int nd_amd_omnibus_c2_pixel_major(const void *c11, const void *c12re,
                                              void *z_out, void *p_out, void *workspace,
                                              size_t workspace_bytes, void *hip_stream)
 {
-    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
-        set_error("nd_amd_omnibus_c2_pixel_major: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", dtype);
-        return ND_AMD_EINVAL;
-    }
-    if (ny < 0 || nx < 0 || k < 0 || !date_stride) {
-        set_error("nd_amd_omnibus_c2_pixel_major: bad shape");
-        return ND_AMD_EINVAL;
-    }
-    for (int vi = 0; vi < 4; ++vi)
-        if (date_stride[vi] != 1 && date_stride[vi] != 2) {
-            set_error("nd_amd_omnibus_c2_pixel_major: date strides must be 1 or 2");
-            return ND_AMD_EINVAL;
-        }
+    constexpr const char *entry = "nd_amd_omnibus_c2_pixel_major";
+    const void *const pl[4] = {c11, c12re, c12im, c22};
+    if (const int rc = check_dtype(entry, dtype)) return rc;
+    bool empty;
+    if (const int rc = check_shape(entry, ny, nx, k, &empty)) return rc;
+    if (const int rc = check_date_strides(entry, date_stride, 4)) return rc;      // (on an empty raster too)
     if (date_stride[1] != date_stride[2]) {
         set_error("nd_amd_omnibus_c2_pixel_major: the two halves of C12 must share their stride");
         return ND_AMD_EINVAL;
     }
-    if (ny == 0 || nx == 0 || k == 0) return ND_AMD_OK;
-    if (!c11 || !c12re || !c12im || !c22 || !change) {
-        set_error("nd_amd_omnibus_c2_pixel_major: null data pointer");
-        return ND_AMD_EINVAL;
-    }
-    if (n_looks == 0) {
-        set_error("nd_amd_omnibus_c2_pixel_major: n_looks must be >= 1");
-        return ND_AMD_EINVAL;
-    }
-    if (ny * nx >= 0xffffffffLL || k > 192) {
-        set_error("nd_amd_omnibus_c2_pixel_major: at most 192 dates and 2^32 - 1 pixels");
+    if (empty) return ND_AMD_OK;
+    if (const int rc = check_planes(entry, pl, 4, change)) return rc;
+    if (const int rc = check_looks(entry, n_looks)) return rc;
+    if (const int rc = check_pixel_index(entry, ny, nx)) return rc;
+    if (k > 192) {
+        set_error("nd_amd_omnibus_c2_pixel_major: at most 192 dates, got %lld", (long long)k);
         return ND_AMD_EUNSUPPORTED;
     }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     // unit-stride geometry of the layout: (y, x, t) -> (y * nx + x) * k + t
-    if (dtype == ND_AMD_F32)
-        return omnibus_c2_impl<float>(c11, c12re, c12im, c22, ny, nx, k, nx * k, k, 1, n_looks, alpha,
-                                      change, z_out, p_out, workspace, workspace_bytes, stream,
-                                      date_stride);
-    return omnibus_c2_impl<double>(c11, c12re, c12im, c22, ny, nx, k, nx * k, k, 1, n_looks, alpha,
-                                   change, z_out, p_out, workspace, workspace_bytes, stream,
-                                   date_stride);
+    return omnibus_c2_run(dtype, pl, ny, nx, k, nx * k, k, 1, n_looks, alpha, change, z_out, p_out, workspace,
+                          workspace_bytes, hip_stream, date_stride);
 }

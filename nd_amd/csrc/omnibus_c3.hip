@@ -1616,24 +1616,21 @@ static bool c3_retain_ok(const C3Workspace &w, const C3Args<T> &g)
     return sizeof(T) == 4 && w.dump_cap > 0 && g.k >= 2 && g.k <= kC3RetainMaxK && g.lane32 != 0;
 }
 
-static int c3_launch_retain(const C3Workspace &, C3Args<double> &, const OmniTab &, unsigned char *, hipStream_t)
+static int c3_launch_retain(const C3Workspace &, C3Args<double> &, RowWalk, const OmniTab &, unsigned char *,
+                            hipStream_t)
 {
     return ND_AMD_EUNSUPPORTED;          // (float32 only: c3_retain_ok)
 }
 
-static int c3_launch_retain(const C3Workspace &w, C3Args<float> &g, const OmniTab &tab, unsigned char *ws,
-                            hipStream_t stream)
+static int c3_launch_retain(const C3Workspace &w, C3Args<float> &g, RowWalk rw, const OmniTab &tab,
+                            unsigned char *ws, hipStream_t stream)
 {
     g.dump = reinterpret_cast<float *>(ws + w.off_dump);
     g.dump_cap = w.dump_cap;
     g.dump_stride = w.dump_stride;
-    g.blocks_per_row = ceil_div(g.nx, (int64_t)64);
-    const int64_t nblocks = g.blocks_per_row * g.nrows;
-    if (nblocks > 0x7fffffffLL) {
-        set_error("nd_amd_omnibus_c3: raster too large for one launch");
-        return ND_AMD_EUNSUPPORTED;
-    }
-    const dim3 grid((unsigned)nblocks), block((unsigned)(64 * kC3Slices));
+    if (const int rc = row_blocks("nd_amd_omnibus_c3", &rw, 64)) return rc;      // a wave's pixels per block
+    g.blocks_per_row = rw.blocks_per_row;
+    const dim3 grid((unsigned)rw.nblocks()), block((unsigned)(64 * kC3Slices));
     // (w.kq is a multiple of 4, at most 16 where c3_retain_ok holds)
     pick_le<4, 8, 12, 16>(w.kq, [&](auto KQ) {
         hipLaunchKernelGGL((omnibus_c3_retain_kernel<decltype(KQ)::value>), grid, block, 0, stream, g, tab);
@@ -1667,14 +1664,15 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
         g.mult[c] = pm_ids ? (int)pm_ids[c] : 1;
     }
     g.pm_vec = 0;
-    const bool flat = ((sx == 1) && (sy == nx)) || pm_ids != nullptr;
-    g.nx = flat ? npix : nx;
-    g.nrows = flat ? 1 : ny;
+    RowWalk rw;
+    if (const int rc = row_walk("nd_amd_omnibus_c3", ny, nx, sy, sx, pm_ids != nullptr, kC3Threads, &rw)) return rc;
+    g.nx = rw.nx;
+    g.nrows = rw.nrows;
     g.nx_orig = nx;
     g.sy = sy;
     g.sx = sx;
     g.st = st;
-    g.blocks_per_row = ceil_div(g.nx, kC3Threads);
+    g.blocks_per_row = rw.blocks_per_row;
     g.k = (int)k;
     g.write_tab = 1;
     g.off32 = (sx >= 0 && sy >= 0 && st >= 0 &&
@@ -1694,11 +1692,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     g.dump = nullptr;
     g.dump_cap = g.dump_stride = 0;
     g.retain_rel = 3.f * (21.f * (float)k + 40.f) * 5.9604645e-08f;
-    const int64_t nblocks = g.blocks_per_row * g.nrows;
-    if (nblocks > 0x7fffffffLL) {
-        set_error("nd_amd_omnibus_c3: raster too large for one launch");
-        return ND_AMD_EUNSUPPORTED;
-    }
+    const int64_t nblocks = rw.nblocks();
     ND_HIP_CHECK(hipMemsetAsync(g.flag_count, 0, kC3CounterBytes, stream));
     const bool stats = z_out != nullptr || p_out != nullptr;
     // Low thresholds: the search fused into the streaming pass (speed only, same map).
@@ -1759,7 +1753,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     if (!fused && !stats && !exact_flags && c3_retain_ok<T>(w, g)) {
         // the sparse design with the candidates' series handed over from registers (omnibus_c3_retain_kernel)
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_GLOBAL, stream);
-        if (int rc = c3_launch_retain(w, g, tab, ws, stream)) return rc;
+        if (int rc = c3_launch_retain(w, g, rw, tab, ws, stream)) return rc;
     } else
     if (!fused || stats) {
         // the sparse design -- or, with a fused search, only the z / P rasters of it
@@ -1817,10 +1811,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     if (use_lds && lds_bytes > 64 * 1024) {
         ND_HIP_CHECK(allow_dynamic_lds(&omnibus_c3_search_kernel<T, true>, lds_bytes));
     }
-    int64_t per_shard = ceil_div(ceil_div(npix, kC3Shards), 64);
-    if (per_shard > 64) per_shard = 64;
-    if (per_shard < 1) per_shard = 1;
-    const int64_t sblocks = per_shard * kC3Shards;
+    const int64_t sblocks = shard_blocks(npix, kC3Shards, 64, 64) * kC3Shards;
     // Pixels per wave: as many as keep the image at ~32 KB, i.e. five waves per CU taking turns at
     // gathering and searching.  Config 4's share (k = 48): 64 / 32 / 16 pixels per wave -> pass B
     // 1.58 / 1.35 / 1.28 ms.  ND_AMD_C3_LANES = 64 / 32 / 16 forces a width.
@@ -1832,9 +1823,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     if (g.dump != nullptr) {
         // the candidates whose series pass A dumped from its registers
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_SEARCH, stream);
-        int64_t per_shard_d = ceil_div((int64_t)g.dump_cap, 64);
-        if (per_shard_d > 64) per_shard_d = 64;
-        if (per_shard_d < 1) per_shard_d = 1;
+        const int64_t per_shard_d = shard_blocks(g.dump_cap, 1, 64, 64);      // (dump_cap is a shard's share already)
         // lockstep rounds on the blocked dump; the lane-per-pixel form (omnibus_c3_search_dump_kernel<T, 1 / 2>) stays
         // for pixel-major inputs, whose series are read where they lie
         const DenseScreen fscr = make_dense_screen<T>(htab, (int)k, n_looks);
@@ -1845,10 +1834,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
     if (g.pm_vec) {
         // pixel-major inputs: every listed pixel read where it lies in the caller's arrays
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_SEARCH, stream);
-        int64_t per_shard_d = ceil_div(ceil_div(npix, kC3Shards), 64);
-        if (per_shard_d > 64) per_shard_d = 64;
-        if (per_shard_d < 1) per_shard_d = 1;
-        const dim3 gridd((unsigned)(per_shard_d * kC3Shards));
+        const dim3 gridd((unsigned)(shard_blocks(npix, kC3Shards, 64, 64) * kC3Shards));
         pick(g.mult[3] == 2, [&](auto C) {      // interleaved complex arrays, or nine real ones
             hipLaunchKernelGGL((omnibus_c3_search_dump_kernel<T, decltype(C)::value ? 2 : 1>), gridd, dim3(64), scr_bytes, stream, g);
         });
@@ -1859,10 +1845,7 @@ static int omnibus_c3_impl(const void *const planes[9], int64_t ny, int64_t nx, 
         if (halves) {
             const int lanes = c3_lanes == 16 ? 16 : 32;
             const size_t lds_part = (size_t)k * 9 * lanes * sizeof(T) + scr_bytes;
-            int64_t per_shard_h = ceil_div(ceil_div(npix, kC3Shards), lanes);
-            if (per_shard_h > 256) per_shard_h = 256;
-            if (per_shard_h < 1) per_shard_h = 1;
-            const dim3 gridh((unsigned)(per_shard_h * kC3Shards));
+            const dim3 gridh((unsigned)(shard_blocks(npix, kC3Shards, lanes, 256) * kC3Shards));
             hipError_t e = hipSuccess;
             pick_eq<16, 32>(lanes, [&](auto L) {
                 constexpr int LANES = decltype(L)::value;
@@ -1892,49 +1875,42 @@ extern "C" size_t nd_amd_omnibus_c3_workspace_bytes(int64_t ny, int64_t nx, int6
     return c3_layout(ny * nx, ny, k).total;
 }
 
+// the two entries end alike: float32 or float64 of omnibus_c3_impl
+static int omnibus_c3_run(int dtype, const void *const planes[9], int64_t ny, int64_t nx, int64_t k, int64_t sy,
+                          int64_t sx, int64_t st, uint32_t n_looks, double alpha, uint8_t *change, void *z_out,
+                          void *p_out, void *workspace, size_t workspace_bytes, void *hip_stream,
+                          const int64_t *pm_ids)
+{
+    int rc = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        rc = omnibus_c3_impl<T>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out, workspace,
+                                workspace_bytes, static_cast<hipStream_t>(hip_stream), pm_ids);
+    });
+    return rc;
+}
+
 extern "C" int nd_amd_omnibus_c3_pixel_major(const void *const planes[9], int dtype, int64_t ny, int64_t nx,
                                              int64_t k, const int64_t date_stride[9], uint32_t n_looks,
                                              double alpha, uint8_t *change, void *z_out, void *p_out,
                                              void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
-        set_error("nd_amd_omnibus_c3_pixel_major: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", dtype);
+    constexpr const char *entry = "nd_amd_omnibus_c3_pixel_major";
+    if (const int rc = check_dtype(entry, dtype)) return rc;
+    bool empty;
+    if (const int rc = check_shape(entry, ny, nx, k, &empty)) return rc;
+    if (!date_stride) {                          // (refused on an empty raster too; the strides' values are not)
+        set_error("nd_amd_omnibus_c3_pixel_major: date_stride is null");
         return ND_AMD_EINVAL;
     }
-    if (ny < 0 || nx < 0 || k < 0 || !date_stride) {
-        set_error("nd_amd_omnibus_c3_pixel_major: bad shape");
-        return ND_AMD_EINVAL;
-    }
-    if (ny == 0 || nx == 0 || k == 0) return ND_AMD_OK;
-    if (!planes || !change) {
-        set_error("nd_amd_omnibus_c3_pixel_major: null data pointer");
-        return ND_AMD_EINVAL;
-    }
-    for (int c = 0; c < 9; ++c) {
-        if (!planes[c]) {
-            set_error("nd_amd_omnibus_c3_pixel_major: plane %d is null", c);
-            return ND_AMD_EINVAL;
-        }
-        if (date_stride[c] != 1 && date_stride[c] != 2) {
-            set_error("nd_amd_omnibus_c3_pixel_major: date strides must be 1 or 2");
-            return ND_AMD_EINVAL;
-        }
-    }
-    if (n_looks == 0) {
-        set_error("nd_amd_omnibus_c3_pixel_major: n_looks must be >= 1");
-        return ND_AMD_EINVAL;
-    }
-    if (ny * nx >= 0xffffffffLL) {
-        set_error("nd_amd_omnibus_c3_pixel_major: raster exceeds the 32-bit pixel index");
-        return ND_AMD_EUNSUPPORTED;
-    }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (empty) return ND_AMD_OK;
+    if (const int rc = check_planes(entry, planes, 9, change)) return rc;
+    if (const int rc = check_date_strides(entry, date_stride, 9)) return rc;
+    if (const int rc = check_looks(entry, n_looks)) return rc;
+    if (const int rc = check_pixel_index(entry, ny, nx)) return rc;
     // unit-stride geometry of the layout: (y, x, t) -> (y * nx + x) * k + t
-    if (dtype == ND_AMD_F32)
-        return omnibus_c3_impl<float>(planes, ny, nx, k, nx * k, k, 1, n_looks, alpha, change, z_out, p_out,
-                                      workspace, workspace_bytes, stream, date_stride);
-    return omnibus_c3_impl<double>(planes, ny, nx, k, nx * k, k, 1, n_looks, alpha, change, z_out, p_out,
-                                   workspace, workspace_bytes, stream, date_stride);
+    return omnibus_c3_run(dtype, planes, ny, nx, k, nx * k, k, 1, n_looks, alpha, change, z_out, p_out, workspace,
+                          workspace_bytes, hip_stream, date_stride);
 }
 
 extern "C" int nd_amd_omnibus_c3(const void *const planes[9], int dtype, int64_t ny, int64_t nx,
@@ -1943,36 +1919,14 @@ extern "C" int nd_amd_omnibus_c3(const void *const planes[9], int dtype, int64_t
                                  void *p_out, void *workspace, size_t workspace_bytes,
                                  void *hip_stream)
 {
-    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
-        set_error("nd_amd_omnibus_c3: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", dtype);
-        return ND_AMD_EINVAL;
-    }
-    if (ny < 0 || nx < 0 || k < 0) {
-        set_error("nd_amd_omnibus_c3: negative shape");
-        return ND_AMD_EINVAL;
-    }
-    if (ny == 0 || nx == 0 || k == 0) return ND_AMD_OK;
-    if (!planes || !change) {
-        set_error("nd_amd_omnibus_c3: null data pointer");
-        return ND_AMD_EINVAL;
-    }
-    for (int c = 0; c < 9; ++c)
-        if (!planes[c]) {
-            set_error("nd_amd_omnibus_c3: plane %d is null", c);
-            return ND_AMD_EINVAL;
-        }
-    if (n_looks == 0) {
-        set_error("nd_amd_omnibus_c3: n_looks must be >= 1");
-        return ND_AMD_EINVAL;
-    }
-    if (ny * nx >= 0xffffffffLL) {
-        set_error("nd_amd_omnibus_c3: raster exceeds the 32-bit pixel index");
-        return ND_AMD_EUNSUPPORTED;
-    }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return omnibus_c3_impl<float>(planes, ny, nx, k, stride_y, stride_x, stride_t, n_looks, alpha,
-                                      change, z_out, p_out, workspace, workspace_bytes, stream);
-    return omnibus_c3_impl<double>(planes, ny, nx, k, stride_y, stride_x, stride_t, n_looks, alpha,
-                                   change, z_out, p_out, workspace, workspace_bytes, stream);
+    constexpr const char *entry = "nd_amd_omnibus_c3";
+    if (const int rc = check_dtype(entry, dtype)) return rc;
+    bool empty;
+    if (const int rc = check_shape(entry, ny, nx, k, &empty)) return rc;
+    if (empty) return ND_AMD_OK;
+    if (const int rc = check_planes(entry, planes, 9, change)) return rc;
+    if (const int rc = check_looks(entry, n_looks)) return rc;
+    if (const int rc = check_pixel_index(entry, ny, nx)) return rc;
+    return omnibus_c3_run(dtype, planes, ny, nx, k, stride_y, stride_x, stride_t, n_looks, alpha, change, z_out,
+                          p_out, workspace, workspace_bytes, hip_stream, nullptr);
 }

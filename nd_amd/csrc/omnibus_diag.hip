@@ -375,14 +375,15 @@ static int omnibus_diag_impl(const void *const planes[], int64_t ny, int64_t nx,
 
     DiagArgs<T> g;
     for (int c = 0; c < 3; ++c) g.pl[c] = static_cast<const T *>(planes[c < Q ? c : 0]);
-    const bool flat = (sx == 1) && (sy == nx);
-    g.nx = flat ? npix : nx;
-    g.nrows = flat ? 1 : ny;
+    RowWalk rw;
+    if (const int rc = row_walk("nd_amd_omnibus_diag", ny, nx, sy, sx, false, kDgThreads, &rw)) return rc;
+    g.nx = rw.nx;
+    g.nrows = rw.nrows;
     g.nx_orig = nx;
     g.sy = sy;
     g.sx = sx;
     g.st = st;
-    g.blocks_per_row = ceil_div(g.nx, kDgThreads);
+    g.blocks_per_row = rw.blocks_per_row;
     g.k = (int)k;
     g.write_tab = tab_in_args ? 1 : 0;
     g.nlooks = n_looks;
@@ -395,13 +396,8 @@ static int omnibus_diag_impl(const void *const planes[], int64_t ny, int64_t nx,
     g.tab_dev = tab_dev;
     g.flag_idx = reinterpret_cast<uint32_t *>(ws + w.off_idx);
     g.seg = w.seg;
-    const int64_t nblocks = g.blocks_per_row * g.nrows;
-    if (nblocks > 0x7fffffffLL) {                             // (only a strided raster of 2^31 rows and more)
-        set_error("nd_amd_omnibus_diag: raster too large for one launch");
-        return ND_AMD_EUNSUPPORTED;
-    }
     const bool stats = z_out != nullptr || p_out != nullptr;
-    const dim3 grid((unsigned)nblocks), block(kDgThreads);
+    const dim3 grid((unsigned)rw.nblocks()), block(kDgThreads);
 
     // (The launches are timed under the dual-pol test's timer ids -- OMNIBUS_FUSED, _GLOBAL, _SEARCH, reported as
     //  omnibus_c2_* -- as the full-pol unit does: the ids name the role of a launch in an omnibus call, and one call
@@ -427,29 +423,13 @@ static int omnibus_diag_impl(const void *const planes[], int64_t ny, int64_t nx,
         ND_HIP_CHECK(hipGetLastError());
     }
     if (k >= 2) {
-        int64_t per_shard = ceil_div(ceil_div(npix, kDgShards), 64);
-        if (per_shard > 64) per_shard = 64;
-        if (per_shard < 1) per_shard = 1;
+        const int64_t per_shard = shard_blocks(npix, kDgShards, 64, 64);
         KernelTimer timer(ND_AMD_KERNEL_OMNIBUS_SEARCH, stream);
         hipLaunchKernelGGL((omnibus_diag_search_kernel<T, Q>), dim3((unsigned)(per_shard * kDgShards)), dim3(64), 0,
                            stream, g);
         ND_HIP_CHECK(hipGetLastError());
     }
     return ND_AMD_OK;
-}
-
-template <typename T>
-static int omnibus_diag_q(int nch, const void *const planes[], int64_t ny, int64_t nx, int64_t k, int64_t sy,
-                          int64_t sx, int64_t st, double n_looks, double alpha, uint8_t *change, void *z_out,
-                          void *p_out, void *workspace, size_t workspace_bytes, hipStream_t stream)
-{
-    // (the entry point admits one to three channels)
-    int rc = ND_AMD_EINVAL;
-    pick_eq<1, 2, 3>(nch, [&](auto Q) {
-        rc = omnibus_diag_impl<T, decltype(Q)::value>(planes, ny, nx, k, sy, sx, st, n_looks, alpha, change, z_out, p_out,
-                                                      workspace, workspace_bytes, stream);
-    });
-    return rc;
 }
 
 }  // namespace nd_amd
@@ -467,40 +447,34 @@ extern "C" int nd_amd_omnibus_diag(const void *const planes[], int nch, int dtyp
                                    uint8_t *change, void *z_out, void *p_out, void *workspace, size_t workspace_bytes,
                                    void *hip_stream)
 {
-    if (dtype != ND_AMD_F32 && dtype != ND_AMD_F64) {
-        set_error("nd_amd_omnibus_diag: dtype must be ND_AMD_F32 or ND_AMD_F64, got %d", dtype);
-        return ND_AMD_EINVAL;
-    }
+    constexpr const char *entry = "nd_amd_omnibus_diag";
+    if (const int rc = check_dtype(entry, dtype)) return rc;
     if (nch < 1 || nch > 3) {
         set_error("nd_amd_omnibus_diag: one to three intensity channels, got %d", nch);
         return ND_AMD_EINVAL;
     }
-    if (ny < 0 || nx < 0 || k < 0) {
-        set_error("nd_amd_omnibus_diag: negative shape");
-        return ND_AMD_EINVAL;
-    }
+    bool empty;
+    if (const int rc = check_shape(entry, ny, nx, k, &empty)) return rc;
     if (!(n_looks > 0.0) || !(n_looks < INFINITY)) {
         set_error("nd_amd_omnibus_diag: n_looks must be positive and finite, got %g", n_looks);
         return ND_AMD_EINVAL;
     }
-    if (ny == 0 || nx == 0 || k == 0) return ND_AMD_OK;
-    if (!planes || !change) {
-        set_error("nd_amd_omnibus_diag: null data pointer");
-        return ND_AMD_EINVAL;
-    }
-    for (int c = 0; c < nch; ++c)
-        if (!planes[c]) {
-            set_error("nd_amd_omnibus_diag: plane %d is null", c);
-            return ND_AMD_EINVAL;
-        }
-    if (ny * nx >= 0xffffffffLL || k > 0x7fffffffLL / 3) {
-        set_error("nd_amd_omnibus_diag: raster exceeds the 32-bit pixel index");
+    if (empty) return ND_AMD_OK;
+    if (const int rc = check_planes(entry, planes, nch, change)) return rc;
+    if (const int rc = check_pixel_index(entry, ny, nx)) return rc;
+    if (k > 0x7fffffffLL / 3) {
+        set_error("nd_amd_omnibus_diag: k = %lld exceeds the supported number of dates", (long long)k);
         return ND_AMD_EUNSUPPORTED;
     }
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return omnibus_diag_q<float>(nch, planes, ny, nx, k, stride_y, stride_x, stride_t, n_looks, alpha, change,
-                                     z_out, p_out, workspace, workspace_bytes, stream);
-    return omnibus_diag_q<double>(nch, planes, ny, nx, k, stride_y, stride_x, stride_t, n_looks, alpha, change, z_out,
-                                  p_out, workspace, workspace_bytes, stream);
+    int rc = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        pick_eq<1, 2, 3>(nch, [&](auto Q) {
+            rc = omnibus_diag_impl<T, decltype(Q)::value>(planes, ny, nx, k, stride_y, stride_x, stride_t, n_looks,
+                                                          alpha, change, z_out, p_out, workspace, workspace_bytes,
+                                                          stream);
+        });
+    });
+    return rc;
 }

@@ -10,6 +10,7 @@
 // fully coalesced loads into LDS (pixel-major, pitch odd so that the column reads below are
 // conflict-free), then written date by date, lanes along the pixels (coalesced plane rows).
 #include "common.hpp"
+#include "dispatch.hpp"
 
 namespace nd_amd {
 
@@ -168,6 +169,19 @@ static int relayout_impl(const void *in, void *out, void *out2, int64_t npix, in
     return ND_AMD_OK;
 }
 
+// the three entries end alike: float32 or float64 of relayout_impl
+static int relayout_run(int dtype, const void *in, void *out, void *out2, int64_t npix, int64_t k, int64_t ids,
+                        int64_t out_date_stride, bool to_planar, void *hip_stream)
+{
+    int rc = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        rc = relayout_impl<T>(in, out, out2, npix, k, ids, out_date_stride, to_planar,
+                              static_cast<hipStream_t>(hip_stream));
+    });
+    return rc;
+}
+
 }  // namespace nd_amd
 
 using namespace nd_amd;
@@ -189,10 +203,7 @@ extern "C" int nd_amd_relayout_planar(const void *in, void *out, int dtype, int6
         set_error("nd_amd_relayout_planar: null data pointer");
         return ND_AMD_EINVAL;
     }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return relayout_impl<float>(in, out, nullptr, npix, k, in_date_stride, out_date_stride, true, stream);
-    return relayout_impl<double>(in, out, nullptr, npix, k, in_date_stride, out_date_stride, true, stream);
+    return relayout_run(dtype, in, out, nullptr, npix, k, in_date_stride, out_date_stride, true, hip_stream);
 }
 
 extern "C" int nd_amd_relayout_pixel_major(const void *in, void *out, int dtype, int64_t npix,
@@ -214,10 +225,7 @@ extern "C" int nd_amd_relayout_pixel_major(const void *in, void *out, int dtype,
     }
     // RelayoutArgs: `ids` is the element distance between dates on the pixel-major side and
     // `out_date_stride` the plane pitch on the planar side, whichever direction the copy runs
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return relayout_impl<float>(in, out, nullptr, npix, k, out_date_stride, in_date_stride, false, stream);
-    return relayout_impl<double>(in, out, nullptr, npix, k, out_date_stride, in_date_stride, false, stream);
+    return relayout_run(dtype, in, out, nullptr, npix, k, out_date_stride, in_date_stride, false, hip_stream);
 }
 
 extern "C" int nd_amd_relayout_planar_complex(const void *in, void *out_re, void *out_im, int dtype,
@@ -237,10 +245,7 @@ extern "C" int nd_amd_relayout_planar_complex(const void *in, void *out_re, void
         set_error("nd_amd_relayout_planar_complex: null data pointer");
         return ND_AMD_EINVAL;
     }
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return relayout_impl<float>(in, out_re, out_im, npix, k, 2, out_date_stride, true, stream);
-    return relayout_impl<double>(in, out_re, out_im, npix, k, 2, out_date_stride, true, stream);
+    return relayout_run(dtype, in, out_re, out_im, npix, k, 2, out_date_stride, true, hip_stream);
 }
 
 // ---- interleaved complex -> two real arrays of the same (contiguous) shape --------------------
@@ -310,14 +315,12 @@ extern "C" int nd_amd_split_complex(const void *in, void *out_re, void *out_im, 
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     {
         KernelTimer timer(ND_AMD_KERNEL_RELAYOUT, stream);
-        if (dtype == ND_AMD_F32)
-            hipLaunchKernelGGL((split_complex_kernel<float>), dim3((unsigned)nblocks), dim3(256), 0, stream,
-                               static_cast<const float *>(in), static_cast<float *>(out_re),
-                               static_cast<float *>(out_im), n);
-        else
-            hipLaunchKernelGGL((split_complex_kernel<double>), dim3((unsigned)nblocks), dim3(256), 0, stream,
-                               static_cast<const double *>(in), static_cast<double *>(out_re),
-                               static_cast<double *>(out_im), n);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            hipLaunchKernelGGL((split_complex_kernel<T>), dim3((unsigned)nblocks), dim3(256), 0, stream,
+                               static_cast<const T *>(in), static_cast<T *>(out_re), static_cast<T *>(out_im),
+                               n);
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;
@@ -386,14 +389,12 @@ extern "C" int nd_amd_merge_complex(const void *in_re, const void *in_im, void *
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     {
         KernelTimer timer(ND_AMD_KERNEL_RELAYOUT, stream);
-        if (dtype == ND_AMD_F32)
-            hipLaunchKernelGGL((merge_complex_kernel<float>), dim3((unsigned)nblocks), dim3(256), 0, stream,
-                               static_cast<const float *>(in_re), static_cast<const float *>(in_im),
-                               static_cast<float *>(out), n);
-        else
-            hipLaunchKernelGGL((merge_complex_kernel<double>), dim3((unsigned)nblocks), dim3(256), 0, stream,
-                               static_cast<const double *>(in_re), static_cast<const double *>(in_im),
-                               static_cast<double *>(out), n);
+        pick(dtype == ND_AMD_F64, [&](auto F64) {
+            using T = std::conditional_t<decltype(F64)::value, double, float>;
+            hipLaunchKernelGGL((merge_complex_kernel<T>), dim3((unsigned)nblocks), dim3(256), 0, stream,
+                               static_cast<const T *>(in_re), static_cast<const T *>(in_im),
+                               static_cast<T *>(out), n);
+        });
     }
     ND_HIP_CHECK(hipGetLastError());
     return ND_AMD_OK;

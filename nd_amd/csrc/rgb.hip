@@ -21,6 +21,7 @@
 //     wave that hit the same bin land in different banks instead of serialising on one address;
 //   * a block adds only its non-zero bins to the plane's global histogram (one atomic per bin and block).
 #include "common.hpp"
+#include "dispatch.hpp"
 
 using namespace nd_amd;
 
@@ -559,14 +560,11 @@ int rgb_limits_launch(const RgbPlanes &a, double pmin, double pmax, T *limits, l
     const dim3 grid((unsigned)planes, (unsigned)(n ? ceil_div(n, chunk) : 1));
     for (int d = 0; d < ps.n; d++) {
         uint32_t *hist = hist0 + (size_t)d * hist_words;
-        if (n > 0) {
-            if (d == 0)
-                hipLaunchKernelGGL((rgb_hist_kernel<T, true>), grid, dim3(RGB_HIST_THREADS), 0, stream, a, state,
-                                   hist, ps.shift[d], ps.bits[d], chunk);
-            else
-                hipLaunchKernelGGL((rgb_hist_kernel<T, false>), grid, dim3(RGB_HIST_THREADS), 0, stream, a, state,
-                                   hist, ps.shift[d], ps.bits[d], chunk);
-        }
+        if (n > 0)
+            pick(d == 0, [&](auto FIRST) {
+                hipLaunchKernelGGL((rgb_hist_kernel<T, decltype(FIRST)::value>), grid, dim3(RGB_HIST_THREADS), 0,
+                                   stream, a, state, hist, ps.shift[d], ps.bits[d], chunk);
+            });
         hipLaunchKernelGGL((rgb_select_kernel<T>), dim3((unsigned)planes), dim3(256), 0, stream, state, hist, d,
                            ps.n, ps.bits[d], pmin, pmax, limits, counts);
     }
@@ -630,11 +628,13 @@ extern "C" int nd_amd_rgb_limits(const void *const *num, const void *const *den,
         return ND_AMD_EWORKSPACE;
     }
     hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return rgb_limits_launch<float>(a, pmin, pmax, reinterpret_cast<float *>(limits),
-                                        reinterpret_cast<long long *>(counts), workspace, need, stream);
-    return rgb_limits_launch<double>(a, pmin, pmax, reinterpret_cast<double *>(limits),
-                                     reinterpret_cast<long long *>(counts), workspace, need, stream);
+    int rcl = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        rcl = rgb_limits_launch<T>(a, pmin, pmax, reinterpret_cast<T *>(limits),
+                                   reinterpret_cast<long long *>(counts), workspace, need, stream);
+    });
+    return rcl;
 }
 
 extern "C" int nd_amd_rgb_compose(const void *const *num, const void *const *den, int nchan, int dtype,
@@ -664,7 +664,10 @@ extern "C" int nd_amd_rgb_compose(const void *const *num, const void *const *den
         if (vmax && c < nchan) st.given |= 1 << (2 * c + 1);
     }
     hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-    if (dtype == ND_AMD_F32)
-        return rgb_compose_launch<float>(a, reinterpret_cast<const float *>(limits), st, mask, out, stream);
-    return rgb_compose_launch<double>(a, reinterpret_cast<const double *>(limits), st, mask, out, stream);
+    int rcl = ND_AMD_EINVAL;
+    pick(dtype == ND_AMD_F64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        rcl = rgb_compose_launch<T>(a, reinterpret_cast<const T *>(limits), st, mask, out, stream);
+    });
+    return rcl;
 }

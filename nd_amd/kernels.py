@@ -71,6 +71,23 @@ def _omnibus_outputs(ny, nx, k, dtype, dev, stats):
     return change, z, P
 
 
+def _omnibus_run(shape, dtype, dev, stats, nbytes, entry, *head):
+    """The tail the omnibus wrappers share.  On `dev`: the outputs of a (ny, nx, k) raster, a workspace of
+    `nbytes` bytes, entry(*head, change, z, P, workspace, nbytes, stream) -- every omnibus entry ends in these six
+    arguments -- and the workspace kept alive until the stream has consumed it.  nbytes = None (the wrapper's word for
+    an empty raster; a size of 0 is not: that call is made and refused): the empty outputs and no call.  Returns
+    the library's code, which the wrapper judges, and change, or (change, z, P) with stats."""
+    with torch.cuda.device(dev):
+        change, z, P = _omnibus_outputs(*shape, dtype, dev, stats)
+        rc = _lib.OK
+        if nbytes is not None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            rc = entry(*head, _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes, _stream_ptr(dev))
+            if rc == _lib.OK:
+                ws.record_stream(torch.cuda.current_stream(dev))
+    return rc, ((change, z, P) if stats else change)
+
+
 def _pixel_major_ids(planes):
     """_pixel_major_stride of every plane, or None unless all share shape, dtype and device and have one."""
     p0 = planes[0]
@@ -106,26 +123,19 @@ def change_detection(c11, c12re, c12im, c22, alpha, n=1, dims=('time', 'y', 'x')
     ny, nx, k, sy, sx, st = _yxt(dims, c11)
     dev = c11.device
     L = _lib.lib()
-    with torch.cuda.device(dev):
-        change, z, P = _omnibus_outputs(ny, nx, k, c11.dtype, dev, stats)
-        if ny * nx * k > 0:
-            min_bytes = C.c_size_t(0)
-            nbytes = L.nd_amd_omnibus_c2_workspace_bytes(_DT[c11.dtype], ny, nx, k,
-                                                         C.byref(min_bytes))
-            if workspace == 'minimal':
-                nbytes = min_bytes.value
-            elif workspace != 'recommended':
-                raise ValueError("workspace must be 'recommended' or 'minimal'")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.nd_amd_omnibus_c2(
-                _ptr(c11), _ptr(c12re), _ptr(c12im), _ptr(c22), _DT[c11.dtype],
-                ny, nx, k, sy, sx, st, int(n), float(alpha),
-                _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes, _stream_ptr(dev)))
-            # keep the workspace alive until the stream has consumed it
-            ws.record_stream(torch.cuda.current_stream(dev))
-    if stats:
-        return change, z, P
-    return change
+    nbytes = None
+    if ny * nx * k > 0:                     # (an empty raster: empty outputs, no call)
+        min_bytes = C.c_size_t(0)
+        nbytes = L.nd_amd_omnibus_c2_workspace_bytes(_DT[c11.dtype], ny, nx, k, C.byref(min_bytes))
+        if workspace == 'minimal':
+            nbytes = min_bytes.value
+        elif workspace != 'recommended':
+            raise ValueError("workspace must be 'recommended' or 'minimal'")
+    rc, out = _omnibus_run((ny, nx, k), c11.dtype, dev, stats, nbytes, L.nd_amd_omnibus_c2,
+                           _ptr(c11), _ptr(c12re), _ptr(c12im), _ptr(c22), _DT[c11.dtype], ny, nx, k, sy, sx, st,
+                           int(n), float(alpha))
+    _lib.check(rc)
+    return out
 
 
 def change_detection_multilooked(c11, c12re, c12im, c22, alpha, ml, stats=False):
@@ -193,19 +203,13 @@ def change_detection_pixel_major(c11, c12re, c12im, c22, alpha, n=1, stats=False
         return None
     dev = c11.device
     L = _lib.lib()
-    with torch.cuda.device(dev):
-        change, z, P = _omnibus_outputs(ny, nx, k, dt, dev, stats)
-        nbytes = L.nd_amd_omnibus_c2_workspace_bytes(_DT[dt], ny, nx, k, None)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        rc = L.nd_amd_omnibus_c2_pixel_major(
-            _ptr(c11), _ptr(c12re), _ptr(c12im), _ptr(c22), _DT[dt], ny, nx, k,
-            _lib.i64_array(ids), int(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
-            _stream_ptr(dev))
-        if long_series and rc == _lib.EUNSUPPORTED:
-            return None                   # the caller transposes and takes the planar path
-        _lib.check(rc)
-        ws.record_stream(torch.cuda.current_stream(dev))
-    return (change, z, P) if stats else change
+    rc, out = _omnibus_run((ny, nx, k), dt, dev, stats, L.nd_amd_omnibus_c2_workspace_bytes(_DT[dt], ny, nx, k, None),
+                           L.nd_amd_omnibus_c2_pixel_major, _ptr(c11), _ptr(c12re), _ptr(c12im), _ptr(c22), _DT[dt],
+                           ny, nx, k, _lib.i64_array(ids), int(n), float(alpha))
+    if long_series and rc == _lib.EUNSUPPORTED:
+        return None                   # the caller transposes and takes the planar path
+    _lib.check(rc)
+    return out
 
 
 def change_detection_c3(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=False):
@@ -219,19 +223,13 @@ def change_detection_c3(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=False
     ny, nx, k, sy, sx, st = _yxt(dims, p0)
     dev = p0.device
     L = _lib.lib()
-    with torch.cuda.device(dev):
-        change, z, P = _omnibus_outputs(ny, nx, k, p0.dtype, dev, stats)
-        if ny * nx * k > 0:
-            nbytes = L.nd_amd_omnibus_c3_workspace_bytes(ny, nx, k)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            ptrs = (C.c_void_p * 9)(*[t.data_ptr() for t in planes])
-            _lib.check(L.nd_amd_omnibus_c3(
-                ptrs, _DT[p0.dtype], ny, nx, k, sy, sx, st, int(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
-                _stream_ptr(dev)))
-            ws.record_stream(torch.cuda.current_stream(dev))
-    if stats:
-        return change, z, P
-    return change
+    # (an empty raster: empty outputs, no call)
+    nbytes = L.nd_amd_omnibus_c3_workspace_bytes(ny, nx, k) if ny * nx * k > 0 else None
+    ptrs = (C.c_void_p * 9)(*[t.data_ptr() for t in planes])
+    rc, out = _omnibus_run((ny, nx, k), p0.dtype, dev, stats, nbytes, L.nd_amd_omnibus_c3,
+                           ptrs, _DT[p0.dtype], ny, nx, k, sy, sx, st, int(n), float(alpha))
+    _lib.check(rc)
+    return out
 
 
 def change_detection_diag(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=False):
@@ -246,19 +244,13 @@ def change_detection_diag(planes, alpha, n=1, dims=('time', 'y', 'x'), stats=Fal
     ny, nx, k, sy, sx, st = _yxt(dims, p0)
     dev = p0.device
     L = _lib.lib()
-    with torch.cuda.device(dev):
-        change, z, P = _omnibus_outputs(ny, nx, k, p0.dtype, dev, stats)
-        if ny * nx * k > 0:
-            nbytes = L.nd_amd_omnibus_diag_workspace_bytes(_DT[p0.dtype], len(planes), ny, nx, k)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            ptrs = (C.c_void_p * len(planes))(*[t.data_ptr() for t in planes])
-            _lib.check(L.nd_amd_omnibus_diag(
-                ptrs, len(planes), _DT[p0.dtype], ny, nx, k, sy, sx, st, float(n), float(alpha), _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes,
-                _stream_ptr(dev)))
-            ws.record_stream(torch.cuda.current_stream(dev))
-    if stats:
-        return change, z, P
-    return change
+    # (an empty raster: empty outputs, no call)
+    nbytes = L.nd_amd_omnibus_diag_workspace_bytes(_DT[p0.dtype], len(planes), ny, nx, k) if ny * nx * k > 0 else None
+    ptrs = (C.c_void_p * len(planes))(*[t.data_ptr() for t in planes])
+    rc, out = _omnibus_run((ny, nx, k), p0.dtype, dev, stats, nbytes, L.nd_amd_omnibus_diag,
+                           ptrs, len(planes), _DT[p0.dtype], ny, nx, k, sy, sx, st, float(n), float(alpha))
+    _lib.check(rc)
+    return out
 
 
 _STRUCTURES = {'diag': (_lib.STRUCT_DIAG, (1, 2, 3)), 'c2': (_lib.STRUCT_C2, (4,)), 'c3': (_lib.STRUCT_C3, (9,))}
@@ -343,18 +335,14 @@ def change_detection_c3_pixel_major(planes, alpha, n=1, stats=False):
         return None
     dev = p0.device
     L = _lib.lib()
-    with torch.cuda.device(dev):
-        change, z, P = _omnibus_outputs(ny, nx, k, dt, dev, stats)
-        nbytes = L.nd_amd_omnibus_c3_workspace_bytes(ny, nx, k)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ptrs = (C.c_void_p * 9)(*[t.data_ptr() for t in planes])
-        rc = L.nd_amd_omnibus_c3_pixel_major(ptrs, _DT[dt], ny, nx, k, _lib.i64_array(ids), int(n), float(alpha),
-                                             _ptr(change), _ptr(z), _ptr(P), _ptr(ws), nbytes, _stream_ptr(dev))
-        if rc == _lib.EUNSUPPORTED:
-            return None
-        _lib.check(rc)
-        ws.record_stream(torch.cuda.current_stream(dev))
-    return (change, z, P) if stats else change
+    ptrs = (C.c_void_p * 9)(*[t.data_ptr() for t in planes])
+    rc, out = _omnibus_run((ny, nx, k), dt, dev, stats, L.nd_amd_omnibus_c3_workspace_bytes(ny, nx, k),
+                           L.nd_amd_omnibus_c3_pixel_major, ptrs, _DT[dt], ny, nx, k, _lib.i64_array(ids), int(n),
+                           float(alpha))
+    if rc == _lib.EUNSUPPORTED:
+        return None
+    _lib.check(rc)
+    return out
 
 
 # ---------------------------------------------------------------------------

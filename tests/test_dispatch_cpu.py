@@ -23,3 +23,20 @@ def test_dispatch_helpers(tmp_path, sanitize):
     assert [ln for ln in run.stdout.splitlines() if ln.startswith('ok ')] == ['ok pick_le', 'ok pick_eq', 'ok pick',
                                                                                'ok nested']
     assert 'FAILED' not in run.stdout
+
+
+@pytest.mark.parametrize('sanitize', [False, True], ids=['plain', 'asan_ubsan'])
+def test_grid_helpers(tmp_path, sanitize):
+    """shard_blocks and row_walk / row_blocks (nd_amd/csrc/entry_args.hpp) against the clamp and the row walk the
+    launch sites used to write out (tools/check_entry_args.cpp): every (shards, entries per block, cap) of the
+    library on both sides of every step up to 2^32 - 2 listed pixels; flat, strided and forced-flat rasters and
+    the shapes around 2^31 - 1 blocks.  A stand-alone host program, as above."""
+    exe = str(tmp_path / 'check_entry_args')
+    flags = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-g'] if sanitize else []
+    subprocess.check_call([_clangxx(), '-std=c++17', '-O1', '-Wall', '-Werror'] + flags +
+                          [os.path.join(ROOT, 'tools', 'check_entry_args.cpp'), '-o', exe])
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    print(run.stdout)
+    assert run.returncode == 0, run.stdout
+    assert [ln for ln in run.stdout.splitlines() if ln.startswith('ok ')] == ['ok shard_blocks', 'ok row_walk']
+    assert 'FAILED' not in run.stdout

@@ -56,6 +56,190 @@ def test_argument_validation_without_gpu():
     assert rec >= mn.value > 4096 * 4096 * 4
 
 
+def _entry_code_cases():
+    """(id, entry, overrides, expected code, message prefix) for the seven change-detection entries.  Every case
+    returns before the first HIP call: refused arguments and check_workspace come first, so the non-null addresses
+    (DUMMY) are never dereferenced.  The cases with two faults pin the ORDER of the checks."""
+    from nd_amd import _lib
+    OK, EINVAL, EWS, EUNS = _lib.OK, _lib.EINVAL, _lib.EWORKSPACE, _lib.EUNSUPPORTED
+    nan, inf = float('nan'), float('inf')
+    big = 65536                                       # 65536 x 65536 pixels: one past the 32-bit pixel index
+    cases = []
+
+    def add(entry, name, expect, impl=None, **over):
+        # impl: refused one level down, in the family's *_impl, whose name then begins the message -- the workspace
+        # always is (check_workspace), the full-pol date limit too
+        impl = expect == EWS if impl is None else impl
+        prefix = _ENTRY_NAMES[_IMPL_OF.get(entry, entry) if impl else entry]
+        cases.append(('%s-%s' % (entry, name), entry, over, expect, prefix))
+
+    def common(entry, nplanes, dims_ok=OK):
+        add(entry, 'bad_dtype', EINVAL, dtype=7)
+        add(entry, 'bad_dtype_empty', EINVAL, dtype=7, ny=0, null=True)
+        for d in ('ny', 'nx', 'k'):
+            add(entry, 'negative_' + d, EINVAL, **{d: -1})
+            add(entry, 'zero_%s_all_null' % d, dims_ok, **{d: 0, 'null': True})
+        add(entry, 'zero_ny_negative_nx', EINVAL, ny=0, nx=-1, null=True)
+        for p in range(nplanes):
+            add(entry, 'plane%d_null' % p, EINVAL, null_planes=(p,))
+        add(entry, 'change_null', EINVAL, change=None)
+
+    for entry in ('c2', 'c2_pm', 'c3', 'c3_pm'):
+        common(entry, 4 if entry.startswith('c2') else 9)
+        add(entry, 'no_looks', EINVAL, n_looks=0)
+        add(entry, 'no_looks_empty', OK, n_looks=0, nx=0, null=True)
+        add(entry, 'no_looks_too_many_pixels', EINVAL, n_looks=0, ny=big, nx=big)
+        add(entry, 'plane_null_too_many_pixels', EINVAL, null_planes=(1,), ny=big, nx=big)
+        add(entry, 'too_many_pixels', EUNS, ny=big, nx=big)
+        add(entry, 'most_pixels_no_workspace', EWS, ny=big, nx=big - 1)     # 2^32 - 65536 pixels: admitted
+        add(entry, 'no_workspace', EWS)
+        add(entry, 'short_workspace', EWS, workspace=DUMMY, workspace_bytes=256)
+        add(entry, 'misaligned_workspace', EINVAL, impl=True, workspace=DUMMY + 16, workspace_bytes=1 << 40)
+    add('c2', 'too_many_dates', EUNS, k=0x40000000)
+    add('c2', 'most_dates_no_workspace', EWS, k=4096)
+    add('c2_pm', 'too_many_dates', EUNS, k=193)
+    add('c2_pm', 'most_dates_no_workspace', EWS, k=192)
+    for entry in ('c3', 'c3_pm'):
+        add(entry, 'planes_null', EINVAL, planes=None)
+        add(entry, 'too_many_dates', EUNS, impl=True, k=97, workspace=DUMMY, workspace_bytes=1 << 40)
+        add(entry, 'too_many_dates_no_workspace', EWS, k=97)
+    for entry, n in (('c2_pm', 4), ('c3_pm', 9)):
+        add(entry, 'date_stride_null', EINVAL, date_stride=None)
+        add(entry, 'date_stride_null_empty', EINVAL, date_stride=None, nx=0, null=True)
+        for v in range(n):
+            add(entry, 'date_stride%d_3' % v, EINVAL, date_stride=[3 if i == v else 1 for i in range(n)])
+        add(entry, 'date_stride_0', EINVAL, date_stride=[0] * n)
+        add(entry, 'date_stride_2', EWS, date_stride=[2] * n)
+        add(entry, 'date_stride_3_too_many_pixels', EINVAL, date_stride=[3] * n, ny=big, nx=big)
+    add('c2_pm', 'date_stride_3_empty', EINVAL, date_stride=[3, 3, 3, 3], nx=0, null=True)
+    add('c3_pm', 'date_stride_3_empty', OK, date_stride=[3] * 9, nx=0, null=True)
+    add('c2_pm', 'c12_halves_differ', EINVAL, date_stride=[1, 1, 2, 1])
+    add('c2_pm', 'c12_halves_differ_empty', EINVAL, date_stride=[1, 2, 1, 1], k=0, null=True)
+    add('c2_pm', 'c12_interleaved', EWS, date_stride=[1, 2, 2, 1])
+
+    # the fused-multilook entry: the window where the others have the looks
+    common('c2_ml', 4)
+    add('c2_ml', 'no_window', EINVAL, ml=0)
+    add('c2_ml', 'no_window_empty', EINVAL, ml=0, nx=0, null=True)
+    add('c2_ml', 'even_window_empty', OK, ml=4, nx=0, null=True)
+    add('c2_ml', 'even_window', EUNS, ml=4)
+    add('c2_ml', 'plane_null_even_window', EINVAL, ml=4, null_planes=(2,))
+    add('c2_ml', 'float64', EUNS, dtype=_lib.F64)
+    add('c2_ml', 'one_date', EUNS, k=1)
+    add('c2_ml', 'too_many_dates', EUNS, k=25)
+    add('c2_ml', 'most_dates_no_workspace', EWS, k=24, stride_t=64)
+    add('c2_ml', 'strided_x', EUNS, stride_x=2)
+    add('c2_ml', 'narrower_than_the_window', EUNS, ml=5, nx=4)
+    add('c2_ml', 'too_many_pixels', EUNS, ny=big, nx=big)
+    add('c2_ml', 'no_workspace', EWS)
+
+    # intensities only: a channel count, and real-valued looks that are checked BEFORE the empty raster
+    common('diag', 3)
+    for nch in (0, 4):
+        add('diag', 'nch_%d' % nch, EINVAL, nch=nch)
+        add('diag', 'nch_%d_empty' % nch, EINVAL, nch=nch, ny=0, null=True)
+    for nch in (1, 2):
+        add('diag', 'nch_%d_plane_behind_null' % nch, EWS, nch=nch, null_planes=(nch,))
+        add('diag', 'nch_%d_last_plane_null' % nch, EINVAL, nch=nch, null_planes=(nch - 1,))
+    add('diag', 'planes_null', EINVAL, planes=None)
+    for name, v in (('0', 0.0), ('minus_1', -1.0), ('inf', inf), ('nan', nan)):
+        add('diag', 'looks_' + name, EINVAL, n_looks=v)
+        add('diag', 'looks_%s_empty' % name, EINVAL, n_looks=v, nx=0, null=True)
+    add('diag', 'looks_fractional', EWS, n_looks=4.4)
+    add('diag', 'too_many_pixels', EUNS, ny=big, nx=big)
+    add('diag', 'plane_null_too_many_pixels', EINVAL, null_planes=(0,), ny=big, nx=big)
+    add('diag', 'too_many_dates', EUNS, k=0x7fffffff // 3 + 1)
+    add('diag', 'no_workspace', EWS)
+    add('diag', 'misaligned_workspace', EINVAL, impl=True, workspace=DUMMY + 16, workspace_bytes=1 << 40)
+
+    # change_segments has no workspace and no pixel limit: valid arguments would launch, so none are given
+    common('cs', 4)
+    add('cs', 'bad_structure', EINVAL, structure=3)
+    add('cs', 'bad_structure_empty', EINVAL, structure=-1, ny=0, null=True)
+    for structure, nplanes in ((_lib.STRUCT_DIAG, 0), (_lib.STRUCT_DIAG, 4), (_lib.STRUCT_C2, 3), (_lib.STRUCT_C2, 9),
+                               (_lib.STRUCT_C3, 4)):
+        add('cs', 'structure_%d_with_%d_planes' % (structure, nplanes), EINVAL, structure=structure, nplanes=nplanes)
+        add('cs', 'structure_%d_with_%d_planes_empty' % (structure, nplanes), EINVAL, structure=structure,
+            nplanes=nplanes, k=0, null=True)
+    add('cs', 'no_output', EINVAL, direction=None, means=None)
+    add('cs', 'no_output_empty', EINVAL, direction=None, means=None, nx=0, null=True, keep_outputs=True)
+    add('cs', 'direction_only_empty', OK, means=None, nx=0, null=True, keep_outputs=True)
+    add('cs', 'means_only_empty', OK, direction=None, k=0, null=True, keep_outputs=True)
+    add('cs', 'planes_null', EINVAL, planes=None)
+    for p in range(4):
+        add('cs', 'means_plane%d_null' % p, EINVAL, null_means=(p,))
+    for p in range(9):
+        add('cs', 'c3_plane%d_null' % p, EINVAL, structure=_lib.STRUCT_C3, nplanes=9, null_planes=(p,))
+    add('cs', 'diag_last_plane_null', EINVAL, structure=_lib.STRUCT_DIAG, nplanes=2, null_planes=(1,), means=None)
+    return cases
+
+
+DUMMY = 0x10000      # a non-null, 256-byte aligned address that is never dereferenced
+_ENTRY_NAMES = {'c2': b'nd_amd_omnibus_c2:', 'c2_ml': b'nd_amd_omnibus_c2_ml:', 'c2_pm': b'nd_amd_omnibus_c2_pixel_major:',
+                'c3': b'nd_amd_omnibus_c3:', 'c3_pm': b'nd_amd_omnibus_c3_pixel_major:', 'diag': b'nd_amd_omnibus_diag:',
+                'cs': b'nd_amd_change_segments:'}
+_IMPL_OF = {'c2_ml': 'c2', 'c2_pm': 'c2', 'c3_pm': 'c3'}      # the entry whose *_impl serves it
+
+
+def _call_entry(L, entry, over):
+    """calls one entry with valid arguments for a tiny raster (null workspace), changed by `over`"""
+    from nd_amd import _lib
+    vp = ctypes.c_void_p
+    a = dict(dtype=_lib.F32, ny=8, nx=8, k=4, stride_y=8, stride_x=1, stride_t=64, n_looks=4, ml=3, alpha=0.5,
+             change=DUMMY, z_out=None, p_out=None, workspace=None, workspace_bytes=0, nch=3, structure=_lib.STRUCT_C2,
+             nplanes=4, direction=DUMMY)
+    nplanes = {'c2': 4, 'c2_ml': 4, 'c2_pm': 4, 'c3': 9, 'c3_pm': 9, 'diag': 3, 'cs': over.get('nplanes', 4)}[entry]
+    addr = [None if (p in over.get('null_planes', ()) or over.get('null')) else DUMMY + 4096 * p for p in range(9)]
+    a['planes'] = (vp * 9)(*addr)
+    a['means'] = (vp * 9)(*[None if p in over.get('null_means', ()) else DUMMY for p in range(9)])
+    a['date_stride'] = [1] * nplanes
+    if over.get('null'):                              # an empty raster is admitted with every pointer null
+        a.update(planes=None, change=None)
+        if entry == 'cs' and not over.get('keep_outputs'):
+            a.update(means=None)                      # (direction stays: one output must be asked for)
+    a.update({k: v for k, v in over.items() if k not in ('null', 'null_planes', 'null_means', 'keep_outputs')})
+    ds = None if a['date_stride'] is None else _lib.i64_array(a['date_stride'])
+    c2 = [addr[p] if a['planes'] is not None else None for p in range(4)]
+    dims = [a['ny'], a['nx'], a['k']]
+    strides = [a['stride_y'], a['stride_x'], a['stride_t']]
+    tail = [a['alpha'], a['change'], a['z_out'], a['p_out'], a['workspace'], a['workspace_bytes'], None]
+    if entry == 'c2':
+        return L.nd_amd_omnibus_c2(*c2, a['dtype'], *dims, *strides, a['n_looks'], *tail)
+    if entry == 'c2_ml':
+        return L.nd_amd_omnibus_c2_ml(*c2, a['dtype'], *dims, *strides, a['ml'], *tail)
+    if entry == 'c2_pm':
+        return L.nd_amd_omnibus_c2_pixel_major(*c2, a['dtype'], *dims, ds, a['n_looks'], *tail)
+    if entry == 'c3':
+        return L.nd_amd_omnibus_c3(a['planes'], a['dtype'], *dims, *strides, a['n_looks'], *tail)
+    if entry == 'c3_pm':
+        return L.nd_amd_omnibus_c3_pixel_major(a['planes'], a['dtype'], *dims, ds, a['n_looks'], *tail)
+    if entry == 'diag':
+        return L.nd_amd_omnibus_diag(a['planes'], a['nch'], a['dtype'], *dims, *strides, float(a['n_looks']), *tail)
+    assert entry == 'cs'
+    return L.nd_amd_change_segments(a['planes'], a['nplanes'], a['structure'], a['dtype'], *dims, *strides, a['change'],
+                                    a['direction'], a['means'], None)
+
+
+def test_entry_return_codes_without_gpu():
+    """The return code of every refusal of the seven change-detection entries, and of the empty raster, as a table
+    (_entry_code_cases); a refusal also leaves a message that begins with the entry's name."""
+    from nd_amd import _lib
+    L = _lib.lib()
+    cases = _entry_code_cases()
+    assert len(set(c[0] for c in cases)) == len(cases)
+    wrong = []
+    for cid, entry, over, expect, prefix in cases:
+        rc = _call_entry(L, entry, over)
+        msg = L.nd_amd_last_error()
+        if rc != expect:
+            wrong.append('%s: %d, expected %d (%s)' % (cid, rc, expect, msg.decode()))
+        elif rc != _lib.OK and not msg.startswith(prefix):
+            wrong.append('%s: message %r does not begin with %r' % (cid, msg, prefix))
+        elif 'dtype' in cid and b'dtype' not in msg:
+            wrong.append('%s: message %r does not name the dtype' % (cid, msg))
+    assert not wrong, '\n'.join(wrong)
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from nd_amd import kernels

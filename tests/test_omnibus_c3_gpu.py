@@ -263,3 +263,33 @@ def test_c3_sparse_regime_degenerate_values(oracle, device, k):
         torch.cuda.synchronize()
         assert int((got.cpu().numpy() != want).sum()) == 0, (k, alpha)
         assert want.sum() > 0
+
+
+@pytest.mark.parametrize('alpha', [0.01, 0.99])
+@pytest.mark.parametrize('shape', [(4, 1, 1), (6, 1, 3), (8, 5, 7)], ids=lambda s: 'k%d_%dx%d' % s)
+def test_c3_smallest_rasters_flat_and_cropped(oracle, device, shape, alpha):
+    """1 x 1 and 1 x 3 pixels: the blocks per shard of every search sit on their lower bound of one; 5 x 7 pixels;
+    each contiguous (one flat row) and as a crop of a wider buffer (row by row).  alpha = 0.01: the streaming search
+    and what runs behind it; 0.99: the sparse regime, float32 without the rasters through the time-split pass A and
+    its dump.  _run asks with and without the z / P rasters."""
+    import torch
+    from nd_amd import kernels
+    k, ny, nx = shape
+    planes = synth.omnibus_stack_c3(seed=300 + nx, k=k, ny=ny, nx=nx, dtype=np.float32, change_frac=0.5)
+    yxt = [np.ascontiguousarray(np.moveaxis(p, 0, -1)) for p in planes]
+    want, z0, P0 = oracle.change_detection_pol(yxt, 3, alpha, 9, njobs=4, stats=True)
+    ch, z, P = _run(planes, alpha, 9, device)
+    np.testing.assert_array_equal(ch, want)
+    np.testing.assert_allclose(z, z0, rtol=1e-5, equal_nan=True)
+    np.testing.assert_allclose(P, P0, rtol=1e-5, atol=1e-30, equal_nan=True)
+    views = []
+    for p in planes:
+        wide = torch.zeros((k, ny + 4, nx + 9), dtype=torch.float32, device=device)
+        wide[:, 2:2 + ny, 3:3 + nx] = torch.from_numpy(p).to(device)
+        views.append(wide[:, 2:2 + ny, 3:3 + nx])
+    assert views[0].stride(1) != nx
+    np.testing.assert_array_equal(kernels.change_detection_c3(views, alpha=alpha, n=9).cpu().numpy(), want)
+    ch, z, P = kernels.change_detection_c3(views, alpha=alpha, n=9, stats=True)
+    np.testing.assert_array_equal(ch.cpu().numpy(), want)
+    np.testing.assert_allclose(z.cpu().numpy(), z0, rtol=1e-5, equal_nan=True)
+    np.testing.assert_allclose(P.cpu().numpy(), P0, rtol=1e-5, atol=1e-30, equal_nan=True)

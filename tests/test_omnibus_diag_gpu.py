@@ -133,6 +133,32 @@ def test_arbitrary_strides(golden, device):
             np.testing.assert_array_equal(got.cpu().numpy(), want)
 
 
+@pytest.mark.parametrize('alpha', [0.01, 0.99])
+@pytest.mark.parametrize('shape', [(6, 1, 1), (6, 1, 3), (8, 5, 7)], ids=lambda s: 'k%d_%dx%d' % s)
+def test_smallest_rasters_flat_and_cropped(device, shape, alpha):
+    """1 x 1 and 1 x 3 pixels: the blocks per shard of pass B sit on their lower bound of one; 5 x 7 pixels; each
+    contiguous (one flat row) and as a crop of a wider buffer (row by row).  alpha = 0.01: the one-launch form;
+    0.99: pass A and pass B.  Against the restatement computed here, by the file's rule (C.compare)."""
+    import torch
+    from nd_amd import kernels
+    from tests import omnibus_diag_ref as R
+    k, ny, nx = shape
+    planes = C.gamma_stack(40 + nx, 2, k, ny, nx, 4.4, 'float32')
+    S = R.Series(planes, (1, 1), 4.4)
+    want, z0, P0 = R.change_detection(planes, (1, 1), alpha, 4.4, series=S)
+    ch, z, P = _run(planes, alpha, 4.4, device)
+    C.compare(ch, z, P, want, z0, P0, S.closest, alpha, 'float32')
+    views = []
+    for p in planes:
+        wide = torch.zeros((k, ny + 4, nx + 9), dtype=torch.float32, device=device)
+        wide[:, 2:2 + ny, 3:3 + nx] = torch.from_numpy(p).to(device)
+        views.append(wide[:, 2:2 + ny, 3:3 + nx])
+    assert views[0].stride(1) != nx
+    ch, z, P = kernels.change_detection_diag(views, alpha=alpha, n=4.4, stats=True)
+    C.compare(ch.cpu().numpy(), z.cpu().numpy(), P.cpu().numpy(), want, z0, P0, S.closest, alpha, 'float32')
+    assert torch.equal(kernels.change_detection_diag(views, alpha=alpha, n=4.4), ch)
+
+
 def test_public_interface(golden, device):
     """OmnibusTest(pol='diag') on xr_lite datasets: host and device data, both layouts, named channels and the
     C11 / C22 default with a C12 present and ignored; omnibus_statistics; omnibus()."""

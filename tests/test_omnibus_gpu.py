@@ -378,3 +378,35 @@ def test_pass_b_one_lane_per_segment_start(oracle, device, dtype, k, alpha):
     # their determinants underflows, z is infinite and the reference reports no change)
     assert want[7, 10:50].any() and want[11, 10:50].any() and (k > 32 or want[3, 5:45].any())
     assert not want[22, 44].any()
+
+
+def _crop_of_a_wider_buffer(planes_np, device):
+    """the planes as views into buffers with a margin on every side: stride_y != nx, rows are walked one by one"""
+    import torch
+    views = []
+    for p in planes_np:
+        k, ny, nx = p.shape
+        wide = torch.zeros((k, ny + 4, nx + 9), dtype=torch.from_numpy(p).dtype, device=device)
+        wide[:, 2:2 + ny, 3:3 + nx] = torch.from_numpy(p).to(device)
+        views.append(wide[:, 2:2 + ny, 3:3 + nx])
+    return views
+
+
+@pytest.mark.parametrize('alpha', [0.01, 0.99])
+@pytest.mark.parametrize('shape', [(6, 1, 1), (6, 1, 3), (8, 5, 7)], ids=lambda s: 'k%d_%dx%d' % s)
+def test_smallest_rasters_flat_and_cropped(oracle, device, shape, alpha):
+    """1 x 1 and 1 x 3 pixels: a candidate list of one entry per shard at the most, where the number of blocks
+    that walk it sits on its lower bound of one (none would be a failed launch); 5 x 7 pixels; each as a contiguous
+    stack (walked as one flat row) and as a crop of a wider buffer (walked row by row).  alpha = 0.01 launches the
+    searches behind the fused pass, 0.99 those of the sparse regime; with and without the z / P rasters."""
+    from nd_amd import kernels
+    k, ny, nx = shape
+    planes = synth.omnibus_stack(seed=900 + nx, k=k, ny=ny, nx=nx, dtype=np.float32, change_frac=0.5)
+    want = _run_oracle(oracle, planes, alpha, 9)
+    _compare(_run_gpu(planes, alpha, 9, device), want)
+    views = _crop_of_a_wider_buffer(planes, device)
+    assert views[0].stride(1) != nx
+    ch, z, P = kernels.change_detection(*views, alpha=alpha, n=9, stats=True)
+    _compare((ch.cpu().numpy(), z.cpu().numpy(), P.cpu().numpy()), want)
+    for ts in (views, [v.contiguous() for v in views]):
+        np.testing.assert_array_equal(kernels.change_detection(*ts, alpha=alpha, n=9).cpu().numpy(), want[0])
