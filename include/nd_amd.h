@@ -44,6 +44,7 @@ extern "C" {
 #define ND_AMD_EHIP         -3   /* a HIP runtime call failed */
 #define ND_AMD_ENOSOLUTION  -4   /* nlmeans: find_weight has no solution (ValueError in the reference) */
 #define ND_AMD_EUNSUPPORTED -5   /* valid request this build does not cover */
+#define ND_AMD_EINTERNAL    -6   /* a bounded loop of the region kernels reached its bound: a bug, never the input */
 
 /* scipy.ndimage border modes accepted by nd_amd_correlate (nd/filters.py:226
  * forwards **kwargs to scipy.ndimage.convolve; default 'reflect') */
@@ -83,6 +84,7 @@ extern "C" {
 #define ND_AMD_KERNEL_RASTERIZE       27  /* nd_amd_rasterize_polygons, the whole call (clear, fill, resolve) */
 #define ND_AMD_KERNEL_RESAMPLE        28  /* nd_amd_resample and nd_amd_resample_nearest */
 #define ND_AMD_KERNEL_SPECKLE         29  /* nd_amd_speckle_lee and nd_amd_speckle_multitemporal, the whole call */
+#define ND_AMD_KERNEL_REGIONS         30  /* nd_amd_label_regions, nd_amd_region_sizes, nd_amd_sieve_regions, the whole call */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -107,6 +109,9 @@ extern "C" {
 
 /* nd_amd_rasterize_polygons: type of `values`, `fill` and `out` (8-byte elements, copied bit for bit) */
 #define ND_AMD_I64 2
+/* the region entries: maps of 1-byte (uint8, and bool as 0 / 1) and int32 elements besides the three above */
+#define ND_AMD_U8  3
+#define ND_AMD_I32 4
 /* crossings of one (polygon, row) a wave keeps in its LDS list; rows with more take the per-pixel walk */
 #define ND_AMD_RASTERIZE_MAX_CROSSINGS 256
 /* nd_amd_resample: the longest run of taps an axis table may hold */
@@ -1112,6 +1117,87 @@ int nd_amd_speckle_multitemporal(const void *const *src, void *const *dst, int n
                                  int dtype, int64_t k, int64_t ny, int64_t nx,
                                  const int64_t *src_strides, const int64_t *dst_strides,
                                  int w, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* ----------------------------------------------------------------------
+ * Regions of a map: connected-component labelling, region sizes and the
+ * sieve (minimum mapping unit) of boolean, class and label maps.  The
+ * reference has no counterpart.  The result is pinned by scipy itself:
+ * scipy.ndimage.label numbers regions in raster order of their first pixel,
+ * which makes the labels a pure function of the input, so the device result
+ * equals scipy's everywhere.  tests/regions_ref.py restates the by_value form.
+ *
+ * A plane v has ny x nx elements of type T: ND_AMD_U8 (bool as 0 / 1),
+ * ND_AMD_I32, ND_AMD_I64, ND_AMD_F32 or ND_AMD_F64.
+ *
+ *   Foreground.  A pixel is foreground iff v != background and v == v: NaN is
+ *       always background.  `background` is one host element of type T.
+ *   Joined.  Two foreground pixels are joined iff they are neighbours and
+ *       (by_value is 0 or their values compare ==).  connectivity 4:
+ *       neighbours share an edge; 8: an edge or a corner.  -0.0 == 0.0 holds;
+ *       int64 values are compared as int64, never through a double.
+ *   Region.  A class of the transitive closure of "joined".
+ *   labels[i, j] (int32) is 0 on background, else 1 + the rank of the pixel's
+ *       region, regions ranked by the raster index i * nx + j of their first
+ *       pixel.  counts[plane] (int64) is the number of regions of the plane.
+ *       With by_value 0 this is scipy.ndimage.label(v != background,
+ *       structure), structure = generate_binary_structure(2, 1) for 4 and
+ *       ones((3, 3)) for 8.
+ *   area[i, j] (int32) is the pixel count of the pixel's region, 0 on
+ *       background; sizes[l - 1] is the pixel count of region l.
+ *   sieve: out = v where the pixel is background (NaN bits kept) or
+ *       area >= min_size, elsewhere out = fill (one host element of type T).
+ *       min_size <= 1 is a copy.
+ *   Batches.  Every plane is labelled on its own and labels restart at 1 per
+ *       plane; no link is ever made between planes.
+ *
+ * nd_amd_label_regions writes labels, area (may be NULL) and counts (device,
+ * nplanes) from one labelling.  nd_amd_region_sizes writes sizes[offsets[p] +
+ * l - 1] = pixels of label l of plane p from a labelling (integer counts; it
+ * does not label again): offsets is a device array of nplanes int64, the
+ * exclusive prefix sums of counts; sizes has nsizes elements and is zeroed
+ * first; a label outside its plane's range is counted nowhere.
+ * nd_amd_sieve_regions writes the sieved planes without materialising labels.
+ *
+ * Strides are 3 host values in elements for (plane, y, x), none negative:
+ * (time, y, x) and (y, x, time) maps, crops and strided outputs are read and
+ * written where they lie.  Outputs must not overlap the input or each other.
+ *
+ * The workspace (nd_amd_regions_workspace_bytes; with_sizes for a labelling
+ * with area, and for the sieve) holds an int32 parent per pixel and plane, with
+ * sizes another int32, and one int32 per 1024 pixels: 4 or 8 bytes per pixel
+ * and plane.  A caller caps it by passing fewer planes per call.
+ *
+ * The labelling is a union-find whose loops are all bounded by what a correct
+ * run cannot reach; a loop that reaches its bound sets a word that
+ * nd_amd_label_regions and nd_amd_sieve_regions read back before they return:
+ * these two entries WAIT for the stream (they cannot be captured in a graph)
+ * and return ND_AMD_EINTERNAL then.  nd_amd_region_sizes does not wait.
+ * ND_AMD_EINVAL before any HIP call for a bad dtype or connectivity, negative
+ * sizes or strides and null pointers; ND_AMD_EUNSUPPORTED for planes of 2^31
+ * pixels or more (checked before the pointers) and more blocks than a launch
+ * holds; ND_AMD_EWORKSPACE for a missing or short workspace; ND_AMD_OK for an
+ * empty batch or plane.
+ * ---------------------------------------------------------------------- */
+size_t nd_amd_regions_workspace_bytes(int64_t nplanes, int64_t ny, int64_t nx, int with_sizes);
+
+int nd_amd_label_regions(const void *src, int dtype, int64_t nplanes, int64_t ny, int64_t nx,
+                         const int64_t *src_strides, int connectivity, int by_value,
+                         const void *background,                       /* one host element                  */
+                         int32_t *labels, const int64_t *label_strides,
+                         int32_t *area, const int64_t *area_strides,   /* NULL: no area plane               */
+                         int64_t *counts,                              /* device, nplanes                   */
+                         void *workspace, size_t workspace_bytes, void *hip_stream);
+
+int nd_amd_region_sizes(const int32_t *labels, const int64_t *label_strides,
+                        int64_t nplanes, int64_t ny, int64_t nx,
+                        const int64_t *offsets,                        /* device, nplanes                   */
+                        int32_t *sizes, int64_t nsizes, void *hip_stream);
+
+int nd_amd_sieve_regions(const void *src, void *dst, int dtype, int64_t nplanes, int64_t ny, int64_t nx,
+                         const int64_t *src_strides, const int64_t *dst_strides,
+                         int connectivity, int by_value,
+                         const void *background, const void *fill,     /* one host element each             */
+                         int64_t min_size, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,9 @@ LIB_PATH = os.environ.get('ND_AMD_LIB') or os.path.join(_HERE, 'libnd_amd.so')
 
 F32, F64 = 0, 1
 I64 = 2                 # values of nd_amd_rasterize_polygons
+U8, I32 = 3, 4          # with F32, F64 and I64: the map types of the region entries
 OK, EINVAL, EWORKSPACE, EHIP, ENOSOLUTION, EUNSUPPORTED = 0, -1, -2, -3, -4, -5
+EINTERNAL = -6
 MODES = {'reflect': 0, 'constant': 1, 'nearest': 2, 'mirror': 3, 'wrap': 4,
          'grid-constant': 1, 'grid-mirror': 0, 'grid-wrap': 4}
 KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
@@ -22,7 +24,7 @@ KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose',
                 17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean',
                 21: 'classify_knn', 22: 'classify_linear', 23: 'kmeans_step', 24: 'feature_moments',
-                25: 'gather_rows', 26: 'change_segments', 27: 'rasterize', 28: 'resample', 29: 'speckle'}
+                25: 'gather_rows', 26: 'change_segments', 27: 'rasterize', 28: 'resample', 29: 'speckle', 30: 'regions'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 STRUCT_DIAG, STRUCT_C2, STRUCT_C3 = 0, 1, 2
 
@@ -48,7 +50,8 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_gather_rows',
            'nd_amd_rasterize_workspace_bytes', 'nd_amd_rasterize_polygons',
            'nd_amd_resample', 'nd_amd_resample_nearest', 'nd_amd_resample_check_table',
-           'nd_amd_speckle_lee', 'nd_amd_speckle_multitemporal_workspace_bytes', 'nd_amd_speckle_multitemporal')
+           'nd_amd_speckle_lee', 'nd_amd_speckle_multitemporal_workspace_bytes', 'nd_amd_speckle_multitemporal',
+           'nd_amd_regions_workspace_bytes', 'nd_amd_label_regions', 'nd_amd_region_sizes', 'nd_amd_sieve_regions')
 CLASSIFY_BLOCK_ROWS, CLASSIFY_MAX_FEATURES = 1024, 1024
 CLASSIFY_KNN_MAX_K, CLASSIFY_KNN_MAX_FEATURES, CLASSIFY_KNN_TILE = 32, 128, 8
 KMEANS_FIT_MAX_ACC = 4096
@@ -216,6 +219,16 @@ def lib():
     L.nd_amd_speckle_multitemporal.restype = i32
     L.nd_amd_speckle_multitemporal.argtypes = [C.POINTER(vp), C.POINTER(vp), i32, i32, i64, i64, i64, pi64, pi64,
                                                i32, vp, C.c_size_t, vp]
+    L.nd_amd_regions_workspace_bytes.restype = C.c_size_t
+    L.nd_amd_regions_workspace_bytes.argtypes = [i64, i64, i64, i32]
+    L.nd_amd_label_regions.restype = i32
+    L.nd_amd_label_regions.argtypes = [vp, i32, i64, i64, i64, pi64, i32, i32, vp, vp, pi64, vp, pi64, vp,
+                                       vp, C.c_size_t, vp]
+    L.nd_amd_region_sizes.restype = i32
+    L.nd_amd_region_sizes.argtypes = [vp, pi64, i64, i64, i64, vp, vp, i64, vp]
+    L.nd_amd_sieve_regions.restype = i32
+    L.nd_amd_sieve_regions.argtypes = [vp, vp, i32, i64, i64, i64, pi64, pi64, i32, i32, vp, vp, i64,
+                                       vp, C.c_size_t, vp]
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

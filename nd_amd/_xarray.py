@@ -2,7 +2,8 @@
 nd_amd/_xarray.py -- optional xarray accessors mirroring nd/_xarray.py:135-161 for the algorithms
 this package provides: `ds.nd_amd.change_omnibus(...)`, `ds.nd_amd.nlmeans(...)`,
 `ds.nd_amd.boxcar(...)`, `ds.nd_amd.convolve(...)`, `ds.nd_amd.gaussian(...)`, `ds.nd_amd.to_rgb(...)`,
-`ds.nd_amd.resample(...)`, `ds.nd_amd.reproject(...)`, `ds.nd_amd.lee(...)`, `ds.nd_amd.multitemporal(...)`.
+`ds.nd_amd.resample(...)`, `ds.nd_amd.reproject(...)`, `ds.nd_amd.lee(...)`, `ds.nd_amd.multitemporal(...)`,
+`ds.nd_amd.sieve(...)`, `ds.nd_amd.label_regions(...)`.
 
 Registered only when xarray is importable (it is not installed in the build or GPU images); the
 accessor name differs from the reference's (`nd`, `filter`) so both can be loaded side by side.
@@ -24,6 +25,8 @@ _METHODS = {
     'multitemporal': ('filters', 'multitemporal'),
     'resample': ('warp', 'resample'),
     'reproject': ('warp', 'reproject'),
+    'sieve': ('regions', 'sieve'),
+    'label_regions': ('regions', 'label_regions'),
 }
 
 
@@ -54,8 +57,8 @@ def register():
     """Attach the `nd_amd` accessor to xarray Datasets and DataArrays; False without xarray."""
     if xr is None:
         return False
-    from . import change, filters, warp
-    modules = {'change': change, 'filters': filters, 'warp': warp}
+    from . import change, filters, regions, warp
+    modules = {'change': change, 'filters': filters, 'regions': regions, 'warp': warp}
     namespace = {'__init__': lambda accessor, obj: setattr(accessor, '_obj', obj)}
     for name, (module, function) in _METHODS.items():
         namespace[name] = _forward(getattr(modules[module], function))

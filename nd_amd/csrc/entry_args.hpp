@@ -1,5 +1,5 @@
 // nd_amd/csrc/entry_args.hpp -- what the change-detection entries (nd_amd_omnibus_c2 / _c2_ml / _c2_pixel_major,
-// _c3 / _c3_pixel_major, _diag, nd_amd_change_segments) decide alike, written once: which arguments are
+// _c3 / _c3_pixel_major, _diag, nd_amd_change_segments) and the region entries decide alike, written once: which arguments are
 // acceptable, how a raster is walked in rows, and how many blocks walk a sharded candidate list.  Plain C++:
 // no HIP header and no device symbol, so every unit may include it (common.hpp does) and a CPU checks it
 // (tools/check_entry_args.cpp, tests/test_host_logic.py).
@@ -78,6 +78,54 @@ static inline int check_date_strides(const char *entry, const int64_t *date_stri
             return ND_AMD_EINVAL;
         }
     return ND_AMD_OK;
+}
+
+// ---- the region entries (nd_amd_label_regions, nd_amd_region_sizes, nd_amd_sieve_regions)
+// the element size of a map's type, 0 for a type that is none
+static inline int region_dtype_size(int dtype)
+{
+    switch (dtype) {
+    case ND_AMD_U8: return 1;
+    case ND_AMD_F32: case ND_AMD_I32: return 4;
+    case ND_AMD_F64: case ND_AMD_I64: return 8;
+    default: return 0;
+    }
+}
+
+static inline int check_region_dtype(const char *entry, int dtype)
+{
+    if (region_dtype_size(dtype)) return ND_AMD_OK;
+    set_error("%s: dtype must be ND_AMD_U8, ND_AMD_I32, ND_AMD_I64, ND_AMD_F32 or ND_AMD_F64, got %d", entry, dtype);
+    return ND_AMD_EINVAL;
+}
+
+static inline int check_connectivity(const char *entry, int connectivity)
+{
+    if (connectivity == 4 || connectivity == 8) return ND_AMD_OK;
+    set_error("%s: connectivity must be 4 or 8, got %d", entry, connectivity);
+    return ND_AMD_EINVAL;
+}
+
+// pixels of a plane are linked by their in-plane index in an int32
+static inline int check_plane_pixels(const char *entry, int64_t ny, int64_t nx)
+{
+    const int64_t limit = (int64_t)1 << 31;
+    if (ny <= 0 || nx < limit / ny + (limit % ny != 0)) return ND_AMD_OK;
+    set_error("%s: planes of 2^31 pixels or more are not served (%lld x %lld)", entry, (long long)ny, (long long)nx);
+    return ND_AMD_EUNSUPPORTED;
+}
+
+// 3 host values in elements for (plane, y, x), none negative
+static inline int check_strides(const char *entry, const char *what, const int64_t *s)
+{
+    if (!s) {
+        set_error("%s: %s is null", entry, what);
+        return ND_AMD_EINVAL;
+    }
+    if (s[0] >= 0 && s[1] >= 0 && s[2] >= 0) return ND_AMD_OK;
+    set_error("%s: negative stride in %s (%lld, %lld, %lld)", entry, what, (long long)s[0], (long long)s[1],
+              (long long)s[2]);
+    return ND_AMD_EINVAL;
 }
 
 // ---- grids

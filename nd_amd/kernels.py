@@ -1953,6 +1953,236 @@ def speckle_multitemporal(planes, w, dims=('time', 'y', 'x'), out=None):
     return given[0] if single else given
 
 
+# ---------------------------------------------------------------------------
+# regions of a map (include/nd_amd.h "Regions of a map"; scipy.ndimage.label pins the result,
+# tests/regions_ref.py restates the by_value form)
+# ---------------------------------------------------------------------------
+_REGION_DT = {torch.bool: _lib.U8, torch.uint8: _lib.U8, torch.int32: _lib.I32, torch.int64: _lib.I64,
+              torch.float32: _lib.F32, torch.float64: _lib.F64}
+_REGION_NP = {torch.bool: np.uint8, torch.uint8: np.uint8, torch.int32: np.int32, torch.int64: np.int64,
+              torch.float32: np.float32, torch.float64: np.float64}
+# The labelling's workspace (4 bytes per pixel and plane, 8 with area and for the sieve) is capped at this many
+# bytes: a larger batch is walked in chunks of planes.  One plane is always served, whatever it takes.
+REGIONS_WORKSPACE_CAP = 1 << 30
+
+
+def region_element(value, dtype, name='background'):
+    """`value` as one numpy element of the map's torch `dtype` (bool as uint8); ValueError if the type cannot hold it
+    exactly.  NaN is held by the floating types."""
+    if dtype not in _REGION_DT:
+        raise TypeError('maps of bool, uint8, int32, int64, float32 and float64 are served, got %s' % (dtype,))
+    npt = np.dtype(_REGION_NP[dtype])
+    if isinstance(value, (bool, np.bool_)):
+        value = int(value)
+    bad = ValueError('%s = %r is not representable in %s' % (name, value, dtype))
+    if npt.kind == 'f':
+        with np.errstate(over='ignore', invalid='ignore'):
+            e = npt.type(value)
+        v = float(value)
+        if not (v != v and e != e) and not (np.isfinite(e) == np.isfinite(v) and float(e) == v):
+            raise bad
+        return e
+    if isinstance(value, (float, np.floating)):
+        if value != value or value != int(value):
+            raise bad
+        value = int(value)
+    value = int(value)
+    info = np.iinfo(npt)
+    if not info.min <= value <= (1 if dtype == torch.bool else info.max):
+        raise bad
+    return npt.type(value)
+
+
+def _region_input(inp, dims, name='inp'):
+    """-> (dims, ay, ax, ny, nx): the checks label_regions and sieve_regions share"""
+    if not torch.is_tensor(inp):
+        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(inp)))
+    if not inp.is_cuda:
+        raise ValueError('%s must live on a ROCm device (got %s); nd_amd has no CPU path' % (name, inp.device))
+    if inp.is_complex():
+        raise TypeError('%s is complex: regions are defined on real maps' % name)
+    if inp.dtype not in _REGION_DT:
+        raise TypeError('%s must be bool, uint8, int32, int64, float32 or float64, got %s' % (name, inp.dtype))
+    if dims is None:
+        dims = {2: ('y', 'x'), 3: ('time', 'y', 'x')}.get(inp.dim())
+        if dims is None:
+            raise ValueError('dims must name the %d axes of %s' % (inp.dim(), name))
+    dims = tuple(dims)
+    if len(dims) != inp.dim() or len(set(dims)) != len(dims) or 'y' not in dims or 'x' not in dims:
+        raise ValueError("dims must name the tensor's %d axes, 'y' and 'x' among them, got %r" % (inp.dim(), dims))
+    ay, ax = dims.index('y'), dims.index('x')
+    ny, nx = inp.shape[ay], inp.shape[ax]
+    if ny * nx >= 2 ** 31:
+        raise NotImplementedError('planes of 2^31 pixels or more are not served (%d x %d)' % (ny, nx))
+    return dims, ay, ax, ny, nx
+
+
+def _region_connectivity(connectivity):
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError('connectivity must be 4 or 8, got %r' % (connectivity,))
+    return int(connectivity)
+
+
+def _region_out(out, like, dtype, name, sources):
+    if out is None:
+        # the input's memory order, packed
+        order = sorted(range(like.dim()), key=lambda d: (-like.stride(d), d))
+        inv = [order.index(d) for d in range(like.dim())]
+        return torch.empty([like.shape[d] for d in order], dtype=dtype, device=like.device).permute(*inv)
+    if (not torch.is_tensor(out) or out.shape != like.shape or out.dtype != dtype or out.device != like.device):
+        raise ValueError('%s must be %s of %s on %s' % (name, tuple(like.shape), dtype, like.device))
+    if any(s == 0 and n > 1 for s, n in zip(out.stride(), out.shape)):
+        raise ValueError('an expanded %s (stride 0) is not served' % name)
+    if any(s < 0 for s in out.stride()):
+        raise ValueError('%s has a negative stride' % name)
+    for s in sources:
+        if s is not None and _may_overlap(out, s):
+            raise ValueError('%s must not overlap the input or another output' % name)
+    return out
+
+
+def _plane_batches(tensors, ay, ax):
+    """every tensor (all of one shape) as (lead..., plane, y, x) views, and the index tuples of the leading axes: the
+    batch axis of a call is the last axis besides y and x, axes before it are walked on the host"""
+    t0 = tensors[0]
+    rest = [d for d in range(t0.dim()) if d not in (ay, ax)]
+    order = rest + [ay, ax]
+    views = [None if t is None else t.permute(*order) for t in tensors]
+    if not rest:
+        views = [None if v is None else v[None] for v in views]
+    return views, list(np.ndindex(*views[0].shape[:-3]))
+
+
+def _region_chunks(nplanes, ny, nx, sizes):
+    """plane ranges of a batch so that the workspace of each stays under REGIONS_WORKSPACE_CAP"""
+    per_plane = ny * nx * (8 if sizes else 4) + 4 * (-(-ny * nx // 1024)) + 512
+    step = max(1, min(nplanes, REGIONS_WORKSPACE_CAP // max(per_plane, 1)))
+    return [(p, min(nplanes, p + step)) for p in range(0, nplanes, step)]
+
+
+def _byte_view(t):
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def label_regions(inp, connectivity=4, background=0, by_value=False, dims=None, labels=None, area=None):
+    """The connected regions of every (y, x) plane of `inp`, numbered from 1 in raster order of their first pixel
+    (include/nd_amd.h "Regions of a map"; with by_value=False it is scipy.ndimage.label(inp != background)).
+    inp: a ROCm tensor of bool, uint8, int32, int64, float32 or float64 whose axes `dims` names, 'y' and 'x' among
+    them -- by default ('y', 'x') for two axes and ('time', 'y', 'x') for three; any non-negative strides.
+    connectivity: 4 or 8.  background: the value that is no region (NaN never is one).  by_value: neighbours are
+    joined only where their values are equal.  labels: an int32 tensor of the input's shape, any strides, not
+    overlapping it.  area: True, or such a tensor, for the pixel count of every pixel's region as well.
+    -> (labels, counts) or (labels, counts, area); counts is int64 with the input's shape without y and x: the
+    number of regions of every plane.  Waits for the device."""
+    dims, ay, ax, ny, nx = _region_input(inp, dims)
+    conn = _region_connectivity(connectivity)
+    bg = region_element(background, inp.dtype)
+    dev = inp.device
+    labels = _region_out(labels, inp, torch.int32, 'labels', [inp])
+    want_area = area is not None and area is not False
+    area = _region_out(None if area is True else area, inp, torch.int32, 'area', [inp, labels]) if want_area else None
+    lead_shape = [n for d, n in enumerate(inp.shape) if d not in (ay, ax)]
+    counts = torch.zeros(lead_shape, dtype=torch.int64, device=dev)
+    if inp.numel() == 0:
+        return (labels, counts, area) if want_area else (labels, counts)
+    (src, lab, ar), lead = _plane_batches([_byte_view(inp), labels, area], ay, ax)
+    cnt = counts.reshape(src.shape[:-2]) if lead_shape else counts.reshape(1)
+    L = _lib.lib()
+    bg_buf = np.array([bg])
+    bgp = C.c_void_p(bg_buf.ctypes.data)
+    with torch.cuda.device(dev):
+        nplanes = src.shape[-3]
+        chunks = _region_chunks(nplanes, ny, nx, want_area)
+        nbytes = int(L.nd_amd_regions_workspace_bytes(chunks[0][1] - chunks[0][0], ny, nx, int(want_area)))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        for idx in lead:
+            s, l, c = src[idx], lab[idx], cnt[idx]
+            a = ar[idx] if want_area else None
+            for p0, p1 in chunks:
+                _lib.check(L.nd_amd_label_regions(
+                    _ptr(s[p0:p1]), _REGION_DT[inp.dtype], p1 - p0, ny, nx, _lib.i64_array(s.stride()), conn,
+                    int(bool(by_value)), bgp, _ptr(l[p0:p1]), _lib.i64_array(l.stride()),
+                    _ptr(a[p0:p1]) if want_area else None, _lib.i64_array(a.stride()) if want_area else None,
+                    _ptr(c[p0:p1]), _ptr(work), nbytes, _stream_ptr(dev)))
+        _record([inp, labels, area, counts, work], dev)
+    return (labels, counts, area) if want_area else (labels, counts)
+
+
+def region_sizes(labels, counts, dims=None):
+    """The pixel count of every region of a labelling: `labels` and `counts` as label_regions returned them.
+    -> (sizes, offsets): sizes is int32 with counts.sum() entries, the regions of plane p (in the order of counts'
+    elements) at offsets[p] : offsets[p] + counts[p]; offsets is an int64 host array with one entry more than planes.
+    It counts the labels; it does not label again."""
+    dims, ay, ax, ny, nx = _region_input(labels, dims, 'labels')
+    if labels.dtype != torch.int32:
+        raise TypeError('labels must be int32, got %s' % labels.dtype)
+    lead_shape = [n for d, n in enumerate(labels.shape) if d not in (ay, ax)]
+    if not torch.is_tensor(counts) or list(counts.shape) != lead_shape:
+        raise ValueError('counts must be the tensor label_regions returned: shape %s' % (tuple(lead_shape),))
+    dev = labels.device
+    host = counts.reshape(-1).to('cpu', torch.int64).numpy()
+    if (host < 0).any():
+        raise ValueError('counts must not be negative')
+    offsets = np.concatenate(([0], np.cumsum(host))).astype(np.int64)
+    total = int(offsets[-1])
+    sizes = torch.zeros(total, dtype=torch.int32, device=dev)
+    if total == 0 or labels.numel() == 0:
+        return sizes, offsets
+    (lab,), lead = _plane_batches([labels], ay, ax)
+    nplanes = lab.shape[-3]
+    off_dev = torch.from_numpy(offsets[:-1].copy()).to(dev).reshape(lab.shape[:-2])
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        for n, idx in enumerate(lead):
+            l = lab[idx]
+            lo, hi = int(offsets[n * nplanes]), int(offsets[(n + 1) * nplanes])
+            if hi == lo:
+                continue
+            # this batch's planes count into their own slice of sizes: offsets relative to its start
+            rel = (off_dev[idx] - lo).contiguous()
+            _lib.check(L.nd_amd_region_sizes(_ptr(l), _lib.i64_array(l.stride()), nplanes, ny, nx, _ptr(rel),
+                                             _ptr(sizes[lo:hi]), hi - lo, _stream_ptr(dev)))
+            _record([rel], dev)
+        _record([labels, sizes], dev)
+    return sizes, offsets
+
+
+def sieve_regions(inp, min_size, connectivity=4, background=0, by_value=False, fill=None, dims=None, out=None):
+    """`inp` with every region of fewer than `min_size` pixels replaced by `fill` (default: `background`); background
+    pixels, NaN among them, keep their bits, and min_size <= 1 is a copy (include/nd_amd.h "Regions of a map").
+    Arguments as for label_regions; out: a tensor of the input's shape and type, any strides, not overlapping it.
+    -> out.  Waits for the device."""
+    dims, ay, ax, ny, nx = _region_input(inp, dims)
+    conn = _region_connectivity(connectivity)
+    if isinstance(min_size, bool) or int(min_size) != min_size:
+        raise ValueError('min_size must be an integer, got %r' % (min_size,))
+    min_size = max(-1, min(int(min_size), 2 ** 62))
+    bg = region_element(background, inp.dtype)
+    fl = bg if fill is None else region_element(fill, inp.dtype, 'fill')
+    out = _region_out(out, inp, inp.dtype, 'out', [inp])
+    if inp.numel() == 0:
+        return out
+    dev = inp.device
+    (src, dst), lead = _plane_batches([_byte_view(inp), _byte_view(out)], ay, ax)
+    bg_buf, fill_buf = np.array([bg]), np.array([fl])
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nplanes = src.shape[-3]
+        chunks = _region_chunks(nplanes, ny, nx, True)
+        nbytes = int(L.nd_amd_regions_workspace_bytes(chunks[0][1] - chunks[0][0], ny, nx, 1)) if min_size > 1 else 0
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        for idx in lead:
+            s, d = src[idx], dst[idx]
+            for p0, p1 in chunks:
+                _lib.check(L.nd_amd_sieve_regions(
+                    _ptr(s[p0:p1]), _ptr(d[p0:p1]), _REGION_DT[inp.dtype], p1 - p0, ny, nx,
+                    _lib.i64_array(s.stride()), _lib.i64_array(d.stride()), conn, int(bool(by_value)),
+                    C.c_void_p(bg_buf.ctypes.data), C.c_void_p(fill_buf.ctypes.data), min_size, _ptr(work), nbytes,
+                    _stream_ptr(dev)))
+        _record([inp, out, work], dev)
+    return out
+
+
 def _lib_device(device=None):
     if device is not None:
         return torch.device(device)
