@@ -386,8 +386,6 @@ __global__ void __launch_bounds__(256) coreg_refine_kernel(const double *mag, co
     status[t] = t == ref ? 0 : (best.nan | p.nan);
 }
 
-static inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 struct ShiftLayout {
     size_t stage, spec, spec2, partials, peaks, kxa, kxb, ky, kyr, A, B, mag, total;
     int nblk, R;
@@ -402,7 +400,7 @@ static ShiftLayout shift_layout(int dtype, int64_t k, int64_t ny, int64_t nx, in
     const int64_t nb = n / (256 * 16);
     L.nblk = (int)(nb < 1 ? 1 : (nb > 256 ? 256 : nb));
     size_t off = 0;
-    auto put = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
+    auto put = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
     const size_t R = (size_t)L.R;
     L.stage = put(k * n * es);                       // planar C11, then the C2R output
     L.spec = put(k * ny * nh * 2 * es);              // F_t
@@ -793,7 +791,7 @@ static WarpLayout warp_layout(int dtype, int nvars, int64_t k, int64_t nr, int64
         if (L.nblk > cap) L.nblk = (int)(cap < 1 ? 1 : cap);
     }
     size_t off = 0;
-    auto put = [&](size_t bytes) { const size_t o = off; off += al256(bytes); return o; };
+    auto put = [&](size_t bytes) { const size_t o = off; off += align256(bytes); return o; };
     L.ri = put(k * nr * 4);
     L.ci = put(k * nc * 4);
     L.rf = put(k * nr * es);

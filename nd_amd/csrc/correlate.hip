@@ -15,8 +15,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "borders.hpp"
 #include "common.hpp"
 #include "dispatch.hpp"
+#include "lanes.hpp"
 
 namespace nd_amd {
 
@@ -35,50 +37,6 @@ struct Tap {
 struct TapsByValue {
     Tap t[kTapsArgs];
 };
-
-__device__ __forceinline__ int64_t extend_index(int64_t cc, int64_t len, int mode)
-{
-    if (cc >= 0 && cc < len) return cc;
-    switch (mode) {
-    case ND_AMD_MODE_REFLECT: {
-        if (len <= 1) return 0;
-        const int64_t sz2 = 2 * len;
-        if (cc < 0) {
-            if (cc < -sz2) cc += sz2 * (-cc / sz2);
-            return cc < -len ? cc + sz2 : -cc - 1;
-        }
-        cc -= sz2 * (cc / sz2);
-        if (cc >= len) cc = sz2 - cc - 1;
-        return cc;
-    }
-    case ND_AMD_MODE_CONSTANT:
-        return -1;
-    case ND_AMD_MODE_NEAREST:
-        return cc < 0 ? 0 : len - 1;
-    case ND_AMD_MODE_MIRROR: {
-        if (len <= 1) return 0;
-        const int64_t sz2 = 2 * len - 2;
-        if (cc < 0) {
-            cc = sz2 * (-cc / sz2) + cc;
-            return cc <= 1 - len ? cc + sz2 : -cc;
-        }
-        cc -= sz2 * (cc / sz2);
-        if (cc >= len) cc = sz2 - cc;
-        return cc;
-    }
-    case ND_AMD_MODE_WRAP: {
-        if (len <= 1) return 0;
-        if (cc < 0) {
-            cc += len * (-cc / len);
-            if (cc < 0) cc += len;
-            return cc;
-        }
-        cc -= len * (cc / len);
-        return cc;
-    }
-    }
-    return -1;
-}
 
 template <typename T>
 struct CorrArgs {
@@ -115,10 +73,10 @@ __global__ void __launch_bounds__(256) correlate_kernel(const CorrArgs<T> a, con
             v = (double)a.in[base + tp.o[0] * a.si[0] + tp.o[1] * a.si[1] + tp.o[2] * a.si[2] +
                              tp.o[3] * a.si[3]];
         } else {
-            const int64_t j0 = extend_index(i0 + tp.o[0], a.A[0], a.mode);
-            const int64_t j1 = extend_index(i1 + tp.o[1], a.A[1], a.mode);
-            const int64_t j2 = extend_index(i2 + tp.o[2], a.A[2], a.mode);
-            const int64_t j3 = extend_index(i3 + tp.o[3], a.A[3], a.mode);
+            const int64_t j0 = extend_index<int64_t, false>(i0 + tp.o[0], a.A[0], a.mode);
+            const int64_t j1 = extend_index<int64_t, false>(i1 + tp.o[1], a.A[1], a.mode);
+            const int64_t j2 = extend_index<int64_t, false>(i2 + tp.o[2], a.A[2], a.mode);
+            const int64_t j3 = extend_index<int64_t, false>(i3 + tp.o[3], a.A[3], a.mode);
             if (j0 < 0 || j1 < 0 || j2 < 0 || j3 < 0)
                 v = a.cval;
             else
@@ -208,10 +166,10 @@ __global__ void __launch_bounds__(256) correlate_tiled_kernel(const TiledArgs<T>
         // mode `constant`: -1 marks a sample outside the plane; it is staged as cval (below) and its
         // load goes to element 0
         if (i < th) {
-            const int64_t m = extend_index(y_base + a.oy0 + i, a.ny, a.mode);
+            const int64_t m = extend_index<int64_t, false>(y_base + a.oy0 + i, a.ny, a.mode);
             ymap[i] = m < 0 ? (a.mode == ND_AMD_MODE_CONSTANT ? -1 : 0) : (int)m;
         } else {
-            const int64_t m = extend_index(x_base + a.ox0 + (i - th), a.nx, a.mode);
+            const int64_t m = extend_index<int64_t, false>(x_base + a.ox0 + (i - th), a.nx, a.mode);
             xmap[i - th] = m < 0 ? (a.mode == ND_AMD_MODE_CONSTANT ? -1 : 0) : (int)m;
         }
     }
@@ -262,7 +220,7 @@ __global__ void __launch_bounds__(256) correlate_tiled_kernel(const TiledArgs<T>
     auto load_plane = [&](int64_t bb, int dt) {
         const int64_t v = bb / a.nt, t = bb - v * a.nt;
         // (a single tap plane may still lie off the output's own: a sparse kernel whose other planes are zero)
-        const int64_t ts = (kt == 1 && a.ot0 == 0) ? t : extend_index(t + a.ot0 + dt, a.nt, a.mode);
+        const int64_t ts = (kt == 1 && a.ot0 == 0) ? t : extend_index<int64_t, false>(t + a.ot0 + dt, a.nt, a.mode);
         plane_ok = ts >= 0;
         const T *plane = a.in + v * a.sin_v + (ts < 0 ? 0 : ts) * a.sin_t;
 #pragma unroll
@@ -426,54 +384,6 @@ static bool launch_tiled_big(const TiledArgs<T> &a, int kw, bool box, int64_t nb
 // -----------------------------------------------------------------------------------------
 constexpr int kRollStrip = 256;          // columns per wave: 64 lanes x 4
 
-// extend_index in 32-bit arithmetic (extents below 2^30, checked on the host), clamped into the
-// array: the row loop holds 2 K inlined copies and the 64-bit divisions made most of its code
-__device__ __forceinline__ int extend_index32(int cc, int len, int mode)
-{
-    if (cc >= 0 && cc < len) return cc;
-    int m = 0;
-    if (len > 1) {
-        switch (mode) {
-        case ND_AMD_MODE_REFLECT: {
-            const int sz2 = 2 * len;
-            if (cc < 0) {
-                if (cc < -sz2) cc += sz2 * (-cc / sz2);
-                m = cc < -len ? cc + sz2 : -cc - 1;
-            } else {
-                cc -= sz2 * (cc / sz2);
-                m = cc >= len ? sz2 - cc - 1 : cc;
-            }
-            break;
-        }
-        case ND_AMD_MODE_NEAREST:
-            m = cc < 0 ? 0 : len - 1;
-            break;
-        case ND_AMD_MODE_MIRROR: {
-            const int sz2 = 2 * len - 2;
-            if (cc < 0) {
-                cc = sz2 * (-cc / sz2) + cc;
-                m = cc <= 1 - len ? cc + sz2 : -cc;
-            } else {
-                cc -= sz2 * (cc / sz2);
-                m = cc >= len ? sz2 - cc : cc;
-            }
-            break;
-        }
-        case ND_AMD_MODE_WRAP: {
-            if (cc < 0) {
-                cc += len * (-cc / len);
-                if (cc < 0) cc += len;
-                m = cc;
-            } else {
-                m = cc - len * (cc / len);
-            }
-            break;
-        }
-        }
-    }
-    return m < 0 ? 0 : (m >= len ? len - 1 : m);
-}
-
 struct RollArgs {
     const float *in;
     float *out;
@@ -485,19 +395,6 @@ struct RollArgs {
     int vec_in, vec_out;        // 16-byte accesses allowed (base and strides aligned)
     double w[49];               // dense KH x KW weights, row-major
 };
-
-__device__ __forceinline__ double roll_from_prev(double x)      // lane i <- lane i - 1
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x138, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x138, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double roll_from_next(double x)      // lane i <- lane i + 1
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x130, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x130, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
 
 template <int K, bool BOX>
 __global__ void __launch_bounds__(256, (K == 3 ? 6 : (K == 5 ? 4 : 2))) correlate_roll_kernel(const RollArgs a)
@@ -523,10 +420,10 @@ __global__ void __launch_bounds__(256, (K == 3 ? 6 : (K == 5 ? 4 : 2))) correlat
     int xm[4], xe[H];
     const bool first = lane == 0, lastl = lane == 63;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) xm[c] = 4 * extend_index32(x + c, nx, a.mode);
+    for (int c = 0; c < 4; ++c) xm[c] = 4 * extend_index<int, true>(x + c, nx, a.mode);
 #pragma unroll
     for (int j = 0; j < H; ++j)
-        xe[j] = 4 * extend_index32((lane < 32 ? xs - H : xs + kRollStrip) + j, nx, a.mode);
+        xe[j] = 4 * extend_index<int, true>((lane < 32 ? xs - H : xs + kRollStrip) + j, nx, a.mode);
     const bool wave_vec = a.vec_in && xs + kRollStrip <= nx;
     const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in + plane * a.sin_b), 0,
                                                        0x7fffffff, 0x00020000);
@@ -541,7 +438,7 @@ __global__ void __launch_bounds__(256, (K == 3 ? 6 : (K == 5 ? 4 : 2))) correlat
     auto load_row = [&](int64_t r) -> RowRegs {
         RowRegs rr;
         f32x4 v;
-        const int m = extend_index32((int)r, (int)a.ny, a.mode);
+        const int m = extend_index<int, true>((int)r, (int)a.ny, a.mode);
         const int soff = __builtin_amdgcn_readfirstlane(m * (int)a.sin_y * 4);
         if (wave_vec) {
             v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, xm[0], soff, 0));
@@ -602,7 +499,7 @@ __global__ void __launch_bounds__(256, (K == 3 ? 6 : (K == 5 ? 4 : 2))) correlat
                 for (int c = 0; c < 4; ++c) win[ph][H + c] = d[c];
 #pragma unroll
                 for (int j = 0; j < H; ++j) {
-                    const double lp = roll_from_prev(d[4 - H + j]), rn = roll_from_next(d[j]);
+                    const double lp = lane_from_prev(d[4 - H + j]), rn = lane_from_next(d[j]);
                     win[ph][j] = first ? de[j] : lp;
                     win[ph][H + 4 + j] = lastl ? de[j] : rn;
                 }
@@ -925,40 +822,7 @@ static int correlate_impl(const void *in, void *out, const int64_t dims[4], cons
 // -----------------------------------------------------------------------------------------
 constexpr int kMaxW1D = 255;
 
-// Line extension of NI_ExtendLine (ni_support.c), which the 1-D filters use: exactly periodic
-// for any distance from the array (unlike the offset table of the N-D correlate).
-//   reflect  d c b a | a b c d | d c b a      (period 2n)
-//   mirror     d c b | a b c d | c b a        (period 2n - 2)
-//   wrap     a b c d | a b c d | a b c d      nearest: edge value      constant: cval (-1)
-__device__ __forceinline__ int64_t extend_line(int64_t cc, int64_t len, int mode)
-{
-    if (cc >= 0 && cc < len) return cc;
-    switch (mode) {
-    case ND_AMD_MODE_REFLECT: {
-        const int64_t p = 2 * len;
-        int64_t m = cc % p;
-        if (m < 0) m += p;
-        return m < len ? m : p - 1 - m;
-    }
-    case ND_AMD_MODE_CONSTANT:
-        return -1;
-    case ND_AMD_MODE_NEAREST:
-        return cc < 0 ? 0 : len - 1;
-    case ND_AMD_MODE_MIRROR: {
-        if (len <= 1) return 0;
-        const int64_t p = 2 * len - 2;
-        int64_t m = cc % p;
-        if (m < 0) m += p;
-        return m < len ? m : p - m;
-    }
-    case ND_AMD_MODE_WRAP: {
-        int64_t m = cc % len;
-        if (m < 0) m += len;
-        return m;
-    }
-    }
-    return -1;
-}
+// (lines are extended by extend_line, borders.hpp: NI_ExtendLine, periodic at any distance from the array)
 
 template <typename T>
 struct Corr1dArgs {
@@ -987,7 +851,7 @@ __global__ void __launch_bounds__(256) correlate1d_kernel(const Corr1dArgs<T> a)
     const int64_t len = a.A[a.axis], sax = a.si[a.axis], pos = i[a.axis];
     const int64_t base = i[0] * a.si[0] + i[1] * a.si[1] + i[2] * a.si[2] + i[3] * a.si[3] - pos * sax;
     auto x = [&](int64_t j) -> double {
-        const int64_t q = extend_line(pos + j, len, a.mode);
+        const int64_t q = extend_line<int64_t, false>(pos + j, len, a.mode);
         return q < 0 ? a.cval : (double)a.in[base + q * sax];
     };
     const double *fw = a.w + a.size1;
@@ -1061,7 +925,7 @@ __global__ void __launch_bounds__(256) correlate1d_tiled_kernel(const Corr1dTile
     // the other axis beyond the array are clamped (their outputs are never stored)
     const int nmap = ALONG_X ? ucols : trows;
     const int64_t flen = ALONG_X ? a.nx : a.nrows, f0 = (ALONG_X ? x0 : r0) - a.size1;
-    for (int i = tid; i < nmap; i += 256) map[i] = (int)extend_line(f0 + i, flen, a.mode);
+    for (int i = tid; i < nmap; i += 256) map[i] = (int)extend_line<int64_t, false>(f0 + i, flen, a.mode);
     __syncthreads();
 
     // Staging map: thread (row parity, column) takes every second row of its column.  ALONG_X: the
@@ -1353,39 +1217,6 @@ static int correlate1d_impl(const void *in, void *out, const int64_t dims[4], co
 // the plane are scipy's periodic line extension as index maps: the first pass evaluated at a mapped
 // column IS the extended intermediate line.  One read and one write of the array instead of two.
 // -----------------------------------------------------------------------------------------
-__device__ __forceinline__ int extend_line32(int cc, int len, int mode)      // clamped into the line
-{
-    if (cc >= 0 && cc < len) return cc;
-    int m = 0;
-    if (len > 1) {
-        switch (mode) {
-        case ND_AMD_MODE_REFLECT: {
-            const int p = 2 * len;
-            m = cc % p;
-            if (m < 0) m += p;
-            m = m < len ? m : p - 1 - m;
-            break;
-        }
-        case ND_AMD_MODE_NEAREST:
-            m = cc < 0 ? 0 : len - 1;
-            break;
-        case ND_AMD_MODE_MIRROR: {
-            const int p = 2 * len - 2;
-            m = cc % p;
-            if (m < 0) m += p;
-            m = m < len ? m : p - m;
-            break;
-        }
-        case ND_AMD_MODE_WRAP: {
-            m = cc % len;
-            if (m < 0) m += len;
-            break;
-        }
-        }
-    }
-    return m < 0 ? 0 : (m >= len ? len - 1 : m);
-}
-
 template <typename T>
 struct Corr2PassArgs {
     const T *in;
@@ -1399,32 +1230,8 @@ struct Corr2PassArgs {
     double wy[9], wx[9];        // w[d] = weight at distance d from the centre
 };
 
-__device__ __forceinline__ float f32_from_prev(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x138, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float f32_from_next(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x130, 0xF, 0xF, true));
-}
-
 // float64 planes (round 6): the same kernel on doubles -- a lane's four columns are two 16-byte loads, the
 // intermediate array is float64 itself (scipy rounds it to the ARRAY dtype), a value crosses lanes as two DPP moves.
-__device__ __forceinline__ double f32_from_prev(double x)
-{
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, 0x138, 0xF, 0xF, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), 0x138, 0xF, 0xF, true);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double f32_from_next(double x)
-{
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, 0x130, 0xF, 0xF, true);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), 0x130, 0xF, 0xF, true);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
 template <typename T, int R, bool DWIN>
 __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs<T> a)
 {
@@ -1452,7 +1259,7 @@ __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs
 
     int xm[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) xm[c] = ES * extend_line32(x + c, nx, a.mode);
+    for (int c = 0; c < 4; ++c) xm[c] = ES * extend_line<int, true>(x + c, nx, a.mode);
     const bool inside = x >= 0 && x + 3 < nx;
     const bool wave_vec = a.vec_in && __builtin_amdgcn_ballot_w64(!inside) == 0ull;
     const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(a.in + plane * a.sin_b), 0,
@@ -1464,7 +1271,7 @@ __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     typedef double f64x2 __attribute__((ext_vector_type(2)));
     auto load_row = [&](int t) -> f32x4 {            // input row of step t: ys - R + t
-        const int m = extend_line32(ys - R + t, ny, a.mode);
+        const int m = extend_line<int, true>(ys - R + t, ny, a.mode);
         const int soff = __builtin_amdgcn_readfirstlane(m * (int)a.sin_y * ES);
         f32x4 v;
         if constexpr (sizeof(T) == 4) {
@@ -1543,8 +1350,8 @@ __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs
                         T pl[4], nr[4];
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
-                            pl[c] = f32_from_prev(ty[c]);
-                            nr[c] = f32_from_next(ty[c]);
+                            pl[c] = lane_from_prev(ty[c]);
+                            nr[c] = lane_from_next(ty[c]);
                         }
                         constexpr int R1 = R < 4 ? R : 4;
 #pragma unroll
@@ -1555,8 +1362,8 @@ __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs
                         if (R > 4) {
 #pragma unroll
                             for (int j = 0; j < R - 4; ++j) {
-                                ax[R - 5 - j] = (double)f32_from_prev(pl[3 - j]);
-                                ax[R + 8 + j] = (double)f32_from_next(nr[j]);
+                                ax[R - 5 - j] = (double)lane_from_prev(pl[3 - j]);
+                                ax[R + 8 + j] = (double)lane_from_next(nr[j]);
                             }
                         }
                     }

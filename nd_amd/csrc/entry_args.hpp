@@ -1,10 +1,12 @@
 // nd_amd/csrc/entry_args.hpp -- what the change-detection entries (nd_amd_omnibus_c2 / _c2_ml / _c2_pixel_major,
 // _c3 / _c3_pixel_major, _diag, nd_amd_change_segments) and the region entries decide alike, written once: which arguments are
-// acceptable, how a raster is walked in rows, and how many blocks walk a sharded candidate list.  Plain C++:
+// acceptable, how a raster is walked in rows, and how many blocks walk a sharded candidate list; and align256, where
+// every unit's workspace sections start.  Plain C++:
 // no HIP header and no device symbol, so every unit may include it (common.hpp does) and a CPU checks it
 // (tools/check_entry_args.cpp, tests/test_host_logic.py).
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/nd_amd.h"
@@ -14,6 +16,9 @@ namespace nd_amd {
 void set_error(const char *fmt, ...);
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// workspace sections start on 256-byte boundaries
+static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // ---- entry checks: ND_AMD_OK to go on, or the code to return with the message set.  `entry` is the entry
 // point's name.  An entry keeps what only it checks between these calls.  Every refusal here is ND_AMD_EINVAL

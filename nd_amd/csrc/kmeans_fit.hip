@@ -18,6 +18,7 @@
 
 #include "classify_common.hpp"
 #include "dispatch.hpp"
+#include "lanes.hpp"
 
 using namespace nd_amd;
 
@@ -26,13 +27,6 @@ namespace {
 constexpr int WAVE = 64;                    // threads of a block of the reducing kernels
 constexpr int FIT_MAX_GRID = 8192;
 constexpr int64_t FIT_PARTIAL_DOUBLES = INT64_C(1) << 22;   // at most 32 MiB of float64 partials
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
 
 // ---- one Lloyd iteration ----------------------------------------------------------------------
 // NREG > 0: the row's nfeat <= NREG features live in registers.  NREG == 0: they are read again where
@@ -268,8 +262,6 @@ static int fit_grid(int64_t rows, int nfeat, int k)
     const int64_t b = ceil_div(rows, WAVE);
     return (int)(b < cap ? (b < 1 ? 1 : b) : cap);
 }
-
-static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 
 struct FitWorkspace {
     const void *const *tab;

@@ -23,8 +23,10 @@
 
 #include <type_traits>
 
+#include "borders.hpp"
 #include "common.hpp"
 #include "dispatch.hpp"
+#include "lanes.hpp"
 
 namespace nd_amd {
 
@@ -47,14 +49,6 @@ struct NlmArgs {
     int32_t *status;
     int64_t total;
 };
-
-__device__ __forceinline__ int64_t nlm_idx(int64_t i, int64_t shape)
-{
-    // nd/_filters.pyx:34-40 EDGE_MODE_REFLECT
-    if (i < 0) return -i;
-    if (i >= shape) return 2 * shape - 2 - i;
-    return i;
-}
 
 template <typename T, int VMAX>
 __global__ void __launch_bounds__(256) nlmeans_generic_kernel(const NlmArgs<T> a)
@@ -88,12 +82,12 @@ __global__ void __launch_bounds__(256) nlmeans_generic_kernel(const NlmArgs<T> a
         for (int64_t d0 = a.dlo[0]; d0 < a.dhi[0]; ++d0)
         for (int64_t d1 = a.dlo[1]; d1 < a.dhi[1]; ++d1)
         for (int64_t d2 = a.dlo[2]; d2 < a.dhi[2]; ++d2) {
-            const int64_t pa = (nlm_idx(g0 + d0, a.G[0]) - a.toff[0]) * a.si[0] +
-                               (nlm_idx(g1 + d1, a.G[1]) - a.toff[1]) * a.si[1] +
-                               (nlm_idx(g2 + d2, a.G[2]) - a.toff[2]) * a.si[2];
-            const int64_t qa = (nlm_idx(q0 + d0, a.G[0]) - a.toff[0]) * a.si[0] +
-                               (nlm_idx(q1 + d1, a.G[1]) - a.toff[1]) * a.si[1] +
-                               (nlm_idx(q2 + d2, a.G[2]) - a.toff[2]) * a.si[2];
+            const int64_t pa = (reflect_once<int64_t>(g0 + d0, a.G[0]) - a.toff[0]) * a.si[0] +
+                               (reflect_once<int64_t>(g1 + d1, a.G[1]) - a.toff[1]) * a.si[1] +
+                               (reflect_once<int64_t>(g2 + d2, a.G[2]) - a.toff[2]) * a.si[2];
+            const int64_t qa = (reflect_once<int64_t>(q0 + d0, a.G[0]) - a.toff[0]) * a.si[0] +
+                               (reflect_once<int64_t>(q1 + d1, a.G[1]) - a.toff[1]) * a.si[1] +
+                               (reflect_once<int64_t>(q2 + d2, a.G[2]) - a.toff[2]) * a.si[2];
 #pragma unroll
             for (int v = 0; v < VMAX; ++v) {
                 if (v < a.nvars) {
@@ -110,9 +104,9 @@ __global__ void __launch_bounds__(256) nlmeans_generic_kernel(const NlmArgs<T> a
         total_weight = total_weight + weight;
         total_sq_weight = total_sq_weight + (weight * weight);
         if (weight > max_weight) max_weight = weight;
-        const int64_t qq = (nlm_idx(q0, a.G[0]) - a.toff[0]) * a.si[0] +
-                           (nlm_idx(q1, a.G[1]) - a.toff[1]) * a.si[1] +
-                           (nlm_idx(q2, a.G[2]) - a.toff[2]) * a.si[2];
+        const int64_t qq = (reflect_once<int64_t>(q0, a.G[0]) - a.toff[0]) * a.si[0] +
+                           (reflect_once<int64_t>(q1, a.G[1]) - a.toff[1]) * a.si[1] +
+                           (reflect_once<int64_t>(q2, a.G[2]) - a.toff[2]) * a.si[2];
 #pragma unroll
         for (int v = 0; v < VMAX; ++v) {
             if (v < a.nvars)
@@ -199,13 +193,6 @@ struct NlmTiledArgs {
     int32_t *status;
 };
 
-__device__ __forceinline__ int nlm_reflect_i(int64_t i, int64_t shape)
-{
-    if (i < 0) return (int)(-i);
-    if (i >= shape) return (int)(2 * shape - 2 - i);
-    return (int)i;
-}
-
 // stage (rows x cols) of variable v, slice i2, top-left global coordinate (gy0, gx0), into lds
 // (T = double: the float64 window kernel; `arr` / `out` of the arguments are then double arrays and
 // every stride counts doubles)
@@ -218,11 +205,11 @@ __device__ __forceinline__ void nlm_stage_t(const NlmTiledArgs &a, T *lds, int *
         // Positions that feed a written pixel reflect into the tile (checked on the host); the
         // clamps only keep the staging of never-used corner positions inside the allocation.
         if (i < rows) {
-            int m = nlm_reflect_i(gy0 + i, a.G0) - (int)a.off0;
+            int m = reflect_once<int>(gy0 + i, a.G0) - (int)a.off0;
             m = m < 0 ? 0 : (m >= (int)a.N0 ? (int)a.N0 - 1 : m);
             ymap[i] = m;
         } else {
-            int m = nlm_reflect_i(gx0 + (i - rows), a.G1) - (int)a.off1;
+            int m = reflect_once<int>(gx0 + (i - rows), a.G1) - (int)a.off1;
             m = m < 0 ? 0 : (m >= (int)a.N1 ? (int)a.N1 - 1 : m);
             xmap[i - rows] = m;
         }
@@ -339,7 +326,7 @@ __global__ void __launch_bounds__(256) nlmeans_window_kernel(const NlmTiledArgs 
         // the window planes along axis 2 (one plane when rz = 0), whole-sample reflection at the
         // global ends of that axis
         for (int dz = 0; dz < nz; ++dz) {
-            int64_t zz = nlm_reflect_i(a.offz + i2 + dz - rz, a.Gz) - a.offz;
+            int64_t zz = reflect_once<int>(a.offz + i2 + dz - rz, a.Gz) - a.offz;
             zz = zz < 0 ? 0 : (zz >= a.N2 ? a.N2 - 1 : zz);
             nlm_stage_t<T>(a, lds + dz * psz, ymap, xmap, rows, cols, a.off0 + y0 - r0, a.off1 + x0 - r1,
                            zz, v, tid);
@@ -458,7 +445,7 @@ __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiled
     int xoff[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        int m = nlm_reflect_i(a.off1 + x0 - R1 + lane + 64 * j, a.G1) - (int)a.off1;
+        int m = reflect_once<int>(a.off1 + x0 - R1 + lane + 64 * j, a.G1) - (int)a.off1;
         xoff[j] = m < 0 ? 0 : (m >= (int)a.N1 ? (int)a.N1 - 1 : m);
     }
     const float *base = a.arr + (int64_t)v * a.si3;
@@ -471,7 +458,7 @@ __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiled
         for (int u = 0; u < kRollRowsPerWave; ++u) {
             const int rr = wave + 4 * u;
             if (rr < rows) {
-                int m = nlm_reflect_i(gy0 + rr, a.G0) - (int)a.off0;
+                int m = reflect_once<int>(gy0 + rr, a.G0) - (int)a.off0;
                 m = m < 0 ? 0 : (m >= (int)a.N0 ? (int)a.N0 - 1 : m);
                 const float *rp = bp + (int64_t)m * a.si0;
                 pre[u][0] = rp[xoff[0]];
@@ -495,7 +482,7 @@ __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiled
     };
     // local plane that stands for logical slice q of the window
     auto zmap = [&](int64_t q) {
-        int64_t zz = (int64_t)nlm_reflect_i(a.offz + q, a.Gz) - a.offz;
+        int64_t zz = (int64_t)reflect_once<int>(a.offz + q, a.Gz) - a.offz;
         return zz < 0 ? (int64_t)0 : (zz >= a.N2 ? a.N2 - 1 : zz);
     };
 
@@ -676,7 +663,7 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
     int xoff[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
-        int m = nlm_reflect_i(a.off1 + x0 - R + lane + 64 * j, a.G1) - (int)a.off1;
+        int m = reflect_once<int>(a.off1 + x0 - R + lane + 64 * j, a.G1) - (int)a.off1;
         xoff[j] = 4 * (m < 0 ? 0 : (m >= (int)a.N1 ? (int)a.N1 - 1 : m));
     }
     int roff[NPRE];
@@ -684,7 +671,7 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
         const int64_t gy0 = a.off0 + y0 - R;
 #pragma unroll
         for (int u = 0; u < NPRE; ++u) {
-            int m = nlm_reflect_i(gy0 + wave + NWAVES * u, a.G0) - (int)a.off0;
+            int m = reflect_once<int>(gy0 + wave + NWAVES * u, a.G0) - (int)a.off0;
             m = m < 0 ? 0 : (m >= (int)a.N0 ? (int)a.N0 - 1 : m);
             roff[u] = __builtin_amdgcn_readfirstlane(m * (int)a.si0 * 4);
         }
@@ -706,7 +693,7 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
         }
     };
     auto zmap = [&](int64_t q) {
-        int64_t zz = (int64_t)nlm_reflect_i(a.offz + q, a.Gz) - a.offz;
+        int64_t zz = (int64_t)reflect_once<int>(a.offz + q, a.Gz) - a.offz;
         return zz < 0 ? (int64_t)0 : (zz >= a.N2 ? a.N2 - 1 : zz);
     };
 
@@ -1155,15 +1142,6 @@ __global__ void __launch_bounds__(256) nlmeans_patch_kernel(const NlmTiledArgs a
 // Pixels whose weights all vanish in float32 are recomputed exactly as in nlmeans_patch_kernel.
 typedef float f2_t __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float dpp_from_prev(float x)      // lane i <- lane i - 1 (lane 0 <- 0)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x138, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float dpp_from_next(float x)      // lane i <- lane i + 1 (lane 63 <- 0)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x130, 0xF, 0xF, true));
-}
-
 template <int V>
 struct Patch2Rows {
     static constexpr int TYW = (V == 1) ? 8 : 4;      // rows per thread
@@ -1192,19 +1170,19 @@ __device__ __forceinline__ f2_t patch2_row_sums(const f2_t e)
     const float P = e.x + e.y;
     f2_t hs;
     if (F == 1) {
-        hs.x = dpp_from_prev(e.y) + P;
-        hs.y = P + dpp_from_next(e.x);
+        hs.x = lane_from_prev(e.y) + P;
+        hs.y = P + lane_from_next(e.x);
     } else if (F == 2) {
-        hs.x = (dpp_from_prev(P) + P) + dpp_from_next(e.x);
-        hs.y = (dpp_from_prev(e.y) + P) + dpp_from_next(P);
+        hs.x = (lane_from_prev(P) + P) + lane_from_next(e.x);
+        hs.y = (lane_from_prev(e.y) + P) + lane_from_next(P);
     } else {
         // columns 2l-3 .. 2l+3 and 2l-2 .. 2l+4 out of three-column pieces, every step one addition
         // with a wave-shifted operand (v_add_f32_dpp; fetching e(2l-3) and e(2l+4) by themselves
         // takes two shifts each):  T(l) = e(2l-1) + P(l),  U(l) = P(l) + e(2l+2)
-        const float T = dpp_from_prev(e.y) + P;
-        const float U = P + dpp_from_next(e.x);
-        hs.x = (dpp_from_prev(T) + P) + dpp_from_next(P);
-        hs.y = (dpp_from_prev(P) + P) + dpp_from_next(U);
+        const float T = lane_from_prev(e.y) + P;
+        const float U = P + lane_from_next(e.x);
+        hs.x = (lane_from_prev(T) + P) + lane_from_next(P);
+        hs.y = (lane_from_prev(P) + P) + lane_from_next(U);
     }
     return hs;
 }
@@ -1565,8 +1543,8 @@ __device__ __forceinline__ float nlm_row_sum_lanes(const float e)
     float acc = e, up = e, dn = e;
 #pragma unroll
     for (int j = 0; j < F; ++j) {
-        up = dpp_from_prev(up);
-        dn = dpp_from_next(dn);
+        up = lane_from_prev(up);
+        dn = lane_from_next(dn);
         acc = (acc + up) + dn;
     }
     return acc;
@@ -1604,7 +1582,7 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
 
     bool nonfinite_here = false;
     for (int pz = 0; pz < np; ++pz) {
-        int zi = nlm_reflect_i(a.offz + i2 - (rz + FZ) + pz, a.Gz) - (int)a.offz;
+        int zi = reflect_once<int>(a.offz + i2 - (rz + FZ) + pz, a.Gz) - (int)a.offz;
         zi = zi < 0 ? 0 : (zi >= (int)a.N2 ? (int)a.N2 - 1 : zi);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
@@ -1681,10 +1659,10 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
                             for (int j = 0; j < F; ++j) {
                                 const unsigned long long ub = __builtin_bit_cast(unsigned long long, up);
                                 const unsigned long long db = __builtin_bit_cast(unsigned long long, dn);
-                                const unsigned ulo = __builtin_bit_cast(unsigned, dpp_from_prev(__builtin_bit_cast(float, (unsigned)ub)));
-                                const unsigned uhi = __builtin_bit_cast(unsigned, dpp_from_prev(__builtin_bit_cast(float, (unsigned)(ub >> 32))));
-                                const unsigned dlo = __builtin_bit_cast(unsigned, dpp_from_next(__builtin_bit_cast(float, (unsigned)db)));
-                                const unsigned dhi = __builtin_bit_cast(unsigned, dpp_from_next(__builtin_bit_cast(float, (unsigned)(db >> 32))));
+                                const unsigned ulo = __builtin_bit_cast(unsigned, lane_from_prev(__builtin_bit_cast(float, (unsigned)ub)));
+                                const unsigned uhi = __builtin_bit_cast(unsigned, lane_from_prev(__builtin_bit_cast(float, (unsigned)(ub >> 32))));
+                                const unsigned dlo = __builtin_bit_cast(unsigned, lane_from_next(__builtin_bit_cast(float, (unsigned)db)));
+                                const unsigned dhi = __builtin_bit_cast(unsigned, lane_from_next(__builtin_bit_cast(float, (unsigned)(db >> 32))));
                                 up = __builtin_bit_cast(double, ((unsigned long long)uhi << 32) | ulo);
                                 dn = __builtin_bit_cast(double, ((unsigned long long)dhi << 32) | dlo);
                                 acc = (acc + up) + dn;

@@ -4,6 +4,7 @@
 // 2.69 against 2.04 ms -- its rows above and below a wave's pair double the bytes staged through
 // L2 -> LDS, and LDS-DMA ingest tops out near 6 - 7 TB/s chip-wide, tools/probe_tiles.hip).
 #pragma once
+#include "borders.hpp"   // ml_reflect
 #include "omnibus_c2_device.hpp"
 
 namespace nd_amd {
@@ -22,19 +23,6 @@ struct OmniMlArgs {
     unsigned long long *trace;   // (unused: the time stamps of round 5's diagnostic builds.  The two fields stay
     int trace_block;             //  so that the kernel's argument layout, and with it its code, does not move)
 };
-
-__device__ __forceinline__ int ml_reflect(int cc, const int len)     // scipy 'reflect': d c b a | a b c d | d c b a
-{
-    if (cc >= 0 && cc < len) return cc;
-    const int sz2 = 2 * len;
-    // (no division: the columns asked for lie within a tile of the raster, the loops run at most a
-    //  few times, and only for rasters narrower than a tile)
-    while (cc < -len) cc += sz2;
-    while (cc >= sz2) cc -= sz2;
-    if (cc < 0) return -cc - 1;
-    if (cc >= len) return sz2 - cc - 1;
-    return cc;
-}
 
 // The rows of the change map of `n` consecutive pixels, lanes lo .. lo + n - 1 of the wave, from the
 // lanes' masks: through a wave-private LDS image (k / 4 words per lane), then 16-byte pieces of

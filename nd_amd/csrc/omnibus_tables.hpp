@@ -165,6 +165,4 @@ static StreamScreen<NJ> make_stream_screen(const std::vector<OmniTabEntry> &tab,
     return s;
 }
 
-static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace nd_amd

@@ -47,7 +47,6 @@ constexpr int RG_SCAN = 1024;                       // pixels of a block of the 
 constexpr int RG_PX = 256;                          // pixels of a block of the seam / write passes
 constexpr int32_t RG_BG = INT_MIN;                  // the parent of a background pixel
 constexpr int64_t RG_MAX_BLOCKS = ((int64_t)1 << 31) - 1;
-constexpr size_t RG_ALIGN = 256;
 
 struct RgArgs {
     const void *src;
@@ -457,8 +456,6 @@ __global__ __launch_bounds__(RG_PX) void regions_sizes_kernel(const int32_t *lab
 }
 
 // ---- host
-size_t rg_round(size_t n) { return (n + RG_ALIGN - 1) / RG_ALIGN * RG_ALIGN; }
-
 struct RgPlan {
     size_t parent_off, cnt_off, sums_off, bytes;
     int64_t scan_blocks;                            // per plane
@@ -467,12 +464,12 @@ struct RgPlan {
 RgPlan rg_plan(int64_t nplanes, int64_t ny, int64_t nx, bool sizes)
 {
     RgPlan p;
-    const size_t plane = rg_round((size_t)nplanes * (size_t)ny * (size_t)nx * sizeof(int32_t));
+    const size_t plane = align256((size_t)nplanes * (size_t)ny * (size_t)nx * sizeof(int32_t));
     p.scan_blocks = ceil_div(ny * nx, RG_SCAN);
-    p.parent_off = RG_ALIGN;                        // the give-up word comes first
+    p.parent_off = align256(sizeof(int32_t));       // the give-up word comes first
     p.cnt_off = p.parent_off + plane;
     p.sums_off = p.cnt_off + (sizes ? plane : 0);
-    p.bytes = p.sums_off + rg_round((size_t)nplanes * (size_t)p.scan_blocks * sizeof(int32_t));
+    p.bytes = p.sums_off + align256((size_t)nplanes * (size_t)p.scan_blocks * sizeof(int32_t));
     return p;
 }
 

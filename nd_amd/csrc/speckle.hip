@@ -20,6 +20,7 @@
 // Both forms do the same operations in the same order on every pixel, so they give the same bits.
 // Strides are arbitrary (in elements), so crops and (y, x, time) data are read where they lie; the latter without
 // coalescing: the filter classes bring such data to the planar layout first (kernels.relayout_planar).
+#include "borders.hpp"
 #include "common.hpp"
 #include "dispatch.hpp"
 
@@ -51,16 +52,6 @@ struct SpArgs {
     int w, nvar;
     double n, cu2, kuan, count;                     // w * w, 1 / looks, 1 + cu2, k * C
 };
-
-// scipy's 'reflect' (half-sample symmetric), periodic so that windows larger than the plane are defined
-__device__ __forceinline__ int64_t sp_refl(int64_t i, int64_t n)
-{
-    if ((uint64_t)i < (uint64_t)n) return i;
-    const int64_t m = 2 * n;
-    int64_t p = i % m;
-    if (p < 0) p += m;
-    return p < n ? p : m - 1 - p;
-}
 
 // a variable's base pointer by a select chain: the argument struct is never indexed at run time
 template <class T>
@@ -111,11 +102,11 @@ __device__ __forceinline__ void sp_row_sums(const T *plane, int64_t sy, int64_t 
     const int lane = threadIdx.x, wave = threadIdx.y;
     const int rows = live + 2 * R;
     // the lane's two staged columns (sw <= 64 + 30 < 128)
-    const int64_t c0 = sp_refl(x0 - R + lane, nx) * sx;
-    const int64_t c1 = lane + SP_TX < sw ? sp_refl(x0 - R + lane + SP_TX, nx) * sx : 0;
+    const int64_t c0 = reflect_line(x0 - R + lane, nx) * sx;
+    const int64_t c1 = lane + SP_TX < sw ? reflect_line(x0 - R + lane + SP_TX, nx) * sx : 0;
     __syncthreads();
     for (int r = wave; r < rows; r += SP_WAVES) {
-        const T *row = plane + sp_refl(y0 - R + r, ny) * sy;
+        const T *row = plane + reflect_line(y0 - R + r, ny) * sy;
         stage[r * sw + lane] = row[c0];
         if (lane + SP_TX < sw) stage[r * sw + lane + SP_TX] = row[c1];
     }

@@ -174,6 +174,23 @@ def test_tiled_edges_and_tiny_planes(device):
                                               ndi.convolve(a, k, mode=mode))
 
 
+@pytest.mark.parametrize('mode', ['reflect', 'constant', 'nearest', 'mirror', 'wrap'])
+def test_per_element_kernel_on_arrays_smaller_than_the_window(device, mode):
+    """The per-element N-D kernel and its offset-table border rule (extend_index, borders.hpp) far outside the
+    array: float64 arrays of 1 to 3 elements per axis under 3-D windows of up to 13 taps per axis.  Every window
+    reaches at least twice an axis' length beyond it (or holds more taps than the tiled kernel takes), so no tiled
+    form runs.  A radius of 6 on a length of 2 and more stays short of -4 len, where the rule differs from a
+    periodic extension.  Bit-equal to scipy."""
+    import scipy.ndimage as ndi
+    rng = np.random.default_rng(613)
+    for shape in [(1, 1, 1), (2, 2, 3), (3, 3, 2)]:
+        a = rng.normal(size=shape)
+        for kshape in [(5, 8, 13), (13, 5, 8), (8, 13, 3), (13, 3, 3), (13, 13, 13)]:
+            k = rng.normal(size=kshape)
+            np.testing.assert_array_equal(_gpu_convolve(a, k, device, mode=mode, cval=-1.25),
+                                          ndi.convolve(a, k, mode=mode, cval=-1.25), err_msg=str((shape, kshape)))
+
+
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_tiled_kernel_on_both_sides_of_its_size_classes(device, dtype):
     """The tiled kernel's instantiations are picked by width (odd 1 .. 15, then 17 .. 31), by height (up to 5 rows,

@@ -47,6 +47,30 @@ def test_correlate1d_general_kernels(device):
             np.testing.assert_array_equal(out.cpu().numpy(), ndi.correlate1d(a, w, axis=axis))
 
 
+@pytest.mark.parametrize('mode', ['reflect', 'constant', 'nearest', 'mirror', 'wrap'])
+def test_per_element_1d_kernel_on_lines_shorter_than_the_kernel(device, mode):
+    """The per-element correlate1d kernel and its line extension (extend_line, borders.hpp) many periods away from
+    the line: lines of 1, 2 and 3 elements under kernels of 3, 8 and 13 taps, along each axis.  The arrays are views
+    whose last axis is not contiguous, which the tiled kernel does not take.  Bit-equal to scipy."""
+    import torch
+    import scipy.ndimage as ndi
+    from nd_amd import kernels
+    rng = np.random.default_rng(1813)
+    for shape in [(1, 2, 3), (3, 1, 2), (2, 3, 1)]:
+        a = rng.normal(size=shape)
+        wide = torch.zeros(shape[:2] + (2 * shape[2],), dtype=torch.float64, device=device)
+        t = wide[..., ::2]
+        t.copy_(torch.from_numpy(a))
+        assert t.stride(-1) == 2
+        for n in (3, 8, 13):
+            w = rng.normal(size=n)
+            for axis in (0, 1, 2):
+                out = torch.empty_like(wide)[..., ::2]
+                kernels.correlate1d(t, w, axis, out, mode, 0.75)
+                np.testing.assert_array_equal(out.cpu().numpy(), ndi.correlate1d(a, w, axis=axis, mode=mode, cval=0.75),
+                                              err_msg=str((shape, n, axis)))
+
+
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_long_kernels_in_the_tiled_1d_kernel(device, dtype):
     """Kernels of 33 .. 97 taps (round 6: Gaussian sigma > 3.75 took the per-element kernel): sigma 5 / 8 / 12 along
