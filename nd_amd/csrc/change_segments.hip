@@ -34,6 +34,7 @@
 // a wave only reads the image it wrote (LDS operations of a wave complete in order).
 #include "common.hpp"
 #include "dispatch.hpp"
+#include "memops.hpp"
 
 namespace nd_amd {
 
@@ -82,8 +83,6 @@ __device__ __forceinline__ int direction_code(const double (&d)[P])
         return (m1 > 0.0 && m2 > 0.0 && m3 > 0.0) ? 1 : ((m1 < 0.0 && m2 > 0.0 && m3 < 0.0) ? 2 : 3);
     }
 }
-
-__device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // ---- the map bytes of dates [t0, t0 + tc) of the wave's wnp pixels -> one bit per date, per lane -------------
 // wc: the first byte of the wave's rows.  words: k % 4 == 0 and wc 4-byte aligned (then t0 and tc are

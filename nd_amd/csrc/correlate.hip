@@ -19,13 +19,9 @@
 #include "common.hpp"
 #include "dispatch.hpp"
 #include "lanes.hpp"
+#include "memops.hpp"
 
 namespace nd_amd {
-
-// cache policy of the window kernels' 16-byte output stores: 2 = non-temporal (written once, never read
-// back by the kernel; boxcar 3 x 3 / 5 x 5 on 24 x 4096^2: 0.632 / 0.640 -> 0.612 / 0.620 ms, the fused
-// Gaussian unchanged).  Non-temporal LOADS of the rows measured slower (0.611 -> 0.623 ms).
-constexpr int kStoreAux = 2;
 
 constexpr int kTapsArgs = 128;   // taps that travel as a kernel argument
 
@@ -425,12 +421,8 @@ __global__ void __launch_bounds__(256, (K == 3 ? 6 : (K == 5 ? 4 : 2))) correlat
     for (int j = 0; j < H; ++j)
         xe[j] = 4 * extend_index<int, true>((lane < 32 ? xs - H : xs + kRollStrip) + j, nx, a.mode);
     const bool wave_vec = a.vec_in && xs + kRollStrip <= nx;
-    const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in + plane * a.sin_b), 0,
-                                                       0x7fffffff, 0x00020000);
-    const auto rout = __builtin_amdgcn_make_buffer_rsrc(a.out + plane * a.sout_b, 0, 0x7fffffff,
-                                                        0x00020000);
+    const auto rin = buffer_of(a.in + plane * a.sin_b), rout = buffer_of(a.out + plane * a.sout_b);
     typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     struct RowRegs {
         f32x4 v;
         float e[H];
@@ -441,15 +433,15 @@ __global__ void __launch_bounds__(256, (K == 3 ? 6 : (K == 5 ? 4 : 2))) correlat
         const int m = extend_index<int, true>((int)r, (int)a.ny, a.mode);
         const int soff = __builtin_amdgcn_readfirstlane(m * (int)a.sin_y * 4);
         if (wave_vec) {
-            v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, xm[0], soff, 0));
+            v = buffer_load16<f32x4, kAuxDefault>(rin, xm[0], soff);
         } else {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                v[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rin, xm[c], soff, 0));
+                v[c] = buffer_load<float, kAuxDefault>(rin, xm[c], soff);
         }
 #pragma unroll
         for (int j = 0; j < H; ++j)
-            rr.e[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rin, xe[j], soff, 0));
+            rr.e[j] = buffer_load<float, kAuxDefault>(rin, xe[j], soff);
         rr.v = v;
         return rr;
     };
@@ -525,13 +517,13 @@ __global__ void __launch_bounds__(256, (K == 3 ? 6 : (K == 5 ? 4 : 2))) correlat
                     if (writer) {
                         if (store_vec) {
                             const f32x4 o = {(float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]};
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rout, x * 4, ooff, kStoreAux);
+                            buffer_store16<kAuxNt>(rout, x * 4, ooff, o);
                         } else {
 #pragma unroll
                             for (int c = 0; c < 4; ++c)
-                                if (x + c < nx)
+                                if (x + c < nx)      // (written out: through buffer_store the 3 x 3 and 5 x 5 kernels move)
                                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[c]), rout,
-                                                                          (x + c) * 4, ooff, 0);
+                                                                          (x + c) * 4, ooff, kAuxDefault);
                         }
                     }
                 }
@@ -1262,39 +1254,22 @@ __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs
     for (int c = 0; c < 4; ++c) xm[c] = ES * extend_line<int, true>(x + c, nx, a.mode);
     const bool inside = x >= 0 && x + 3 < nx;
     const bool wave_vec = a.vec_in && __builtin_amdgcn_ballot_w64(!inside) == 0ull;
-    const auto rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(a.in + plane * a.sin_b), 0,
-                                                       0x7fffffff, 0x00020000);
-    const auto rout = __builtin_amdgcn_make_buffer_rsrc(a.out + plane * a.sout_b, 0, 0x7fffffff,
-                                                        0x00020000);
+    const auto rin = buffer_of(a.in + plane * a.sin_b), rout = buffer_of(a.out + plane * a.sout_b);
     typedef T f32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     typedef double f64x2 __attribute__((ext_vector_type(2)));
     auto load_row = [&](int t) -> f32x4 {            // input row of step t: ys - R + t
         const int m = extend_line<int, true>(ys - R + t, ny, a.mode);
         const int soff = __builtin_amdgcn_readfirstlane(m * (int)a.sin_y * ES);
         f32x4 v;
-        if constexpr (sizeof(T) == 4) {
-            if (wave_vec) {
-                v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, xm[0], soff, 0));
-            } else {
+        if (!wave_vec) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    v[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rin, xm[c], soff, 0));
-            }
+            for (int c = 0; c < 4; ++c) v[c] = buffer_load<T, kAuxDefault>(rin, xm[c], soff);
+        } else if constexpr (sizeof(T) == 4) {
+            v = buffer_load16<f32x4, kAuxDefault>(rin, xm[0], soff);
         } else {
-            if (wave_vec) {
-                const f64x2 lo = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(rin, xm[0], soff, 0));
-                const f64x2 hi = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(rin, xm[0] + 16, soff, 0));
-                v[0] = lo[0];
-                v[1] = lo[1];
-                v[2] = hi[0];
-                v[3] = hi[1];
-            } else {
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    v[c] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rin, xm[c], soff, 0));
-            }
+            const f64x2 lo = buffer_load16<f64x2, kAuxDefault>(rin, xm[0], soff);
+            const f64x2 hi = buffer_load16<f64x2, kAuxDefault>(rin, xm[0] + 16, soff);
+            v = {lo[0], lo[1], hi[0], hi[1]};
         }
         return v;
     };
@@ -1378,29 +1353,17 @@ __global__ void __launch_bounds__(256) correlate1d_yx_kernel(const Corr2PassArgs
                     const int y = ys + t - 2 * R;
                     const int ooff = __builtin_amdgcn_readfirstlane(y * (int)a.sout_y * ES);
                     if (writer) {
-                        if constexpr (sizeof(T) == 4) {
-                            if (store_vec) {
-                                const f32x4 o4 = {res[0], res[1], res[2], res[3]};
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o4), rout, x * 4, ooff, kStoreAux);
-                            } else {
+                        if (!store_vec) {
 #pragma unroll
-                                for (int c = 0; c < 4; ++c)
-                                    if (x + c < nx)
-                                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, res[c]), rout,
-                                                                              (x + c) * 4, ooff, 0);
-                            }
+                            for (int c = 0; c < 4; ++c)
+                                if (x + c < nx) buffer_store<kAuxDefault>(rout, (x + c) * ES, ooff, res[c]);
+                        } else if constexpr (sizeof(T) == 4) {
+                            const f32x4 o4 = {res[0], res[1], res[2], res[3]};
+                            buffer_store16<kAuxNt>(rout, x * 4, ooff, o4);
                         } else {
-                            if (store_vec) {
-                                const f64x2 lo = {res[0], res[1]}, hi = {res[2], res[3]};
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), rout, x * 8, ooff, kStoreAux);
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), rout, x * 8 + 16, ooff, kStoreAux);
-                            } else {
-#pragma unroll
-                                for (int c = 0; c < 4; ++c)
-                                    if (x + c < nx)
-                                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, res[c]), rout,
-                                                                              (x + c) * 8, ooff, 0);
-                            }
+                            const f64x2 lo = {res[0], res[1]}, hi = {res[2], res[3]};
+                            buffer_store16<kAuxNt>(rout, x * 8, ooff, lo);
+                            buffer_store16<kAuxNt>(rout, x * 8 + 16, ooff, hi);
                         }
                     }
                 }

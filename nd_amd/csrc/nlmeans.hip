@@ -27,6 +27,7 @@
 #include "common.hpp"
 #include "dispatch.hpp"
 #include "lanes.hpp"
+#include "memops.hpp"
 
 namespace nd_amd {
 
@@ -679,8 +680,7 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
     const float *base = a.arr + (int64_t)v * a.si3;
 
     auto stage = [&](int64_t p, int slot) {
-        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base + p * a.si2), 0,
-                                                            0x7fffffff, 0x00020000);
+        const auto rsrc = buffer_of(base + p * a.si2);
         nlm_lds_f32 *dst = (nlm_lds_f32 *)(slots + slot * PSZ + wave * COLSP);
 #pragma unroll
         for (int u = 0; u < NPRE; ++u) {
@@ -700,7 +700,7 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
     const int64_t first = a.clo2, last = a.chi2 - 1;
     const int nsteps = (int)(last - first) + 3;
     stage(zmap(first - 1), 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_dma_wait();
     __syncthreads();
 
     const bool vec_ok = ((((uintptr_t)a.out) & 15) == 0) && ((a.so0 | a.so2 | a.so3 | x0) & 3) == 0;
@@ -847,7 +847,7 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
         }
         // the next plane has landed (this wave's transfers) and every wave is done with this one
         if (!same) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            lds_dma_wait();
             __syncthreads();
             slot ^= 1;
         }

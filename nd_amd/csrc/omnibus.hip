@@ -336,9 +336,9 @@ omnibus_c2_retain_wsearch_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, c
     const int rank = __popcll(m & ((1ull << lane) - 1ull));
     if (flag) dump_series<T, KMAX, EXACT>(img + rank * (KMAX * 4), v, k);
     for (int w = lane; w < kWaveSearchMax * KMAX / 4; w += 64) rows_w[w] = 0u;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // same wave: LDS operations complete in order
+    wave_lds_fence();                                      // same wave: LDS operations complete in order
     wave_search_starts<T, KMAX>(img, rows, nc, k, g.nlooks, g.alpha, fscr.e, tab.e, lane);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
     unsigned mask = 0u;
     if (flag) {
 #pragma unroll
@@ -919,15 +919,15 @@ omnibus_c2_pm_dma_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
         const int bytes = np * wpp * (int)sizeof(T);        // a multiple of 16 for whole spans of 64 pixels
         const unsigned char *src = reinterpret_cast<const unsigned char *>(base + px0 * wpp);
         unsigned char *dst = reinterpret_cast<unsigned char *>(img + pm.img_off[vi]);
-        const int bytes16 = bytes & ~15;
-        for (int c0 = 0; c0 < bytes16; c0 += 1024) {
-            const int eb = c0 + lane * 16;
-            if (eb < bytes16)
-                __builtin_amdgcn_global_load_lds((glb_u8_t *)(src + eb), (lds_u8_t *)(dst + c0), 16, 0, kNtAux);
+        for (int c0 = 0; c0 < lds_run_whole<true>(bytes); c0 += kLdsStep) {
+            const LdsPiece p = lds_stage_piece<true>(bytes, c0, lane);
+            if (p.width) lds_dma16<kAuxNt>(src + p.src(), dst + p.base);
         }
         // (the last span of a variable whose series length is not a multiple of the vector: up to three words more)
-        if (bytes16 < bytes && bytes16 + lane * 4 < bytes)
-            __builtin_amdgcn_global_load_lds((glb_u8_t *)(src + bytes16 + lane * 4), (lds_u8_t *)(dst + bytes16), 4, 0, kNtAux);
+        if (lds_run_whole<true>(bytes) < bytes) {
+            const LdsPiece p = lds_stage_tail(bytes, lane);
+            if (p.width) lds_dma4<kAuxNt>(src + p.base + p.off, dst + p.base);
+        }
     };
     if (!DIRECT) {
         stage(g.c11, 0);
@@ -965,7 +965,7 @@ omnibus_c2_pm_dma_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
 #pragma unroll
         for (int u = 0; u < KMAX / VE; ++u) asm volatile("" : "+v"(qa[u]), "+v"(qd[u]));
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_dma_wait();
 
     // ---- this lane's series out of the images (idle lanes copy the last pixel) ----
     T v[KMAX][4];
@@ -1081,10 +1081,9 @@ __global__ void __launch_bounds__(64) omnibus_c2_pm_long_kernel(const OmniGlobal
         const int bytes = np * wpp * (int)sizeof(T);        // multiple of 16 (host checks k)
         const unsigned char *src = reinterpret_cast<const unsigned char *>(base + px0 * wpp);
         unsigned char *dst = reinterpret_cast<unsigned char *>(img + pm.img_off[vi]);
-        for (int c0 = 0; c0 < bytes; c0 += 1024) {
-            const int eb = c0 + lane * 16;
-            if (eb < bytes)
-                __builtin_amdgcn_global_load_lds((glb_u8_t *)(src + eb), (lds_u8_t *)(dst + c0), 16, 0, kNtAux);
+        for (int c0 = 0; c0 < bytes; c0 += kLdsStep) {
+            const LdsPiece p = lds_stage_piece<false>(bytes, c0, lane);
+            if (p.width) lds_dma16<kAuxNt>(src + p.src(), dst + p.base);
         }
     };
     stage(g.c11, 0);
@@ -1094,7 +1093,7 @@ __global__ void __launch_bounds__(64) omnibus_c2_pm_long_kernel(const OmniGlobal
     if (g.write_tab && b == 0) {
         for (int j = lane; j <= k; j += 64) g.tab_dev[j] = tab.e[j];
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_dma_wait();
 
     // ---- fold this lane's series in time order (idle lanes fold the last pixel of the span) ----
     const int own = (lane < np) ? lane : np - 1;
@@ -1294,19 +1293,11 @@ omnibus_c2_chain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Stre
     if (EXACT) {
         const int64_t ub = row * g.sy + bpx0;
         const unsigned lx = in ? (unsigned)tid : (unsigned)(g.nx - 1 - bpx0);   // idle lanes re-read the last pixel
-        const unsigned voff = lx * (unsigned)sizeof(T);
-        const auto r11 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c11 + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r12r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12r + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r12i = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12i + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r22 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c22 + ub), 0, 0x7fffffff, 0x00020000);
-        const unsigned sstep = (unsigned)g.st * (unsigned)sizeof(T);   // host guarantees k * st * sizeof(T) < 2^31
+        const PlaneBuffers pb = plane_buffers(g.c11, g.c12r, g.c12i, g.c22, ub, lx, g.st);
 #pragma unroll
         for (int t = 0; t < KMAX; ++t) {
-            const unsigned soff = (unsigned)t * sstep;
-            v[t][0] = buffer_load<T>(r11, voff, soff);
-            v[t][1] = buffer_load<T>(r12r, voff, soff);
-            v[t][2] = buffer_load<T>(r12i, voff, soff);
-            v[t][3] = buffer_load<T>(r22, voff, soff);
+            const unsigned soff = (unsigned)t * pb.sstep;
+            pb.load(pb.voff, soff, v[t][0], v[t][1], v[t][2], v[t][3]);
         }
     } else {
         const int64_t xc = in ? x0 : g.nx - 1;
@@ -1449,8 +1440,7 @@ struct DateVal {
 // groups of dates: the re-reads are L2 hits) -- no LDS, the occupancy of the planar form
 template <typename T, int MODE>
 struct PlaneReader {
-    __amdgpu_buffer_rsrc_t r11, r12r, r12i, r22;
-    unsigned voff, sstep;
+    PlaneBuffers pb;                       // MODE 1
     const T *p11, *p12r, *p12i, *p22;      // MODE 2 / 3: this lane's series inside each image / variable
     int64_t st;
     int i11, i12, i22, joint;              // MODE 2 / 3: date strides
@@ -1458,11 +1448,8 @@ struct PlaneReader {
     {
         DateVal<T> q;
         if (MODE == 1) {
-            const unsigned soff = (unsigned)t * sstep;
-            q.a = buffer_load<T>(r11, voff, soff);
-            q.b = buffer_load<T>(r12r, voff, soff);
-            q.c = buffer_load<T>(r12i, voff, soff);
-            q.d = buffer_load<T>(r22, voff, soff);
+            const unsigned soff = (unsigned)t * pb.sstep;
+            pb.load(pb.voff, soff, q.a, q.b, q.c, q.d);
         } else if (MODE >= 2) {
             q.a = p11[t * i11];
             q.d = p22[t * i22];
@@ -1488,11 +1475,8 @@ struct PlaneReader {
     {
         if (MODE == 1) {
             DateVal<T> q;
-            const unsigned vo = voff + (unsigned)t * sstep;
-            q.a = buffer_load<T>(r11, vo, 0u);
-            q.b = buffer_load<T>(r12r, vo, 0u);
-            q.c = buffer_load<T>(r12i, vo, 0u);
-            q.d = buffer_load<T>(r22, vo, 0u);
+            const unsigned vo = pb.voff + (unsigned)t * pb.sstep;
+            pb.load(vo, 0u, q.a, q.b, q.c, q.d);
             return q;
         }
         return load(t);
@@ -1574,10 +1558,9 @@ omnibus_c2_stream_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
             const int bytes = np * wpp * (int)sizeof(T);
             const unsigned char *src = reinterpret_cast<const unsigned char *>(base + bpx0 * wpp);
             unsigned char *dst = reinterpret_cast<unsigned char *>(img + pm.img_off[vi]);
-            for (int c0 = 0; c0 < bytes; c0 += 1024) {
-                const int eb = c0 + lane * 16;
-                if (eb < bytes)
-                    __builtin_amdgcn_global_load_lds((glb_u8_t *)(src + eb), (lds_u8_t *)(dst + c0), 16, 0, kNtAux);
+            for (int c0 = 0; c0 < bytes; c0 += kLdsStep) {
+                const LdsPiece p = lds_stage_piece<false>(bytes, c0, lane);
+                if (p.width) lds_dma16<kAuxNt>(src + p.src(), dst + p.base);
             }
         };
         stage(g.c11, 0);
@@ -1593,7 +1576,7 @@ omnibus_c2_stream_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
         rd.p22 = img + pm.img_off[3] + own * k * pm.ids[3];
         rd.p12r = img + pm.img_off[1] + own * k * pm.ids[1];
         rd.p12i = pm.c12_joint ? rd.p12r + 1 : img + pm.img_off[2] + own * k * pm.ids[2];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        lds_dma_wait();
     } else if (MODE >= 3) {
         const int64_t xc = in ? x0 : g.nx - 1;                  // idle lanes re-read the last pixel
         rd.i11 = pm.ids[0];
@@ -1608,12 +1591,7 @@ omnibus_c2_stream_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, const Omn
         const int64_t xc = in ? x0 : g.nx - 1;                  // idle lanes re-read the last pixel
         if (MODE == 1) {
             const int64_t ub = row * g.sy + bpx0;
-            rd.voff = (unsigned)(xc - bpx0) * (unsigned)sizeof(T);
-            rd.r11 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c11 + ub), 0, 0x7fffffff, 0x00020000);
-            rd.r12r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12r + ub), 0, 0x7fffffff, 0x00020000);
-            rd.r12i = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12i + ub), 0, 0x7fffffff, 0x00020000);
-            rd.r22 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c22 + ub), 0, 0x7fffffff, 0x00020000);
-            rd.sstep = (unsigned)g.st * (unsigned)sizeof(T);   // host guarantees k * st * sizeof(T) < 2^31
+            rd.pb = plane_buffers(g.c11, g.c12r, g.c12i, g.c22, ub, (unsigned)(xc - bpx0), g.st);
         } else {
             const int64_t off0 = row * g.sy + xc * g.sx;
             rd.p11 = g.c11 + off0;
@@ -2136,12 +2114,7 @@ omnibus_c2_stream_chain_kernel(const OmniGlobalArgs<T> g, const OmniTab tab, con
         const int64_t xc = in ? x0 : g.nx - 1;                  // idle lanes re-read the last pixel
         if (MODE == 1) {
             const int64_t ub = row * g.sy + bpx0;
-            rd.voff = (unsigned)(xc - bpx0) * (unsigned)sizeof(T);
-            rd.r11 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c11 + ub), 0, 0x7fffffff, 0x00020000);
-            rd.r12r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12r + ub), 0, 0x7fffffff, 0x00020000);
-            rd.r12i = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12i + ub), 0, 0x7fffffff, 0x00020000);
-            rd.r22 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c22 + ub), 0, 0x7fffffff, 0x00020000);
-            rd.sstep = (unsigned)g.st * (unsigned)sizeof(T);
+            rd.pb = plane_buffers(g.c11, g.c12r, g.c12i, g.c22, ub, (unsigned)(xc - bpx0), g.st);
         } else {
             const int64_t off0 = row * g.sy + xc * g.sx;
             rd.p11 = g.c11 + off0;

@@ -23,32 +23,6 @@ __device__ __forceinline__ double z_approx(const Accum<T> &A, int j, double nloo
     return z_approx(A, j, nlooks, e.m2rho, e.pklogk);
 }
 
-// The input planes are read exactly once and the change map is written once: both bypass the
-// cache hierarchy's retention ("nt" = aux bit 1 on gfx950 buffer ops, __builtin_nontemporal_* on
-// plain accesses).  Measured on pass A: 1.30 -> 1.14 ms (profiles/r01_probe_bandwidth.txt).
-constexpr int kNtAux = 2;
-
-// raw buffer load of one element: descriptor (SGPRs) + lane byte offset + scalar byte offset
-template <typename T>
-__device__ __forceinline__ T buffer_load(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff);
-template <>
-__device__ __forceinline__ float buffer_load<float>(__amdgpu_buffer_rsrc_t rsrc, unsigned voff,
-                                                    unsigned soff)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, voff, soff, kNtAux));
-}
-template <>
-__device__ __forceinline__ double buffer_load<double>(__amdgpu_buffer_rsrc_t rsrc, unsigned voff,
-                                                      unsigned soff)
-{
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsrc, voff, soff, kNtAux));
-}
-
-template <typename T, int N>
-struct alignas(sizeof(T) * N) Pack {
-    T v[N];
-};
-
 // A series held in registers goes to its slot d of the dump ([date][4]): one 16-byte store per date.
 // EXACT: k == KMAX.
 template <typename T, int KMAX, bool EXACT>
@@ -135,19 +109,11 @@ __device__ __forceinline__ void retain_load_series(const OmniGlobalArgs<T> &g, c
     if (EXACT) {
         const int64_t ub = row * g.sy + bpx0;
         const unsigned lx = in ? (unsigned)tid : (unsigned)(g.nx - 1 - bpx0);   // idle lanes re-read the last pixel
-        const unsigned voff = lx * (unsigned)sizeof(T);
-        const auto r11 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c11 + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r12r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12r + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r12i = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c12i + ub), 0, 0x7fffffff, 0x00020000);
-        const auto r22 = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(g.c22 + ub), 0, 0x7fffffff, 0x00020000);
-        const unsigned sstep = (unsigned)g.st * (unsigned)sizeof(T);   // host guarantees k * st * sizeof(T) < 2^31
+        const PlaneBuffers pb = plane_buffers(g.c11, g.c12r, g.c12i, g.c22, ub, lx, g.st);
 #pragma unroll
         for (int t = 0; t < KMAX; ++t) {
-            const unsigned soff = (unsigned)t * sstep;
-            v[t][0] = buffer_load<T>(r11, voff, soff);
-            v[t][1] = buffer_load<T>(r12r, voff, soff);
-            v[t][2] = buffer_load<T>(r12i, voff, soff);
-            v[t][3] = buffer_load<T>(r22, voff, soff);
+            const unsigned soff = (unsigned)t * pb.sstep;
+            pb.load(pb.voff, soff, v[t][0], v[t][1], v[t][2], v[t][3]);
         }
     } else {
         const int64_t xc = in ? bpx0 + tid : g.nx - 1;
@@ -231,9 +197,6 @@ __device__ __forceinline__ void wave_search_starts(const T *img, uint8_t *rows, 
     }
 }
 
-
-typedef __attribute__((address_space(3))) unsigned char lds_u8_t;
-typedef __attribute__((address_space(1))) const unsigned char glb_u8_t;
 
 // (series of up to 96 registers: three waves per SIMD; beyond -- 32 float32 / 16 float64 dates and
 // more -- two: under the cap of three the search spilled 150 - 230 bytes per lane)

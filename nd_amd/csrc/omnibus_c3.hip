@@ -345,10 +345,6 @@ __global__ void __launch_bounds__(64 * kC3Slices) omnibus_c3_retain_kernel(const
 // waves per CU do not hide the one behind the other; four lanes per pixel sharing a date's determinant through
 // quad broadcasts, 33 instead of 70 instructions per date on all 64 lanes, measured the same: 3.3 - 3.55 ms).
 // JOINT: C12, C13, C23 are interleaved complex arrays (re at the even places); otherwise nine real ones.
-template <typename T, int N>
-struct alignas(sizeof(T) * N) C3Pack {
-    T v[N];
-};
 struct C3PmArgs {
     int img_off[9];           // element offset of each plane's image in the wave's LDS region
 };
@@ -357,8 +353,6 @@ template <typename T, int PXW, bool STATS, bool JOINT>
 __global__ void __launch_bounds__(64) omnibus_c3_pm_kernel(const C3Args<T> g, const OmniTab tab, const C3PmArgs pm)
 {
     constexpr int VE = 16 / (int)sizeof(T);
-    typedef __attribute__((address_space(1))) unsigned char glb_u8;
-    typedef __attribute__((address_space(3))) unsigned char lds_u8;
     extern __shared__ __align__(16) unsigned char nd_smem3pm[];
     T *img = reinterpret_cast<T *>(nd_smem3pm);
     const int lane = threadIdx.x;
@@ -376,9 +370,9 @@ __global__ void __launch_bounds__(64) omnibus_c3_pm_kernel(const C3Args<T> g, co
         const int bytes = np * wpp * (int)sizeof(T);        // multiple of 16 (host checks k)
         const unsigned char *src = reinterpret_cast<const unsigned char *>(g.pl[c] + px0 * wpp);
         unsigned char *dst = reinterpret_cast<unsigned char *>(img + pm.img_off[c]);
-        for (int c0 = 0; c0 < bytes; c0 += 1024) {
-            const int eb = c0 + lane * 16;
-            if (eb < bytes) __builtin_amdgcn_global_load_lds((glb_u8 *)(src + eb), (lds_u8 *)(dst + c0), 16, 0, 2);
+        for (int c0 = 0; c0 < bytes; c0 += kLdsStep) {
+            const LdsPiece p = lds_stage_piece<false>(bytes, c0, lane);
+            if (p.width) lds_dma16<kAuxNt>(src + p.src(), dst + p.base);
         }
     };
     stage(0, 1);
@@ -394,9 +388,9 @@ __global__ void __launch_bounds__(64) omnibus_c3_pm_kernel(const C3Args<T> g, co
     }
     if (g.write_tab && b == 0)
         for (int j = lane; j <= k; j += 64) g.tab_dev[j] = tab.e[j];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_dma_wait();
 
-    typedef C3Pack<T, VE> PV;
+    typedef Pack<T, VE> PV;
     Accum3<T> A;
     A.reset();
     const int nv = k / VE;
@@ -1179,7 +1173,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_kernel(const C3Args<T> s
             // 16-byte loads, the whole series of a lane in flight group by group: 108 (real planes) or 72 + 36
             // loads of 16 bytes instead of 432 of 4 -- the sectors are the same, the requests a quarter.
             constexpr int VE = 16 / (int)sizeof(T);
-            typedef C3Pack<T, VE> PV;
+            typedef Pack<T, VE> PV;
             const bool joint = s.mult[3] == 2;
             for (int t0 = 0; t0 < k; t0 += 2 * VE) {
                 PV q[9][2];
@@ -1343,7 +1337,7 @@ __global__ void __launch_bounds__(64) omnibus_c3_search_dump_kernel(const C3Args
     constexpr int VE = 16 / (int)sizeof(T);              // values per 16-byte piece
     constexpr int CD = 4;                                // dates per chunk
     constexpr int NV = CD * 9 / VE;                      // pieces per chunk
-    typedef C3Pack<T, VE> PV;
+    typedef Pack<T, VE> PV;
     extern __shared__ __align__(16) unsigned char nd_smem3d[];
     const int lane = threadIdx.x;
     const int k = s.k;

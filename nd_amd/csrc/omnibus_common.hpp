@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "memops.hpp"
 #include "omnibus_tables.hpp"
 
 namespace nd_amd {
@@ -426,12 +427,12 @@ __device__ __forceinline__ void store_change_rows_wave(uint8_t *wob, uint32_t *i
     const int kq = k >> 2;
     for (int q = 0; q < kq; ++q)
         img[lane * kq + q] = (mask_nibble(mask, q) * 0x00204081u) & 0x01010101u;     // bit i -> byte i
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // same wave: LDS operations complete in order
+    wave_lds_fence();
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     const u4 *src = reinterpret_cast<const u4 *>(img);
     u4 *dst = reinterpret_cast<u4 *>(wob);
     for (int c = lane; c < 4 * k; c += 64) __builtin_nontemporal_store(src[c], dst + c);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the image may be written again behind this
+    wave_lds_fence();                                      // the image may be written again behind this
 }
 __device__ __forceinline__ bool change_rows_wave_ok(const uint8_t *wob, const int k, const int wnp)
 {

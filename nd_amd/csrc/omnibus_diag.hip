@@ -328,7 +328,7 @@ __global__ void __launch_bounds__(kDgThreads) omnibus_diag_fused_kernel(const Di
     const int64_t wleft = g.nx - wpx0;
     const int wnp = wleft > 64 ? 64 : (wleft > 0 ? (int)wleft : 0);
     uint8_t *wob = g.change + (row * g.nx + wpx0) * (int64_t)k;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
     if (change_rows_wave_ok(wob, k, wnp)) {
         store_change_rows_wave(wob, reinterpret_cast<uint32_t *>(ser), k, mask, lane);
     } else if (in) {

@@ -139,6 +139,10 @@ __device__ __forceinline__ void ml_dma4x4(const ml_v4i rsrc, const unsigned m0, 
                    "s"(o3), "n"(256 * R), "n"(256 * (R + 1)), "n"(256 * (R + 2)), "n"(256 * (R + 3))
                  : "memory");
 }
+// The descriptor of the assembly transfers.  Word by word it is buffer_of(p) (memops.hpp): base address low, base
+// address high with stride 0, 0x7fffffff bytes, 0x00020000.  It stays written out because an "s" operand of inline
+// assembly takes four integers, and the compiler's descriptor type (__amdgpu_buffer_rsrc_t) is opaque: it can be
+// neither an assembly operand nor the source of a bit cast.  The two readfirstlane say that the address is uniform.
 __device__ __forceinline__ ml_v4i ml_make_rsrc(const float *p)
 {
     const uint64_t a = (uint64_t)(uintptr_t)p;

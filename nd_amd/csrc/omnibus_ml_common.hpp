@@ -35,7 +35,7 @@ __device__ __forceinline__ void ml_store_change_rows(uint8_t *ob, uint32_t *img,
     const int kq = k >> 2;
     for (int q = 0; q < kq; ++q)
         img[lane * kq + q] = (mask_nibble(mask, q) * 0x00204081u) & 0x01010101u;     // bit i -> byte i
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
     const uint32_t *src = img + lo * kq;
     uint32_t *dst = reinterpret_cast<uint32_t *>(ob);
     const int nw = n * kq;                                       // words to write
@@ -51,7 +51,7 @@ __device__ __forceinline__ void ml_store_change_rows(uint8_t *ob, uint32_t *img,
     }
     const int tail0 = head + 4 * nvec;
     if (tail0 + lane < nw) dst[tail0 + lane] = src[tail0 + lane];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wave_lds_fence();
 }
 
 

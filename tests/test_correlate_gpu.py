@@ -318,3 +318,23 @@ def test_even_widths_and_constant_mode_in_the_tiled_kernel(device, dtype):
         for k, kw in cases[:2] + cases[4:6]:
             k3 = np.moveaxis(k, 0, -1)
             np.testing.assert_array_equal(_gpu_convolve(b, k3, device, **kw), ndi.convolve(b, k3, **kw))
+
+
+@pytest.mark.parametrize('w', [3, 5, 7])
+def test_register_window_vector_and_scalar_accesses(device, w):
+    """Both sides of the register-window kernel's choices of access (correlate_roll_kernel through memops.hpp), on the
+    smallest planes that take each: 2 x 9 x 256 -- one whole strip per row, 16-byte aligned: one 16-byte load and store
+    per lane; the same tensor without its first column -- the base 4 bytes off: four single loads and stores per lane,
+    the last lane's fourth masked by the row's end; 2 x 9 x 67 -- a ragged strip: mapped single loads, 16-byte stores
+    up to column 63 and a scalar tail of three.  Boxcar and random weights, bit-equal to scipy."""
+    import scipy.ndimage as ndi
+    import torch
+    from nd_amd import kernels
+    rng = np.random.default_rng(71)
+    whole = torch.from_numpy(rng.normal(size=(2, 9, 256)).astype(np.float32)).to(device)
+    ragged = torch.from_numpy(rng.normal(size=(2, 9, 67)).astype(np.float32)).to(device)
+    for k in (np.ones((1, w, w)) / float(w * w), rng.normal(size=(1, w, w))):
+        for t in (whole, whole[..., 1:], ragged):
+            got = kernels.convolve(t, k)
+            torch.cuda.synchronize()
+            np.testing.assert_array_equal(got.cpu().numpy(), ndi.convolve(t.cpu().numpy(), k))

@@ -181,3 +181,22 @@ def test_fused_y_then_x_kernel(device, mode, npdt):
     torch.cuda.synchronize()
     np.testing.assert_array_equal(out.cpu().numpy(),
                                   ndi.gaussian_filter(view.cpu().numpy(), (0, 1, 1), mode=mode))
+
+
+@pytest.mark.parametrize('npdt', [np.float32, np.float64])
+def test_fused_kernel_vector_and_scalar_accesses(device, npdt):
+    """Both sides of the fused y-then-x kernel's choices of access (correlate1d_yx_kernel through memops.hpp) at
+    sigma = 1, on the smallest planes that take each: 2 x 9 x 256 -- aligned rows wider than a wave's strip: 16-byte
+    loads and stores (two per lane in float64) in the inner waves, mapped single loads at the row's ends; the same
+    tensor without its first column -- the base one element off: single loads and stores throughout (8-byte ones in
+    float64); 2 x 9 x 67 -- a ragged strip with a scalar store tail.  Bit-equal to scipy."""
+    import scipy.ndimage as ndi
+    import torch
+    from nd_amd import kernels
+    rng = np.random.default_rng(72)
+    whole = torch.from_numpy(rng.normal(size=(2, 9, 256)).astype(npdt)).to(device)
+    ragged = torch.from_numpy(rng.normal(size=(2, 9, 67)).astype(npdt)).to(device)
+    for t in (whole, whole[..., 1:], ragged):
+        got = kernels.gaussian_filter(t, (0, 1, 1))
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(got.cpu().numpy(), ndi.gaussian_filter(t.cpu().numpy(), (0, 1, 1)))
