@@ -85,6 +85,7 @@ extern "C" {
 #define ND_AMD_KERNEL_RESAMPLE        28  /* nd_amd_resample and nd_amd_resample_nearest */
 #define ND_AMD_KERNEL_SPECKLE         29  /* nd_amd_speckle_lee and nd_amd_speckle_multitemporal, the whole call */
 #define ND_AMD_KERNEL_REGIONS         30  /* nd_amd_label_regions, nd_amd_region_sizes, nd_amd_sieve_regions, the whole call */
+#define ND_AMD_KERNEL_ZONAL           31  /* nd_amd_zonal_keys, nd_amd_zonal_stats, nd_amd_zonal_paint, the whole call */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -1198,6 +1199,98 @@ int nd_amd_sieve_regions(const void *src, void *dst, int dtype, int64_t nplanes,
                          int connectivity, int by_value,
                          const void *background, const void *fill,     /* one host element each             */
                          int64_t min_size, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* ----------------------------------------------------------------------
+ * Statistics of zones: count, sum, mean, variance, minimum and maximum of
+ * every plane of a stack inside every zone of a label map (a rasterized
+ * parcel layer, a labelling of regions, a class map), and a zone's statistic
+ * painted back onto its pixels.  The reference has no counterpart; the
+ * definition is this project's, tests/zonal_ref.py restates it bit for bit and
+ * scipy.ndimage.sum_labels / mean / variance / minimum / maximum hold it.
+ *
+ *   Zones.  A label plane has ny x nx elements of ND_AMD_U8 (bool as 0 / 1),
+ *       ND_AMD_I32, ND_AMD_I64, ND_AMD_F32 or ND_AMD_F64.  ids is a strictly
+ *       increasing list of n int64 zone ids; NULL stands for 1 .. n.  A pixel
+ *       belongs to zone z (rank 0 .. n - 1) iff its label compares equal to
+ *       ids[z]; NaN and every other value belong to no zone.  Integer labels
+ *       are compared as int64, never through a double; a floating label is
+ *       compared as the int64 it equals, if it is whole and in range.
+ *   Sequence.  A zone's pixels in raster order of i * nx + j are its
+ *       positions p = 0 .. m - 1.  For a data plane of type T (ND_AMD_F32,
+ *       ND_AMD_F64) c_p = (double)x_p; a position takes part iff x_p == x_p.
+ *       NaN is skipped and counted; nothing else is special: inf, zeros and
+ *       negative values enter as they are.
+ *   Statistics per (plane, zone):
+ *       count (int64)      positions that take part
+ *       nan_count (int64)  positions that are NaN
+ *       sum                the sum of c_p over the participants, 0.0 with none
+ *       min, max           of the participants, NaN with none (the sign of a
+ *                          zero is not pinned)
+ *       m2                 the sum of (c_p - mean) * (c_p - mean), mean = sum /
+ *                          count in one IEEE division, one rounding for the
+ *                          difference and one for the product
+ *                          (-ffp-contract=off); 0.0 with none
+ *       mean = sum / count, var = m2 / (count - ddof) and std = sqrt(var) are
+ *       the caller's (nd_amd/kernels.py, nd_amd/zonal.py).
+ *   The order of the sums.  Every floating-point sum is formed in one fixed
+ *       tree, a function of the zone's own sequence alone -- not of other
+ *       zones, the number of planes, the layout, the grid or scheduling -- and
+ *       there is no floating-point atomic anywhere:
+ *         chunk    64 consecutive positions, summed by the aligned pairwise
+ *                  tree: position l with l ^ 1, the pairs with ^ 2, ... ^ 32.
+ *                  An operand that is absent (behind the zone's end) or
+ *                  skipped (NaN) does not take part: a (+) absent = a.
+ *         segment  64 chunks (4096 positions): the chunk sums added
+ *                  sequentially in order, chunks without a participant left out
+ *         zone     its segment sums added sequentially in order, segments
+ *                  without a participant left out
+ *       Two calls give the same bytes, and a zone's bytes do not change when
+ *       other zones are relabelled or merged.
+ *   Paint.  out[i, j] = (T)table[plane, z] for a pixel of zone z; a pixel of
+ *       no zone keeps src's value where src is given, else it is (T)fill.
+ *
+ * nd_amd_zonal_keys writes the dense int32 keys[ny * nx]: the zone's rank, or
+ * n for no zone (a binary search in ids where given; ids is a device array).
+ * BETWEEN the two entries the CALLER sorts: perm (int32, ny * nx) is the
+ * stable argsort of keys, and offsets (int64, n + 1) has offsets[z] = the
+ * number of keys < z, so zone z's pixels are perm[offsets[z] .. offsets[z +
+ * 1]) in raster order.  nd_amd.kernels.zonal_index does this with torch's
+ * stable sort and searchsorted on the device; the library contains no sort.
+ * Entries of perm outside the plane and offsets outside 0 .. ny * nx are
+ * read as nothing, never followed.
+ * nd_amd_zonal_stats takes nplanes data planes (strides: 3 host values in
+ * elements for (plane, y, x), none negative: (time, y, x) and (y, x, time)
+ * stacks and crops are read where they lie) and writes the outputs, each
+ * (nplanes, n) contiguous on the device and each NULL to skip it.  The
+ * workspace (nd_amd_zonal_workspace_bytes) holds the partial sums of the
+ * segments of zones of more than 4096 pixels: 40 bytes per plane and 2048
+ * pixels, and 16 bytes per (plane, zone).  nd_amd_zonal_paint takes keys, a
+ * (nplanes, n) float64 table, src (NULL: fill) and dst of type dtype with
+ * their strides.  No entry waits for the device.
+ * ND_AMD_EINVAL before any HIP call for a bad dtype, negative sizes, n or
+ * strides and null pointers; ND_AMD_EUNSUPPORTED for planes of 2^31 pixels or
+ * more, for n >= 2^31 - 1 (both checked before the pointers) and for more
+ * blocks than a launch holds; ND_AMD_EWORKSPACE for a missing or short
+ * workspace; ND_AMD_OK with nothing done for an empty plane or batch, and in
+ * nd_amd_zonal_stats for n = 0.
+ * ---------------------------------------------------------------------- */
+int nd_amd_zonal_keys(const void *labels, int dtype, int64_t ny, int64_t nx,
+                      const int64_t *label_strides,                    /* 2 host values: y, x               */
+                      const int64_t *ids, int64_t n,                   /* device, n; NULL: 1 .. n           */
+                      int32_t *keys, void *hip_stream);
+
+size_t nd_amd_zonal_workspace_bytes(int64_t nplanes, int64_t ny, int64_t nx, int64_t n);
+
+int nd_amd_zonal_stats(const void *values, int dtype, int64_t nplanes, int64_t ny, int64_t nx,
+                       const int64_t *strides,
+                       const int32_t *perm, const int64_t *offsets, int64_t n,
+                       int64_t *count, int64_t *nan_count,             /* (nplanes, n) each, NULL to skip   */
+                       double *sum, double *min, double *max, double *m2,
+                       void *workspace, size_t workspace_bytes, void *hip_stream);
+
+int nd_amd_zonal_paint(const int32_t *keys, const double *table, int64_t nplanes, int64_t ny, int64_t nx,
+                       int64_t n, const void *src, const int64_t *src_strides,   /* NULL: fill               */
+                       void *dst, const int64_t *dst_strides, int dtype, double fill, void *hip_stream);
 
 #ifdef __cplusplus
 }

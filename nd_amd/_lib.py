@@ -24,7 +24,8 @@ KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 13: 'coregister_shifts', 14: 'warp_translate', 15: 'rgb_limits', 16: 'rgb_compose',
                 17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean',
                 21: 'classify_knn', 22: 'classify_linear', 23: 'kmeans_step', 24: 'feature_moments',
-                25: 'gather_rows', 26: 'change_segments', 27: 'rasterize', 28: 'resample', 29: 'speckle', 30: 'regions'}
+                25: 'gather_rows', 26: 'change_segments', 27: 'rasterize', 28: 'resample', 29: 'speckle', 30: 'regions',
+                31: 'zonal'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 STRUCT_DIAG, STRUCT_C2, STRUCT_C3 = 0, 1, 2
 
@@ -51,7 +52,8 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_rasterize_workspace_bytes', 'nd_amd_rasterize_polygons',
            'nd_amd_resample', 'nd_amd_resample_nearest', 'nd_amd_resample_check_table',
            'nd_amd_speckle_lee', 'nd_amd_speckle_multitemporal_workspace_bytes', 'nd_amd_speckle_multitemporal',
-           'nd_amd_regions_workspace_bytes', 'nd_amd_label_regions', 'nd_amd_region_sizes', 'nd_amd_sieve_regions')
+           'nd_amd_regions_workspace_bytes', 'nd_amd_label_regions', 'nd_amd_region_sizes', 'nd_amd_sieve_regions',
+           'nd_amd_zonal_keys', 'nd_amd_zonal_workspace_bytes', 'nd_amd_zonal_stats', 'nd_amd_zonal_paint')
 CLASSIFY_BLOCK_ROWS, CLASSIFY_MAX_FEATURES = 1024, 1024
 CLASSIFY_KNN_MAX_K, CLASSIFY_KNN_MAX_FEATURES, CLASSIFY_KNN_TILE = 32, 128, 8
 KMEANS_FIT_MAX_ACC = 4096
@@ -229,6 +231,14 @@ def lib():
     L.nd_amd_sieve_regions.restype = i32
     L.nd_amd_sieve_regions.argtypes = [vp, vp, i32, i64, i64, i64, pi64, pi64, i32, i32, vp, vp, i64,
                                        vp, C.c_size_t, vp]
+    L.nd_amd_zonal_keys.restype = i32
+    L.nd_amd_zonal_keys.argtypes = [vp, i32, i64, i64, pi64, vp, i64, vp, vp]
+    L.nd_amd_zonal_workspace_bytes.restype = C.c_size_t
+    L.nd_amd_zonal_workspace_bytes.argtypes = [i64, i64, i64, i64]
+    L.nd_amd_zonal_stats.restype = i32
+    L.nd_amd_zonal_stats.argtypes = [vp, i32, i64, i64, i64, pi64, vp, vp, i64] + [vp] * 6 + [vp, C.c_size_t, vp]
+    L.nd_amd_zonal_paint.restype = i32
+    L.nd_amd_zonal_paint.argtypes = [vp, vp, i64, i64, i64, i64, vp, pi64, vp, pi64, i32, dbl, vp]
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

@@ -1,5 +1,5 @@
 // nd_amd/csrc/entry_args.hpp -- what the change-detection entries (nd_amd_omnibus_c2 / _c2_ml / _c2_pixel_major,
-// _c3 / _c3_pixel_major, _diag, nd_amd_change_segments) and the region entries decide alike, written once: which arguments are
+// _c3 / _c3_pixel_major, _diag, nd_amd_change_segments), the region and the zonal entries decide alike, written once: which arguments are
 // acceptable, how a raster is walked in rows, and how many blocks walk a sharded candidate list; and align256, where
 // every unit's workspace sections start.  Plain C++:
 // no HIP header and no device symbol, so every unit may include it (common.hpp does) and a CPU checks it
@@ -131,6 +131,31 @@ static inline int check_strides(const char *entry, const char *what, const int64
     set_error("%s: negative stride in %s (%lld, %lld, %lld)", entry, what, (long long)s[0], (long long)s[1],
               (long long)s[2]);
     return ND_AMD_EINVAL;
+}
+
+// ---- the zonal entries (nd_amd_zonal_keys, nd_amd_zonal_stats, nd_amd_zonal_paint)
+// 2 host values in elements for (y, x) of one plane, none negative
+static inline int check_strides2(const char *entry, const char *what, const int64_t *s)
+{
+    if (!s) {
+        set_error("%s: %s is null", entry, what);
+        return ND_AMD_EINVAL;
+    }
+    if (s[0] >= 0 && s[1] >= 0) return ND_AMD_OK;
+    set_error("%s: negative stride in %s (%lld, %lld)", entry, what, (long long)s[0], (long long)s[1]);
+    return ND_AMD_EINVAL;
+}
+
+// a pixel's key is its zone's rank in an int32, n itself being "no zone"
+static inline int check_zone_count(const char *entry, int64_t n)
+{
+    if (n < 0) {
+        set_error("%s: negative number of zones %lld", entry, (long long)n);
+        return ND_AMD_EINVAL;
+    }
+    if (n < 0x7fffffffLL) return ND_AMD_OK;
+    set_error("%s: 2^31 - 1 zones or more are not served (%lld)", entry, (long long)n);
+    return ND_AMD_EUNSUPPORTED;
 }
 
 // ---- grids

@@ -2183,6 +2183,188 @@ def sieve_regions(inp, min_size, connectivity=4, background=0, by_value=False, f
     return out
 
 
+# ---------------------------------------------------------------------------
+# statistics of zones (include/nd_amd.h "Statistics of zones"; tests/zonal_ref.py restates it bit for bit)
+# ---------------------------------------------------------------------------
+ZONAL_STATS = ('count', 'nan_count', 'sum', 'min', 'max', 'm2', 'mean')
+_ZONAL_OUT = ('count', 'nan_count', 'sum', 'min', 'max', 'm2')      # the order of nd_amd_zonal_stats' outputs
+
+
+def zonal_ids(ids):
+    """`ids` as a strictly increasing int64 numpy array; ValueError otherwise"""
+    a = np.asarray(ids)
+    if a.ndim == 1 and a.size == 0:
+        return np.zeros(0, np.int64)
+    if a.ndim != 1 or a.dtype.kind not in 'iu':
+        raise ValueError('ids must be a one-dimensional list of integers, got %s %s' % (a.dtype, a.shape))
+    if a.dtype.kind == 'u' and a.size and int(a.max()) >= 2 ** 63:
+        raise ValueError('ids must fit an int64')
+    a = a.astype(np.int64)
+    if a.size > 1 and not (a[1:] > a[:-1]).all():
+        raise ValueError('ids must be strictly increasing')
+    return a
+
+
+class ZonalIndex(object):
+    """A label plane's zones as the statistics read them: keys (int32, (ny, nx): the zone's rank, n for no zone), perm
+    (int32: the stable argsort of the keys), offsets (int64, n + 1: the keys below z), n, and ids (int64 numpy)."""
+
+    def __init__(self, keys, perm, offsets, n, ids):
+        self.keys, self.perm, self.offsets, self.n, self.ids = keys, perm, offsets, n, ids
+
+    @property
+    def shape(self):
+        return tuple(self.keys.shape)
+
+
+def _zonal_default_n(labels):
+    """the largest label that is a positive whole number, 0 if there is none: one number read back"""
+    if labels.numel() == 0:
+        return 0
+    if labels.dtype == torch.bool:
+        return int(labels.any())
+    if labels.is_floating_point():
+        whole = (labels == labels.trunc()) & (labels.abs() < 2.0 ** 63)
+        top = float(labels.masked_fill(~whole, 0).max())
+        if top >= 2 ** 31 - 1:
+            raise NotImplementedError('2^31 - 1 zones or more are not served (largest label %r)' % top)
+        return max(int(top), 0)
+    return max(int(labels.max()), 0)
+
+
+def zonal_index(labels, ids=None, dims=None, n=None):
+    """The zones of one label plane: a ROCm tensor of bool, uint8, int32, int64, float32 or float64 with the axes
+    ('y', 'x') (dims: their order), any non-negative strides.  ids: a strictly increasing list of integer zone ids;
+    by default 1 .. the largest label.  A pixel belongs to the zone whose id its label equals, every other pixel
+    (0, NaN, 2.5, a label not listed) to none.  -> ZonalIndex.  The keys come from nd_amd_zonal_keys; the stable sort
+    and the search between the two entries are torch's, on the device.  n: with ids=None, the zones are 1 .. n (a
+    caller that labels several planes alike); without it the call reads the largest label back and waits for the
+    device."""
+    dims = ('y', 'x') if dims is None else tuple(dims)
+    if torch.is_tensor(labels) and labels.dim() != 2:
+        raise ValueError('labels must be one plane with the axes y and x, got %d axes' % labels.dim())
+    dims, ay, ax, ny, nx = _region_input(labels, dims, 'labels')
+    dev = labels.device
+    lab = _byte_view(labels).permute(ay, ax)
+    if ids is None:
+        if n is not None and (isinstance(n, bool) or int(n) != n or n < 0):
+            raise ValueError('n must be a non-negative integer, got %r' % (n,))
+        n = _zonal_default_n(lab) if n is None else int(n)
+        host_ids = np.arange(1, n + 1, dtype=np.int64)
+        ids_dev = None
+    else:
+        host_ids = zonal_ids(ids)
+        n = len(host_ids)
+        ids_dev = torch.from_numpy(host_ids).to(dev) if n else None
+    if n >= 2 ** 31 - 1:
+        raise NotImplementedError('2^31 - 1 zones or more are not served (%d)' % n)
+    with torch.cuda.device(dev):
+        keys = torch.empty((ny, nx), dtype=torch.int32, device=dev)
+        if keys.numel():
+            _lib.check(_lib.lib().nd_amd_zonal_keys(_ptr(lab), _REGION_DT[labels.dtype], ny, nx,
+                                                    _lib.i64_array(lab.stride()), _ptr(ids_dev), n, _ptr(keys),
+                                                    _stream_ptr(dev)))
+            _record([labels, ids_dev, keys], dev)
+        ordered, perm = torch.sort(keys.reshape(-1), stable=True)
+        offsets = torch.searchsorted(ordered, torch.arange(n + 1, dtype=torch.int32, device=dev)).to(torch.int64)
+        return ZonalIndex(keys, perm.to(torch.int32), offsets, n, host_ids)
+
+
+def _zonal_values(values, index, dims, name='values'):
+    if not isinstance(index, ZonalIndex):
+        raise TypeError('index must come from zonal_index, got %r' % type(index))
+    dims, ay, ax, ny, nx = _region_input(values, dims, name)
+    if (ny, nx) != index.shape:
+        raise ValueError('%s has planes of %d x %d, the zones of %d x %d' % ((name, ny, nx) + index.shape))
+    if values.device != index.keys.device:
+        raise ValueError('%s and the index live on different devices' % name)
+    return dims, ay, ax, ny, nx
+
+
+def zonal_stats(values, index, dims=None, stats=('count', 'mean', 'min', 'max', 'm2')):
+    """Statistics of every (y, x) plane of `values` inside every zone of `index` (zonal_index): a ROCm tensor whose
+    axes `dims` names as for label_regions, float32 or float64 (other types are computed as float64), any non-negative
+    strides.  stats: names among ZONAL_STATS.  -> a dict of tensors shaped (the axes besides y and x..., n): int64
+    counts, float64 for the rest.  NaN values are skipped and counted; every sum is formed in the zone's fixed tree, so
+    the bytes do not depend on the layout, the other zones or the number of planes."""
+    stats = tuple(stats)
+    for s in stats:
+        if s not in ZONAL_STATS:
+            raise ValueError('stats must be among %s, got %r' % (ZONAL_STATS, s))
+    dims, ay, ax, ny, nx = _zonal_values(values, index, dims)
+    if not values.is_floating_point():
+        values = values.to(torch.float64)
+    dev, n = values.device, index.n
+    want = set(stats) | ({'sum', 'count'} if 'mean' in stats else set())
+    (src,), lead = _plane_batches([values], ay, ax)
+    shape = tuple(src.shape[:-2]) + (n,)
+    with torch.cuda.device(dev):
+        out = {s: torch.empty(shape, dtype=torch.int64 if s in ('count', 'nan_count') else torch.float64, device=dev)
+               for s in _ZONAL_OUT if s in want}
+        nplanes = src.shape[-3]
+        if n and src.numel():
+            L = _lib.lib()
+            nbytes = int(L.nd_amd_zonal_workspace_bytes(nplanes, ny, nx, n))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            for idx in lead:
+                s = src[idx]
+                _lib.check(L.nd_amd_zonal_stats(
+                    _ptr(s), _DT[values.dtype], nplanes, ny, nx, _lib.i64_array(s.stride()), _ptr(index.perm),
+                    _ptr(index.offsets), n, *[_ptr(out[k][idx]) if k in out else None for k in _ZONAL_OUT],
+                    _ptr(work), nbytes, _stream_ptr(dev)))
+            _record([values, work, index.perm, index.offsets] + list(out.values()), dev)
+        elif n:                                         # zones, and no pixel: what a zone without a participant gets
+            for k, t in out.items():
+                t.fill_(float('nan') if k in ('min', 'max') else 0)
+        if 'mean' in stats:
+            out['mean'] = out['sum'] / out['count'].to(torch.float64)
+    res = {s: out[s] for s in stats}
+    if values.dim() == 2:
+        res = {s: t[0] for s, t in res.items()}
+    return res
+
+
+def zonal_paint(table, index, like=None, out=None, keep=False, fill=None, dims=None):
+    """Every pixel of zone z gets table[..., z]: table is a float64 ROCm tensor shaped (the axes besides y and x..., n),
+    as zonal_stats returns.  like: a float32 or float64 tensor whose shape, type and memory order the result takes, and
+    with keep=True the values of the pixels of no zone; out: the result's tensor, any strides.  Pixels of no zone get
+    `fill` (default NaN) unless keep.  -> out."""
+    ref = out if like is None else like
+    if ref is None:
+        raise ValueError('like or out must be given')
+    dims, ay, ax, ny, nx = _zonal_values(ref, index, dims, 'like' if like is not None else 'out')
+    if ref.dtype not in _DT:
+        raise TypeError('painted planes are float32 or float64, got %s' % ref.dtype)
+    if keep and like is None:
+        raise ValueError('keep=True needs `like`: the values of the pixels of no zone')
+    dev, n = ref.device, index.n
+    out = _region_out(out, ref, ref.dtype, 'out', [like if keep else None])
+    fillv = float('nan') if fill is None else float(fill)
+    (dst, src), lead = _plane_batches([out, like if keep else None], ay, ax)
+    shape = tuple(dst.shape[:-2]) + (n,)
+    if not torch.is_tensor(table) or table.dtype != torch.float64 or table.device != dev:
+        raise ValueError('table must be a float64 tensor on %s' % dev)
+    if out.dim() == 2:
+        table = table[None]
+    if tuple(table.shape) != shape:
+        raise ValueError('table must be shaped %s, got %s' % (shape, tuple(table.shape)))
+    if out.numel() == 0:
+        return out
+    table = table.contiguous()
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        nplanes = dst.shape[-3]
+        for idx in lead:
+            d = dst[idx]
+            s = src[idx] if keep else None
+            _lib.check(L.nd_amd_zonal_paint(
+                _ptr(index.keys), _ptr(table[idx]) if n else None, nplanes, ny, nx, n, _ptr(s) if keep else None,
+                _lib.i64_array(s.stride()) if keep else None, _ptr(d), _lib.i64_array(d.stride()), _DT[out.dtype],
+                fillv, _stream_ptr(dev)))
+        _record([table, index.keys, like, out], dev)
+    return out
+
+
 def _lib_device(device=None):
     if device is not None:
         return torch.device(device)
