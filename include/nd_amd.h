@@ -11,6 +11,26 @@
  * success, a negative ND_AMD_E* code otherwise; nd_amd_last_error() returns a
  * thread-local description.  The library never throws and never aborts.
  *
+ * Streams and threads.  Every launch, memset and copy of an entry goes to
+ * `hip_stream`, nothing to the null stream.  These entries WAIT for the stream
+ * before they return, and therefore cannot be captured in a graph:
+ *   nd_amd_correlate                     with more than 128 taps (the tap list
+ *                                        goes through a host copy);
+ *   nd_amd_omnibus_c2, _c2_pixel_major,
+ *   nd_amd_omnibus_c3, _c3_pixel_major,
+ *   nd_amd_omnibus_diag                  with more than 96 dates (the decision
+ *                                        table likewise);
+ *   nd_amd_resample_check_table          always (it reads its verdict back);
+ *   nd_amd_label_regions,
+ *   nd_amd_sieve_regions                 always (they read a word back).
+ * No other entry waits for its stream or for the device.  Entries may be
+ * called from several host threads at once on different streams: the state
+ * the library keeps between calls (hipFFT plans, per stream; decision tables;
+ * the error text, per thread) is guarded.  Calls on ONE stream from several
+ * threads are the caller's to order: the library takes no lock around the
+ * work it enqueues.  The nd_amd_timing_* ring is one per process and is not
+ * meant for concurrent callers.
+ *
  * No host twins.  SURVEY.md 8(b) sketched a `*_cpu` entry next to every device
  * entry (same arguments on host pointers).  The ABI deliberately has none: the
  * reference interface itself has no such pair (its native calls ARE the host

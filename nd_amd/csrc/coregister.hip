@@ -35,17 +35,22 @@ namespace nd_amd {
         }                                                                                    \
     } while (0)
 
-// (device, ny, nx, batch, dtype, inverse) -> plan.  rocFFT builds its kernels on a plan's first
-// use; the cache keeps that cost to the first call of a shape.
+// (device, stream, ny, nx, batch, dtype, inverse) -> plan.  rocFFT builds its kernels on a plan's
+// first use; the cache keeps that cost to the first call of a shape on a stream.  The stream is part
+// of the key: a plan's stream is set once, when the plan is made, and never changed, and its
+// auto-allocated work area belongs to that stream alone.  The transforms run after g_plan_mu is
+// released, so a plan shared between streams could be retargeted by one host thread between another
+// thread's fft_plan and its hipfftExec*, and two streams would share one work area.  Plans live as
+// long as the process: a caller that makes and destroys streams without end grows the cache.
 static std::mutex g_plan_mu;
-static std::map<std::tuple<int, int, int, int, int, int>, hipfftHandle> g_plans;
+static std::map<std::tuple<int, hipStream_t, int, int, int, int, int>, hipfftHandle> g_plans;
 
 static int fft_plan(int ny, int nx, int batch, int dtype, bool inverse, hipStream_t stream, hipfftHandle *out)
 {
     int dev = 0;
     ND_HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_plan_mu);
-    const auto key = std::make_tuple(dev, ny, nx, batch, dtype, inverse ? 1 : 0);
+    const auto key = std::make_tuple(dev, stream, ny, nx, batch, dtype, inverse ? 1 : 0);
     auto it = g_plans.find(key);
     if (it == g_plans.end()) {
         hipfftHandle h;
@@ -53,9 +58,13 @@ static int fft_plan(int ny, int nx, int batch, int dtype, bool inverse, hipStrea
         const hipfftType type = dtype == ND_AMD_F32 ? (inverse ? HIPFFT_C2R : HIPFFT_R2C)
                                                     : (inverse ? HIPFFT_Z2D : HIPFFT_D2Z);
         ND_FFT_CHECK(hipfftPlanMany(&h, 2, n, nullptr, 1, 0, nullptr, 1, 0, type, batch));
+        const hipfftResult r = hipfftSetStream(h, stream);
+        if (r != HIPFFT_SUCCESS) {
+            hipfftDestroy(h);
+            ND_FFT_CHECK(r);
+        }
         it = g_plans.emplace(key, h).first;
     }
-    ND_FFT_CHECK(hipfftSetStream(it->second, stream));
     *out = it->second;
     return ND_AMD_OK;
 }

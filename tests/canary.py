@@ -33,13 +33,14 @@ import torch
 PATTERNS = (0xFF, 0x55)
 PATCHED = ('empty', 'empty_like', 'empty_strided')       # the uninitialised-allocation functions nd_amd's Python uses
 _HERE = os.path.abspath(__file__)
+HELPERS = [_HERE]       # files whose frames are no call site: a helper that wraps the patched functions adds itself
 _ACTIVE = []
 
 
 def _call_site():
-    """file:line (function) of the innermost frame outside this module"""
+    """file:line (function) of the innermost frame outside this module (and outside every file of HELPERS)"""
     f = sys._getframe(1)
-    while f is not None and os.path.abspath(f.f_code.co_filename) == _HERE:
+    while f is not None and os.path.abspath(f.f_code.co_filename) in HELPERS:
         f = f.f_back
     if f is None:
         return '?'
@@ -72,7 +73,14 @@ class canary(object):
         self.wrapped = 0
         self.guarded = 0
         self._records = []
+        self._unguarded = []
         self._orig = None
+
+    def allocations(self):
+        """[(every byte of the allocation as a flat uint8 tensor, its description)] for what was poisoned since the last
+        check(release=True): a guarded allocation with both guard bands, an unguarded one as its whole storage.  For
+        helpers that watch the memory the library was handed (tests/held_stream.py)."""
+        return [(r.base, r.describe()) for r in self._records] + list(self._unguarded)
 
     # ---- patching ------------------------------------------------------------------------------------------
     def __enter__(self):
@@ -91,6 +99,7 @@ class canary(object):
         if exc_type is None:
             self.check()
         self._records = []
+        self._unguarded = []
         return False
 
     def _wrapper(self, name):
@@ -111,7 +120,10 @@ class canary(object):
         empty = self._orig['empty']
         if not t.is_contiguous():
             # torch's own tensor, its whole storage filled: no guard
-            empty(0, dtype=torch.uint8, device=t.device).set_(t.untyped_storage()).fill_(self.pattern)
+            whole = empty(0, dtype=torch.uint8, device=t.device).set_(t.untyped_storage())
+            whole.fill_(self.pattern)
+            self._unguarded.append((whole, 'shape %s, strides %s, %s, allocated at %s'
+                                    % (tuple(t.shape), tuple(t.stride()), t.dtype, _call_site())))
             return t
         nbytes = t.numel() * t.element_size()
         g = self.guard_bytes
@@ -146,6 +158,7 @@ class canary(object):
         finally:
             if release:
                 self._records = []
+                self._unguarded = []
 
     def is_poison(self, t):
         """elementwise: every byte of the element still holds the pattern (a bool tensor shaped like t)"""
