@@ -326,6 +326,8 @@ __device__ __forceinline__ void follow_starts_chain(const int (&nxt)[NSWEEP], co
 {
     int at = 0;
     for (int step = 0; step < ns; ++step) {
+        // every chain of the wave has ended (a typical one after two or three steps): the steps left would move nothing
+        if (!__any(at >= 0 && at < ns)) break;
         const int ats = (at >= 0 && at < ns) ? at : 0;
         const int src = grp * nsw + (ats & 63) % nsw;
         int nx[NSWEEP];
