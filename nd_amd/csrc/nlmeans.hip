@@ -51,6 +51,48 @@ struct NlmArgs {
     int64_t total;
 };
 
+// The reference's weight of one neighbour from its summed squared differences, in double, and the three
+// weight accumulators it feeds (nd/_filters.pyx:386-403): exp(-max(dsq / norm - 2 sigma^2, 0) / h^2)
+__device__ __forceinline__ double nlm_weight_exact(double dsq, double norm, double two_sigma2, double h2,
+                                                   double *t_w, double *t_sq, double *m_w)
+{
+    dsq = dsq / norm;
+    const double t = dsq - two_sigma2;
+    const double m = (0.0 > t) ? 0.0 : t;
+    const double w = exp((-m) / h2);
+    *t_w = *t_w + w;
+    *t_sq = *t_sq + (w * w);
+    if (w > *m_w) *m_w = w;
+    return w;
+}
+
+// The pixel's own weight: the largest neighbour weight (1 if that is 0), or find_weight (nd/_filters.pyx:299-314).
+// Where that raises: policy 1 sets the status word and *fail (the caller stores nothing), policy 0 gives 0.
+__device__ __forceinline__ double nlm_self_weight(double total_weight, double total_sq_weight,
+                                                  double max_weight, double n_eff, int policy,
+                                                  int32_t *status, bool *fail)
+{
+    *fail = false;
+    if (n_eff < 0) {
+        if (max_weight == 0) max_weight = 1;
+        return max_weight;
+    }
+    const double n = n_eff;
+    bool err = (total_sq_weight == 0);
+    if (!err) err = (n - 1.0) > ((total_weight * total_weight) / total_sq_weight);
+    if (!err) err = ((n - 1.0) == 0);
+    if (err) {
+        if (policy == 1) {
+            if (status) atomicExch(status, 1);
+            *fail = true;
+        }
+        return 0.0;
+    }
+    const double rt = sqrt(((((n * total_weight) * total_weight) - ((n * n) * total_sq_weight)) +
+                            (n * total_sq_weight)));
+    return (total_weight + rt) / (n - 1.0);
+}
+
 template <typename T, int VMAX>
 __global__ void __launch_bounds__(256) nlmeans_generic_kernel(const NlmArgs<T> a)
 {
@@ -98,13 +140,8 @@ __global__ void __launch_bounds__(256) nlmeans_generic_kernel(const NlmArgs<T> a
                 }
             }
         }
-        dsquare = dsquare / (double)a.dsq_norm;
-        const double t = dsquare - a.two_sigma2;
-        const double m = (0.0 > t) ? 0.0 : t;
-        const double weight = exp((-m) / a.h2);
-        total_weight = total_weight + weight;
-        total_sq_weight = total_sq_weight + (weight * weight);
-        if (weight > max_weight) max_weight = weight;
+        const double weight = nlm_weight_exact(dsquare, (double)a.dsq_norm, a.two_sigma2, a.h2, &total_weight,
+                                               &total_sq_weight, &max_weight);
         const int64_t qq = (reflect_once<int64_t>(q0, a.G[0]) - a.toff[0]) * a.si[0] +
                            (reflect_once<int64_t>(q1, a.G[1]) - a.toff[1]) * a.si[1] +
                            (reflect_once<int64_t>(q2, a.G[2]) - a.toff[2]) * a.si[2];
@@ -115,29 +152,10 @@ __global__ void __launch_bounds__(256) nlmeans_generic_kernel(const NlmArgs<T> a
         }
     }
 
-    double weight;
-    if (a.n_eff < 0) {
-        if (max_weight == 0) max_weight = 1;
-        weight = max_weight;
-    } else {
-        // find_weight, nd/_filters.pyx:299-314
-        const double n = a.n_eff;
-        bool err = (total_sq_weight == 0);
-        if (!err) err = (n - 1.0) > ((total_weight * total_weight) / total_sq_weight);
-        if (!err) err = ((n - 1.0) == 0);
-        if (err) {
-            if (a.neff_policy == 1) {
-                if (a.status) atomicExch(a.status, 1);
-                return;
-            }
-            weight = 0.0;
-        } else {
-            const double rt = sqrt(((((n * total_weight) * total_weight) -
-                                     ((n * n) * total_sq_weight)) +
-                                    (n * total_sq_weight)));
-            weight = (total_weight + rt) / (n - 1.0);
-        }
-    }
+    bool fail;
+    const double weight = nlm_self_weight(total_weight, total_sq_weight, max_weight, a.n_eff, a.neff_policy,
+                                          a.status, &fail);
+    if (fail) return;
     total_weight = total_weight + weight;
     const int64_t pp = p[0] * a.si[0] + p[1] * a.si[1] + p[2] * a.si[2];
     const int64_t po = p[0] * a.so[0] + p[1] * a.so[1] + p[2] * a.so[2];
@@ -240,36 +258,46 @@ __device__ __forceinline__ void nlm_stage_t(const NlmTiledArgs &a, T *lds, int *
     __syncthreads();
 }
 
-__device__ __forceinline__ void nlm_stage(const NlmTiledArgs &a, float *lds, int *ymap, int *xmap,
-                                          int rows, int cols, int64_t gy0, int64_t gx0, int64_t i2,
-                                          int v, int tid, bool *nonfinite = nullptr)
+// The block's tile: blocks run over tiles along x, then along y, then `third` -- the slice (relative to clo2)
+// or the variable, whichever the grid's third factor counts.  (y0, x0) is the tile's first pixel, xlo the column
+// the tiles start from (clo1 unless given).
+struct NlmTile {
+    int tx, ty;
+    int64_t third, y0, x0;
+};
+__device__ __forceinline__ NlmTile nlm_tile_of_block(const NlmTiledArgs &a, int TX, int TY, int64_t xlo)
 {
-    nlm_stage_t<float>(a, lds, ymap, xmap, rows, cols, gy0, gx0, i2, v, tid, nonfinite);
+    NlmTile t;
+    int64_t b = blockIdx.x;
+    t.tx = (int)(b % a.tiles_x);
+    b /= a.tiles_x;
+    t.ty = (int)(b % a.tiles_y);
+    t.third = b / a.tiles_y;
+    t.y0 = a.clo0 + (int64_t)t.ty * TY;
+    t.x0 = xlo + (int64_t)t.tx * TX;
+    return t;
+}
+__device__ __forceinline__ NlmTile nlm_tile_of_block(const NlmTiledArgs &a, int TX, int TY)
+{
+    return nlm_tile_of_block(a, TX, TY, a.clo1);
 }
 
-__device__ __forceinline__ double nlm_self_weight(double total_weight, double total_sq_weight,
-                                                  double max_weight, double n_eff, int policy,
-                                                  int32_t *status, bool *fail)
+// The end of a pixel for variable v (nd/_filters.pyx:417-420): the self term enters the weighted sum last, then
+// the quotient, both formed in double and rounded to float.  ws: the neighbours' weighted sum, c: the pixel's own
+// value, total: the neighbours' weights plus wself.
+__device__ __forceinline__ void nlm_finish(const NlmTiledArgs &a, int64_t i2, int v, int64_t y, int64_t x, float ws,
+                                           float c, double wself, double total)
 {
-    *fail = false;
-    if (n_eff < 0) {
-        if (max_weight == 0) max_weight = 1;
-        return max_weight;
-    }
-    const double n = n_eff;
-    bool err = (total_sq_weight == 0);
-    if (!err) err = (n - 1.0) > ((total_weight * total_weight) / total_sq_weight);
-    if (!err) err = ((n - 1.0) == 0);
-    if (err) {
-        if (policy == 1) {
-            if (status) atomicExch(status, 1);
-            *fail = true;
-        }
-        return 0.0;
-    }
-    const double rt = sqrt(((((n * total_weight) * total_weight) - ((n * n) * total_sq_weight)) +
-                            (n * total_sq_weight)));
-    return (total_weight + rt) / (n - 1.0);
+    const float sfin = (float)((double)ws + (wself * (double)c));
+    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = (float)((double)sfin / total);
+}
+
+// the result is NaN for every variable
+template <int V>
+__device__ __forceinline__ void nlm_store_nan(const NlmTiledArgs &a, int64_t i2, int64_t y, int64_t x)
+{
+#pragma unroll
+    for (int v = 0; v < V; ++v) a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = __builtin_nanf("");
 }
 
 // find_weight's discriminant n W^2 - n^2 W2 + n W2 relative to its leading term.  Where the
@@ -308,12 +336,8 @@ __global__ void __launch_bounds__(256) nlmeans_window_kernel(const NlmTiledArgs 
     int *ymap = reinterpret_cast<int *>(lds + nz * psz);
     int *xmap = ymap + rows;
 
-    int64_t b = blockIdx.x;
-    const int tx = (int)(b % a.tiles_x);
-    b /= a.tiles_x;
-    const int ty = (int)(b % a.tiles_y);
-    const int64_t i2 = a.clo2 + b / a.tiles_y;
-    const int64_t y0 = a.clo0 + (int64_t)ty * kWinTY, x0 = a.clo1 + (int64_t)tx * kWinTX;
+    const NlmTile tile = nlm_tile_of_block(a, kWinTX, kWinTY);
+    const int64_t i2 = a.clo2 + tile.third, y0 = tile.y0, x0 = tile.x0;
 
     const int lx = (tid % 32) * 4, ly = (tid / 32) * 4;          // 4 x 4 pixels per thread
     const double nq = (double)(nz * (2 * r0 + 1) * (2 * r1 + 1) - 1);
@@ -386,6 +410,32 @@ typedef float nlm_f32x2 __attribute__((ext_vector_type(2)));
 constexpr int kRollRowsPerWave = 13;          // (32 + 2 * 10) rows over 4 waves
 constexpr int kRollR0Max = 10;
 
+// A staged row of the ring and the streaming form, for the kernels and the host that sizes their LDS: a thread
+// reads roll_nw(R) floats of it (whole float4s); the row pitch follows (a multiple of 4, >= 128 + 2 R).
+constexpr int roll_nw(int R) { return ((2 * R + 4) + 3) / 4 * 4; }
+constexpr int roll_pitch(int R) { return kWinTX - 4 + roll_nw(R); }
+// bytes of `planes` staged planes of kWinTY + 2 r0 rows
+constexpr size_t roll_lds(int planes, int r0, int R) { return (size_t)planes * (kWinTY + 2 * r0) * roll_pitch(R) * sizeof(float); }
+
+// source column of each staged column a lane handles (reflected in global coordinates; the clamps only keep
+// never-used corner positions inside the allocation)
+template <int R>
+__device__ __forceinline__ void nlm_col_offsets(const NlmTiledArgs &a, int64_t x0, int lane, int (&xoff)[3])
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        int m = reflect_once<int>(a.off1 + x0 - R + lane + 64 * j, a.G1) - (int)a.off1;
+        xoff[j] = m < 0 ? 0 : (m >= (int)a.N1 ? (int)a.N1 - 1 : m);
+    }
+}
+
+// local plane that stands for logical slice q of the window (reflected at the global ends of the third axis)
+__device__ __forceinline__ int64_t nlm_zmap(const NlmTiledArgs &a, int64_t q)
+{
+    int64_t zz = (int64_t)reflect_once<int>(a.offz + q, a.Gz) - a.offz;
+    return zz < 0 ? (int64_t)0 : (zz >= a.N2 ? a.N2 - 1 : zz);
+}
+
 // res[i] = (float)((double)s[i] / total) for four sums, without the divisions: s * (1/total) is
 // within 3 ulp of the correctly rounded quotient, so both round to the same float unless the
 // product sits within a few ulp of a float rounding boundary or leaves the normal float range --
@@ -418,20 +468,16 @@ __device__ __forceinline__ void nlm_div_rounded4(const float s[4], double total,
 template <int R1, int R0T>
 __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiledArgs a)
 {
-    constexpr int NW = ((2 * R1 + 4) + 3) / 4 * 4;     // floats a thread reads from one staged row
-    constexpr int COLSP = kWinTX - 4 + NW;             // row pitch (multiple of 4, >= COLS)
+    constexpr int NW = roll_nw(R1), COLSP = roll_pitch(R1);
     extern __shared__ __align__(16) unsigned char nd_smem_r[];
     float *lds = reinterpret_cast<float *>(nd_smem_r); // [nzr][rows][COLSP]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r0 = R0T >= 0 ? R0T : a.r0, rz = a.rz;
     const int rows = kWinTY + 2 * r0, psz = rows * COLSP, nzr = 2 * rz + 1;
 
-    int64_t b = blockIdx.x;
-    const int tx = (int)(b % a.tiles_x);
-    b /= a.tiles_x;
-    const int ty = (int)(b % a.tiles_y);
-    const int v = (int)(b / a.tiles_y);
-    const int64_t y0 = a.clo0 + (int64_t)ty * kWinTY, x0 = a.clo1 + (int64_t)tx * kWinTX;
+    const NlmTile tile = nlm_tile_of_block(a, kWinTX, kWinTY);
+    const int v = (int)tile.third;
+    const int64_t y0 = tile.y0, x0 = tile.x0;
     const int lx = (tid % 32) * 4, ly = (tid / 32) * 4;
 
     const double nq = (double)(nzr * (2 * r0 + 1) * (2 * R1 + 1) - 1);
@@ -441,14 +487,8 @@ __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiled
     const double total = nq + wself;
     const double inv_total = 1.0 / total;
 
-    // source column of each staged column this lane handles (whole-sample reflection in global
-    // coordinates; the clamps only keep never-used corner positions inside the allocation)
     int xoff[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        int m = reflect_once<int>(a.off1 + x0 - R1 + lane + 64 * j, a.G1) - (int)a.off1;
-        xoff[j] = m < 0 ? 0 : (m >= (int)a.N1 ? (int)a.N1 - 1 : m);
-    }
+    nlm_col_offsets<R1>(a, x0, lane, xoff);
     const float *base = a.arr + (int64_t)v * a.si3;
     const int64_t gy0 = a.off0 + y0 - r0;
 
@@ -481,11 +521,6 @@ __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiled
             }
         }
     };
-    // local plane that stands for logical slice q of the window
-    auto zmap = [&](int64_t q) {
-        int64_t zz = (int64_t)reflect_once<int>(a.offz + q, a.Gz) - a.offz;
-        return zz < 0 ? (int64_t)0 : (zz >= a.N2 ? a.N2 - 1 : zz);
-    };
 
     {
         const int64_t lo = a.clo2 - rz < 0 ? 0 : a.clo2 - rz;
@@ -517,6 +552,8 @@ __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiled
         // leaves a running sum that started at +0.0 unchanged bit for bit.
         auto row_step = [&](const float *P, int ry, bool cplane, auto full) {
             constexpr bool FULL = decltype(full)::value;     // both outputs of both pairs hold this row
+            // (The row read and the pair addition are spelled out here and in the streaming form: as shared routines
+            //  they cost the R0T = -1 forms 184 - 220 registers instead of 161 - 183, profiles/nlmeans_steps_codeobj.txt.)
             float w[NW];
             const float4 *rp = reinterpret_cast<const float4 *>(P + ry * COLSP);
 #pragma unroll
@@ -559,7 +596,7 @@ __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiled
         // the reference's visiting order: third-axis offset outermost when it is a window axis,
         // then rows, columns innermost; the centre is added last
         for (int dz = 0; dz < nzr; ++dz) {
-            const float *P = lds + (int)(zmap(i2 + dz - rz) % nzr) * psz + ly * COLSP + lx;
+            const float *P = lds + (int)(nlm_zmap(a, i2 + dz - rz) % nzr) * psz + ly * COLSP + lx;
             const bool cplane = (dz == rz);
             if (R0T >= 0) {
 #pragma unroll
@@ -592,6 +629,7 @@ __global__ void __launch_bounds__(256) nlmeans_window_roll_kernel(const NlmTiled
                         sv[i] = (float)((double)ws + (wself * (double)C[py * COLSP + i]));
                     }
                     nlm_div_rounded4(sv, total, inv_total, res);
+                    // (spelled out in both forms: as one routine the store costs the streaming form 2 - 4 registers)
                     float *o = a.out + i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x0 + lx;
                     if (vec_ok && x0 + lx + 3 < a.chi1) {
                         *reinterpret_cast<float4 *>(o) = make_float4(res[0], res[1], res[2], res[3]);
@@ -635,8 +673,7 @@ template <int R, int OY, int WPE>
 __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream3_kernel(const NlmTiledArgs a)
 {
     constexpr int NT = 32 * (kWinTY / OY), NWAVES = NT / 64;
-    constexpr int NW = ((2 * R + 4) + 3) / 4 * 4;      // floats a thread reads from one staged row
-    constexpr int COLSP = kWinTX - 4 + NW;             // row pitch (multiple of 4)
+    constexpr int NW = roll_nw(R), COLSP = roll_pitch(R);
     constexpr int ROWS = kWinTY + 2 * R;
     constexpr int PSZ = ROWS * COLSP;
     constexpr int NPRE = (ROWS + NWAVES - 1) / NWAVES; // staged rows per wave
@@ -645,12 +682,9 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    int64_t b = blockIdx.x;
-    const int tx = (int)(b % a.tiles_x);
-    b /= a.tiles_x;
-    const int ty = (int)(b % a.tiles_y);
-    const int v = (int)(b / a.tiles_y);
-    const int64_t y0 = a.clo0 + (int64_t)ty * kWinTY, x0 = a.clo1 + (int64_t)tx * kWinTX;
+    const NlmTile tile = nlm_tile_of_block(a, kWinTX, kWinTY);
+    const int v = (int)tile.third;
+    const int64_t y0 = tile.y0, x0 = tile.x0;
     const int lx = (tid % 32) * 4, ly = (tid / 32) * OY;
 
     const double nq = (double)(3 * (2 * R + 1) * (2 * R + 1) - 1);
@@ -662,11 +696,9 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
     // A descriptor per plane, a wave-uniform row offset (scalar) and one 32-bit byte offset per
     // lane and staged column.  (Row offsets inside a plane fit 31 bits: checked on the host.)
     int xoff[3];
+    nlm_col_offsets<R>(a, x0, lane, xoff);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        int m = reflect_once<int>(a.off1 + x0 - R + lane + 64 * j, a.G1) - (int)a.off1;
-        xoff[j] = 4 * (m < 0 ? 0 : (m >= (int)a.N1 ? (int)a.N1 - 1 : m));
-    }
+    for (int j = 0; j < 3; ++j) xoff[j] = 4 * xoff[j];
     int roff[NPRE];
     {
         const int64_t gy0 = a.off0 + y0 - R;
@@ -692,14 +724,9 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
             }
         }
     };
-    auto zmap = [&](int64_t q) {
-        int64_t zz = (int64_t)reflect_once<int>(a.offz + q, a.Gz) - a.offz;
-        return zz < 0 ? (int64_t)0 : (zz >= a.N2 ? a.N2 - 1 : zz);
-    };
-
     const int64_t first = a.clo2, last = a.chi2 - 1;
     const int nsteps = (int)(last - first) + 3;
-    stage(zmap(first - 1), 0);
+    stage(nlm_zmap(a, first - 1), 0);
     lds_dma_wait();
     __syncthreads();
 
@@ -722,11 +749,11 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
     // the last two steps start no slice: their `c` sums would be thrown away -- 784 of the 16 016 vector
     // additions a thread issues per tile at 24 dates.
     int slot = 0;
-    int64_t pcur = zmap(first - 1);
+    int64_t pcur = nlm_zmap(a, first - 1);
     for (int s = 0; s < nsteps; ++s) {
         const int64_t q = first - 1 + s;
         const bool has_next = s + 1 < nsteps;
-        const int64_t pnext = has_next ? zmap(q + 1) : pcur;
+        const int64_t pnext = has_next ? nlm_zmap(a, q + 1) : pcur;
         const bool same = pnext == pcur;
         if (has_next && !same) stage(pnext, slot ^ 1);
         const bool do_ab = s >= 1, do_c = s + 2 < nsteps;
@@ -819,6 +846,7 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
                     for (int i = 0; i < 4; ++i)
                         sv[i] = (float)((double)ab[py][i].x + (wself * (double)cen[py][i]));
                     nlm_div_rounded4(sv, total, inv_total, res);
+                    // (spelled out in both forms: as one routine the store costs the streaming form 2 - 4 registers)
                     float *o = a.out + i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x0 + lx;
                     if (vec_ok && x0 + lx + 3 < a.chi1) {
                         *reinterpret_cast<float4 *>(o) = make_float4(res[0], res[1], res[2], res[3]);
@@ -857,17 +885,13 @@ __global__ void __launch_bounds__(32 * (kWinTY / OY), WPE) nlmeans_window_stream
 
 static bool launch_stream3(const NlmTiledArgs &a, int64_t nb, hipStream_t stream)
 {
-    auto lds = [](int R) {
-        const size_t nw = ((2 * (size_t)R + 4) + 3) / 4 * 4;
-        return 2 * (size_t)(kWinTY + 2 * R) * (kWinTX - 4 + nw) * sizeof(float);
-    };
     // 512 threads x (2 x 4) outputs; a 256-thread form (4 x 4 outputs per thread, half the waves)
     // measured the same to 1 % -- the kernel is bound by VALU issue, not by latency
     // (profiles/r02_nlmeans_window_pmc.txt)
     const dim3 grid((unsigned)nb);
     return pick_eq<1, 2, 3, 4, 5>(a.r1, [&](auto R) {
-        hipLaunchKernelGGL((nlmeans_window_stream3_kernel<decltype(R)::value, 2, 4>), grid, dim3(512), lds(decltype(R)::value),
-                           stream, a);
+        hipLaunchKernelGGL((nlmeans_window_stream3_kernel<decltype(R)::value, 2, 4>), grid, dim3(512),
+                           roll_lds(2, decltype(R)::value, decltype(R)::value), stream, a);
     });
 }
 
@@ -904,17 +928,21 @@ static bool launch_roll_r1(const NlmTiledArgs &a, int64_t nb, size_t lds, hipStr
 // variable (nd/_filters.pyx:386-420; the self weight is 1, NaN or -- when n_eff - 1 == 0 -- the error
 // case, which is left to the full evaluation).  Nodata regions therefore cost one look at the patch
 // instead of the whole search window in double precision.
-template <int F, int V>
-__device__ __forceinline__ bool nlm_own_patch_nan(const float *lds, int plane, int cols, int py, int px)
+// (lds[plane][v][row][col] with the pitches pstride, vstride, cols; pz0: the first patch plane.  The planar kernels
+//  pass FZ = 0, pz0 = 0: one plane.)
+template <int F, int FZ, int V>
+__device__ __forceinline__ bool nlm_own_patch_nan(const float *lds, int pz0, int pstride, int vstride, int cols,
+                                                  int py, int px)
 {
     bool nan = false;
-    for (int i = -F; i <= F; ++i)
-        for (int j = -F; j <= F; ++j)
+    for (int z = 0; z < 2 * FZ + 1; ++z)
+        for (int i = -F; i <= F; ++i)
+            for (int j = -F; j <= F; ++j)
 #pragma unroll
-            for (int v = 0; v < V; ++v) {
-                const float c = lds[v * plane + (py + i) * cols + px + j];
-                nan = nan || (c != c);
-            }
+                for (int v = 0; v < V; ++v) {
+                    const float c = lds[(pz0 + z) * pstride + v * vstride + (py + i) * cols + px + j];
+                    nan = nan || (c != c);
+                }
     return nan;
 }
 
@@ -932,18 +960,14 @@ __global__ void __launch_bounds__(256) nlmeans_patch_kernel(const NlmTiledArgs a
     int *ymap = reinterpret_cast<int *>(lds + V * rows * cols);
     int *xmap = ymap + rows;
 
-    int64_t b = blockIdx.x;
-    const int tx = (int)(b % a.tiles_x);
-    b /= a.tiles_x;
-    const int ty = (int)(b % a.tiles_y);
-    const int64_t i2 = a.clo2 + b / a.tiles_y;
-    const int64_t y0 = a.clo0 + (int64_t)ty * TY, x0 = a.clo1 + (int64_t)tx * TX;
+    const NlmTile tile = nlm_tile_of_block(a, TX, TY);
+    const int64_t i2 = a.clo2 + tile.third, y0 = tile.y0, x0 = tile.x0;
 
 #pragma unroll
     for (int v = 0; v < V; ++v) {
         __syncthreads();
-        nlm_stage(a, lds + v * rows * cols, ymap, xmap, rows, cols, a.off0 + y0 - halo0,
-                  a.off1 + x0 - halo1, i2, v, tid);
+        nlm_stage_t<float>(a, lds + v * rows * cols, ymap, xmap, rows, cols, a.off0 + y0 - halo0,
+                           a.off1 + x0 - halo1, i2, v, tid);
     }
 
     // this thread: column `lane`, rows wave*TYW .. wave*TYW + TYW - 1 of the tile
@@ -1039,6 +1063,8 @@ __global__ void __launch_bounds__(256) nlmeans_patch_kernel(const NlmTiledArgs a
         if (y < a.chi0 && x < a.chi1) {
             if (((nan_mask >> p) & 1u) && !(a.n_eff >= 0 && (a.n_eff - 1.0) == 0)) {
                 // a NaN patch distance: NaN weight, NaN sums, NaN result (nd/_filters.pyx:386-420)
+                // (nlm_store_nan written out: the call here raised sgpr spills or registers of some instantiations,
+                //  profiles/nlmeans_steps_codeobj.txt)
 #pragma unroll
                 for (int v = 0; v < V; ++v)
                     a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = __builtin_nanf("");
@@ -1056,10 +1082,7 @@ __global__ void __launch_bounds__(256) nlmeans_patch_kernel(const NlmTiledArgs a
                 const double total = tw[p] + wself;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const float c = lds[v * rows * cols + (cy0 + p) * cols + cx];
-                    const float sfin = (float)((double)ws[p][v] + (wself * (double)c));
-                    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] =
-                        (float)((double)sfin / total);
+                    nlm_finish(a, i2, v, y, x, ws[p][v], lds[v * rows * cols + (cy0 + p) * cols + cx], wself, total);
                 }
             }
         }
@@ -1068,12 +1091,13 @@ __global__ void __launch_bounds__(256) nlmeans_patch_kernel(const NlmTiledArgs a
         for (int p = 0; p < TYW; ++p) {
             if (!((exact_mask >> p) & 1u)) continue;
             // nd/_filters.pyx:363-420 for this one pixel, from the staged tile
+            // (Three copies: here, and in the other two patch kernels.  One routine for all three, nlm_exact_pixel, raised
+            //  register figures of 28 instantiations, profiles/nlmeans_steps_codeobj.txt; its steps -- NaN test, weight,
+            //  finish -- are shared.  A fix to this loop nest is a fix to three.)
             const int py = cy0 + p;
-            if (!(a.n_eff >= 0 && (a.n_eff - 1.0) == 0) && nlm_own_patch_nan<F, V>(lds, rows * cols, cols, py, cx)) {
+            if (!(a.n_eff >= 0 && (a.n_eff - 1.0) == 0) && nlm_own_patch_nan<F, 0, V>(lds, 0, 0, rows * cols, cols, py, cx)) {
                 const int64_t y = y0 + wave * TYW + p;
-#pragma unroll
-                for (int v = 0; v < V; ++v)
-                    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = __builtin_nanf("");
+                nlm_store_nan<V>(a, i2, y, x);
                 continue;
             }
             double t_w = 0.0, t_sq = 0.0, m_w = 0.0;
@@ -1094,13 +1118,7 @@ __global__ void __launch_bounds__(256) nlmeans_patch_kernel(const NlmTiledArgs a
                                 const float sq = df * df;
                                 dsq = dsq + (double)sq;
                             }
-                    dsq = dsq / (double)a.dsq_norm;
-                    const double t = dsq - a.two_sigma2;
-                    const double m = (0.0 > t) ? 0.0 : t;
-                    const double w = exp((-m) / a.h2);
-                    t_w = t_w + w;
-                    t_sq = t_sq + (w * w);
-                    if (w > m_w) m_w = w;
+                    const double w = nlm_weight_exact(dsq, (double)a.dsq_norm, a.two_sigma2, a.h2, &t_w, &t_sq, &m_w);
 #pragma unroll
                     for (int v = 0; v < V; ++v)
                         wsum[v] = (float)((double)wsum[v] +
@@ -1113,10 +1131,7 @@ __global__ void __launch_bounds__(256) nlmeans_patch_kernel(const NlmTiledArgs a
                 const int64_t y = y0 + wave * TYW + p;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const float c = lds[v * rows * cols + py * cols + cx];
-                    const float sfin = (float)((double)wsum[v] + (wself * (double)c));
-                    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] =
-                        (float)((double)sfin / total);
+                    nlm_finish(a, i2, v, y, x, wsum[v], lds[v * rows * cols + py * cols + cx], wself, total);
                 }
             }
         }
@@ -1140,7 +1155,6 @@ __global__ void __launch_bounds__(256) nlmeans_patch_kernel(const NlmTiledArgs a
 // float32 as well; total weights are summed in float32 per search row and in double across rows.
 // Differences from the reference's double arithmetic stay <= ~1e-6 relative (tests: 1e-5).
 // Pixels whose weights all vanish in float32 are recomputed exactly as in nlmeans_patch_kernel.
-typedef float f2_t __attribute__((ext_vector_type(2)));
 
 template <int V>
 struct Patch2Rows {
@@ -1151,24 +1165,26 @@ struct Patch2Geom {
     static constexpr int HL = (F == 3) ? 2 : (F >= 1 ? 1 : 0);     // feeder lanes on each side
     static constexpr int TX = 2 * (64 - 2 * HL);                   // columns a wave yields
 };
+// left / right margin of the staged tile: even, >= r1 + F and >= r1 + 2 HL (kernel and host)
+constexpr int patch2_margin(int r1, int HL) { return r1 + 2 * HL + (r1 & 1); }
 
 // max of two float pairs, one v_max_f32 per component (gfx950 has no packed max; fmaxf() costs
 // three: it canonicalises both operands first).  A NaN operand is dropped (IEEE maxNum), which is
 // what the callers want: NaNs are tracked separately (`ssum`).
-__device__ __forceinline__ f2_t pk_max(const f2_t a, const f2_t b)
+__device__ __forceinline__ nlm_f32x2 pk_max(const nlm_f32x2 a, const nlm_f32x2 b)
 {
-    f2_t d;
+    nlm_f32x2 d;
     asm("v_max_f32 %0, %1, %2" : "=v"(d.x) : "v"(a.x), "v"(b.x));
     asm("v_max_f32 %0, %1, %2" : "=v"(d.y) : "v"(a.y), "v"(b.y));
     return d;
 }
 
 template <int F>
-__device__ __forceinline__ f2_t patch2_row_sums(const f2_t e)
+__device__ __forceinline__ nlm_f32x2 patch2_row_sums(const nlm_f32x2 e)
 {
     if (F == 0) return e;
     const float P = e.x + e.y;
-    f2_t hs;
+    nlm_f32x2 hs;
     if (F == 1) {
         hs.x = lane_from_prev(e.y) + P;
         hs.y = P + lane_from_next(e.x);
@@ -1206,30 +1222,26 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
     const int lane = tid & 63, wave = tid >> 6;
     const int r0 = a.r0, r1 = a.r1;
     const int halo0 = r0 + F;
-    // left / right margin: even, >= r1 + F and >= r1 + 2 HL
+    // left / right margin: patch2_margin(r1, HL), written out (the call moved the registers of the MC = 0 forms)
     const int M = MC ? MC : r1 + 2 * HL + (r1 & 1);
     const int cols = TX + 2 * M, rows = TY + 2 * halo0;
     float *lds = reinterpret_cast<float *>(nd_smem_n);               // [V][rows][cols]
     int *ymap = reinterpret_cast<int *>(lds + V * rows * cols);
     int *xmap = ymap + rows;
 
-    int64_t b = blockIdx.x;
-    const int tx = (int)(b % a.tiles_x);
-    b /= a.tiles_x;
-    const int ty = (int)(b % a.tiles_y);
-    const int64_t i2 = a.clo2 + b / a.tiles_y;
     // Lane pairs sit on GLOBAL (even, odd) columns whatever the tile or the written range: the two
     // columns of a pair add their row sums in different groupings, and a pixel's value must not
     // depend on how the raster was cut (multi-GPU row blocks, halo tiles).
     const int64_t xs = a.clo1 - ((a.off1 + a.clo1) & 1);
-    const int64_t y0 = a.clo0 + (int64_t)ty * TY, x0 = xs + (int64_t)tx * TX;
+    const NlmTile tile = nlm_tile_of_block(a, TX, TY, xs);
+    const int64_t i2 = a.clo2 + tile.third, y0 = tile.y0, x0 = tile.x0;
 
     bool nonfinite = false;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
         __syncthreads();
-        nlm_stage(a, lds + v * rows * cols, ymap, xmap, rows, cols, a.off0 + y0 - halo0,
-                  a.off1 + x0 - M, i2, v, tid, &nonfinite);
+        nlm_stage_t<float>(a, lds + v * rows * cols, ymap, xmap, rows, cols, a.off0 + y0 - halo0,
+                           a.off1 + x0 - M, i2, v, tid, &nonfinite);
     }
     // A patch sum can only be NaN when the tile holds a NaN or an infinity (squares of finite
     // differences are finite or +inf, and +inf gives the weight 0 like the reference's exp(-inf)):
@@ -1241,30 +1253,30 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
     const int cx = M + 2 * (lane - HL);
     const int cy0 = halo0 + wave * TYW;
     double tw[TYW][2], tsq[NEFF ? TYW : 1][2];
-    f2_t wmax[TYW], ws[TYW][V];
+    nlm_f32x2 wmax[TYW], ws[TYW][V];
 #pragma unroll
     for (int p = 0; p < TYW; ++p) {
         tw[p][0] = tw[p][1] = 0.0;
         if (NEFF) tsq[p][0] = tsq[p][1] = 0.0;
-        wmax[p] = (f2_t){0.f, 0.f};
+        wmax[p] = (nlm_f32x2){0.f, 0.f};
 #pragma unroll
-        for (int v = 0; v < V; ++v) ws[p][v] = (f2_t){0.f, 0.f};
+        for (int v = 0; v < V; ++v) ws[p][v] = (nlm_f32x2){0.f, 0.f};
     }
     // the reference divides in double; reciprocals in float32 differ by ~1e-7 relative
     const float exp2_scale = (float)(-1.4426950408889634 / a.h2);      // w = 2^(m * exp2_scale)
     const float c1 = (float)((double)exp2_scale / (double)a.dsq_norm);
     const float c0 = (float)(-(double)a.two_sigma2 * (double)exp2_scale);
-    const f2_t exp_c1 = (f2_t){c1, c1}, exp_c0 = (f2_t){c0, c0};
-    const f2_t zero2 = (f2_t){0.f, 0.f};
-    f2_t ssum[TYW];
+    const nlm_f32x2 exp_c1 = (nlm_f32x2){c1, c1}, exp_c0 = (nlm_f32x2){c0, c0};
+    const nlm_f32x2 zero2 = (nlm_f32x2){0.f, 0.f};
+    nlm_f32x2 ssum[TYW];
 #pragma unroll
     for (int p = 0; p < TYW; ++p) ssum[p] = zero2;
 
     auto search = [&](auto track_nan) {
     for (int dy = -r0; dy <= r0; ++dy) {
-        f2_t twf[TYW];                    // NEFF = false: float32 partial sums of this search row
+        nlm_f32x2 twf[TYW];                    // NEFF = false: float32 partial sums of this search row
 #pragma unroll
-        for (int p = 0; p < TYW; ++p) twf[p] = (f2_t){0.f, 0.f};
+        for (int p = 0; p < TYW; ++p) twf[p] = (nlm_f32x2){0.f, 0.f};
         // three search offsets per trip: their LDS reads then share one address register per row
         // (the offsets along x are immediates); trips beyond r1 and the centre are skipped
         for (int dx0 = -r1; dx0 <= r1; dx0 += 3)
@@ -1272,19 +1284,19 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
         for (int du = 0; du < 3; ++du) {
             const int dx = dx0 + du;
             if (dx > r1 || (dy == 0 && dx == 0)) continue;
-            f2_t H[2 * F + 1], Q[2 * F + 1];      // rings: row sums, and sums of two adjacent rows
+            nlm_f32x2 H[2 * F + 1], Q[2 * F + 1];      // rings: row sums, and sums of two adjacent rows
 #pragma unroll
             for (int s = 0; s < TYW + 2 * F; ++s) {
                 // squared differences of this lane's two columns at image row (cy0 - F + s)
                 const int rr = cy0 - F + s;
-                f2_t e = (f2_t){0.f, 0.f};
+                nlm_f32x2 e = (nlm_f32x2){0.f, 0.f};
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
                     const float *pa = lds + v * rows * cols + rr * cols + cx;
                     const float *qa = pa + dy * cols + dx;
-                    const f2_t pv = *reinterpret_cast<const f2_t *>(pa);      // 8-byte aligned
-                    const f2_t qv = (f2_t){qa[0], qa[1]};
-                    const f2_t df = pv - qv;
+                    const nlm_f32x2 pv = *reinterpret_cast<const nlm_f32x2 *>(pa);      // 8-byte aligned
+                    const nlm_f32x2 qv = (nlm_f32x2){qa[0], qa[1]};
+                    const nlm_f32x2 df = pv - qv;
                     e = __builtin_elementwise_fma(df, df, e);
                 }
                 constexpr int NR = 2 * F + 1;
@@ -1295,7 +1307,7 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
                     // the patch sum: rows p .. p + 2F, always grouped the same way relative to the
                     // pixel's own row (pairs from the top, last row alone) -- the ring position of a
                     // row depends on where the tile starts, the order of the additions must not
-                    f2_t S;
+                    nlm_f32x2 S;
                     if (F == 0) {
                         S = H[s % NR];
                     } else if (F == 1) {
@@ -1313,8 +1325,8 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
                     // remembers it for the exact path below).  The s_nop covers the wait state a
                     // transcendental result needs before an ordinary vector instruction reads it,
                     // which the compiler does not insert around inline assembly.
-                    const f2_t ma = __builtin_elementwise_fma(S, exp_c1, exp_c0);
-                    f2_t w;
+                    const nlm_f32x2 ma = __builtin_elementwise_fma(S, exp_c1, exp_c0);
+                    nlm_f32x2 w;
                     asm("v_exp_f32_e64 %0, %2 clamp\n\tv_exp_f32_e64 %1, %3 clamp\n\ts_nop 0"
                         : "=&v"(w.x), "=v"(w.y) : "v"(ma.x), "v"(ma.y));
                     if (NEFF) {
@@ -1332,7 +1344,7 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
 #pragma unroll
                     for (int v = 0; v < V; ++v) {
                         const float *ap = lds + v * rows * cols + qr * cols + qc;
-                        const f2_t av = (f2_t){ap[0], ap[1]};
+                        const nlm_f32x2 av = (nlm_f32x2){ap[0], ap[1]};
                         // (float)((double)ws + (double)w * (double)a): the product of two floats is
                         // exact in double, so the fused multiply-add rounds to the same value
                         ws[p][v] = __builtin_elementwise_fma(w, av, ws[p][v]);
@@ -1373,6 +1385,8 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
             if (!(sp == sp) && nan_is_final) {
                 // some patch distance of this pixel is NaN: so are that weight, both weight sums and
                 // every weighted sum in the reference (nd/_filters.pyx:386-420) -- the result is NaN
+                // (nlm_store_nan written out: the call here raised sgpr spills or registers of some instantiations,
+                //  profiles/nlmeans_steps_codeobj.txt)
 #pragma unroll
                 for (int v = 0; v < V; ++v)
                     a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = __builtin_nanf("");
@@ -1390,10 +1404,7 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
                     const float cv = lds[v * rows * cols + (cy0 + p) * cols + cx + c];
-                    const float wsv = c ? ws[p][v].y : ws[p][v].x;
-                    const float sfin = (float)((double)wsv + (wself * (double)cv));
-                    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] =
-                        (float)((double)sfin / total);
+                    nlm_finish(a, i2, v, y, x, c ? ws[p][v].y : ws[p][v].x, cv, wself, total);
                 }
             }
         }
@@ -1402,14 +1413,15 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
         for (int pc = 0; pc < 2 * TYW; ++pc) {
             if (!((exact_mask >> pc) & 1u)) continue;
             // nd/_filters.pyx:363-420 for this one pixel, from the staged tile
+            // (Three copies: here, and in the other two patch kernels.  One routine for all three, nlm_exact_pixel, raised
+            //  register figures of 28 instantiations, profiles/nlmeans_steps_codeobj.txt; its steps -- NaN test, weight,
+            //  finish -- are shared.  A fix to this loop nest is a fix to three.)
             const int p = pc >> 1, c = pc & 1;
             const int py = cy0 + p, pxc = cx + c;
-            if (!(a.n_eff >= 0 && (a.n_eff - 1.0) == 0) && nlm_own_patch_nan<F, V>(lds, rows * cols, cols, py, pxc)) {
+            if (!(a.n_eff >= 0 && (a.n_eff - 1.0) == 0) && nlm_own_patch_nan<F, 0, V>(lds, 0, 0, rows * cols, cols, py, pxc)) {
                 const int64_t y = y0 + wave * TYW + p;
                 const int64_t x = x0 + 2 * (lane - HL) + c;
-#pragma unroll
-                for (int v = 0; v < V; ++v)
-                    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = __builtin_nanf("");
+                nlm_store_nan<V>(a, i2, y, x);
                 continue;
             }
             double t_w = 0.0, t_sq = 0.0, m_w = 0.0;
@@ -1430,13 +1442,7 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
                                 const float sq = df * df;
                                 dsq = dsq + (double)sq;
                             }
-                    dsq = dsq / (double)a.dsq_norm;
-                    const double t = dsq - a.two_sigma2;
-                    const double m = (0.0 > t) ? 0.0 : t;
-                    const double w = exp((-m) / a.h2);
-                    t_w = t_w + w;
-                    t_sq = t_sq + (w * w);
-                    if (w > m_w) m_w = w;
+                    const double w = nlm_weight_exact(dsq, (double)a.dsq_norm, a.two_sigma2, a.h2, &t_w, &t_sq, &m_w);
 #pragma unroll
                     for (int v = 0; v < V; ++v)
                         wsum[v] = (float)((double)wsum[v] +
@@ -1450,10 +1456,7 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
                 const int64_t x = x0 + 2 * (lane - HL) + c;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const float cv = lds[v * rows * cols + py * cols + pxc];
-                    const float sfin = (float)((double)wsum[v] + (wself * (double)cv));
-                    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] =
-                        (float)((double)sfin / total);
+                    nlm_finish(a, i2, v, y, x, wsum[v], lds[v * rows * cols + py * cols + pxc], wself, total);
                 }
             }
         }
@@ -1461,15 +1464,24 @@ __global__ void __launch_bounds__(256, V == 1 ? 3 : 2) nlmeans_patch2_kernel(con
 }
 
 // patches of 3 x 3, 5 x 5 and 7 x 7 (f = 1, 2, 3), one to four variables; false if nothing was launched
-static bool launch_patch2(const NlmTiledArgs &a, int f, int64_t nslices, size_t lds, hipStream_t stream)
+// (the tile is sized here, from the kernel's own geometry; `a` is a copy, its tile counts are this form's)
+static bool launch_patch2(NlmTiledArgs a, int f, hipStream_t stream)
 {
-    const int64_t nb = (int64_t)a.tiles_x * a.tiles_y * nslices;
+    const int64_t ey = a.chi0 - a.clo0, ex = a.chi1 - a.clo1, nsl = a.chi2 - a.clo2;
     bool ok = false;
     auto patch = [&](auto FF) {
-        constexpr int F = decltype(FF)::value;
-        const bool mc = a.r1 + 2 * Patch2Geom<F>::HL + (a.r1 & 1) <= kPatch2Margin;    // as the host sized the tile
+        constexpr int F = decltype(FF)::value, HL = Patch2Geom<F>::HL, TX = Patch2Geom<F>::TX;
+        const bool mc = patch2_margin(a.r1, HL) <= kPatch2Margin;      // the constant-pitch instantiation
+        const size_t m = mc ? kPatch2Margin : patch2_margin(a.r1, HL);
         pick_eq<1, 2, 3, 4>(a.nvars, [&](auto VV) {
             constexpr int V = decltype(VV)::value, TYW = Patch2Rows<V>::TYW;
+            const size_t cols = TX + 2 * m, rows = 4 * (size_t)TYW + 2 * (size_t)(a.r0 + F);
+            const size_t lds = V * rows * cols * sizeof(float) + (rows + cols) * sizeof(int);
+            a.tiles_x = (int)ceil_div(ex + 1, TX);        // + 1: the tiles start on an even global column
+            a.tiles_y = (int)ceil_div(ey, 4 * TYW);
+            const int64_t nb = (int64_t)a.tiles_x * a.tiles_y * nsl;
+            if (lds > kBigLds || nb > 0x7fffffffLL) return;
+            KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
             pick(a.n_eff >= 0, [&](auto NEFF) {
                 pick(mc, [&](auto MC) {
                     ok = launch_lds(&nlmeans_patch2_kernel<F, V, TYW, decltype(NEFF)::value, decltype(MC)::value ? kPatch2Margin : 0>,
@@ -1499,7 +1511,6 @@ static bool launch_patch(const NlmTiledArgs &a, int f, int64_t nslices, size_t l
     return ok;
 }
 
-// Try a tiled form; 1 = launched, 0 = not applicable.
 // ---- patch_mode 1 with a window along the third axis (round 6) ---------------------------------
 // The signed patch distances of a search with an extent along time -- NLMeansFilter(dims=('time', 'y',
 // 'x'), r=(1, 3, 3), f=1), the tutorial's filter (examples/tutorial_s1.ipynb cell 11), in the mode the
@@ -1520,22 +1531,6 @@ static bool launch_patch(const NlmTiledArgs &a, int f, int64_t nslices, size_t l
 //     order and per-step rounding to float32); pixels with a non-finite value within reach, with all
 //     float32 weights vanishing, or with an ill-conditioned n_eff equation are recomputed one by one in
 //     double, in the reference's order, from the staged planes.
-template <int F, int FZ, int V>
-__device__ __forceinline__ bool nlm_own_patch_nan3(const float *lds, int pz0, int pstride, int vstride, int cols,
-                                                   int py, int px)
-{
-    bool nan = false;
-    for (int z = 0; z < 2 * FZ + 1; ++z)
-        for (int i = -F; i <= F; ++i)
-            for (int j = -F; j <= F; ++j)
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    const float c = lds[(pz0 + z) * pstride + v * vstride + (py + i) * cols + px + j];
-                    nan = nan || (c != c);
-                }
-    return nan;
-}
-
 template <int F>
 __device__ __forceinline__ float nlm_row_sum_lanes(const float e)
 {
@@ -1573,12 +1568,8 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
     int *ymap = reinterpret_cast<int *>(lds + np * pstride);
     int *xmap = ymap + rows;
 
-    int64_t b = blockIdx.x;
-    const int tx = (int)(b % a.tiles_x);
-    b /= a.tiles_x;
-    const int ty = (int)(b % a.tiles_y);
-    const int64_t i2 = a.clo2 + b / a.tiles_y;
-    const int64_t y0 = a.clo0 + (int64_t)ty * TY, x0 = a.clo1 + (int64_t)tx * TXO;
+    const NlmTile tile = nlm_tile_of_block(a, TXO, TY);
+    const int64_t i2 = a.clo2 + tile.third, y0 = tile.y0, x0 = tile.x0;
 
     bool nonfinite_here = false;
     for (int pz = 0; pz < np; ++pz) {
@@ -1587,8 +1578,8 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             __syncthreads();
-            nlm_stage(a, lds + pz * pstride + v * vstride, ymap, xmap, rows, cols, a.off0 + y0 - (RMAX + F),
-                      a.off1 + x0 - F - RMAX, zi, v, tid, &nonfinite_here);
+            nlm_stage_t<float>(a, lds + pz * pstride + v * vstride, ymap, xmap, rows, cols,
+                               a.off0 + y0 - (RMAX + F), a.off1 + x0 - F - RMAX, zi, v, tid, &nonfinite_here);
         }
     }
     // (any non-finite value in the block's planes: every pixel takes the exact path -- rare, and it spares
@@ -1751,9 +1742,7 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
                 const double total = tw[p_] + wself;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const float c = P[F + p_][FZ][v];
-                    const float sfin = (float)((double)ws[p_][v] + (wself * (double)c));
-                    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = (float)((double)sfin / total);
+                    nlm_finish(a, i2, v, y, x, ws[p_][v], P[F + p_][FZ][v], wself, total);
                 }
             }
         }
@@ -1762,11 +1751,16 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
         for (int p_ = 0; p_ < TYW; ++p_) {
             if (!((exact_mask >> p_) & 1u)) continue;
             // nd/_filters.pyx:363-420 for this one pixel, from the staged planes, in double
+            // (Three copies: here, and in the other two patch kernels.  One routine for all three, nlm_exact_pixel, raised
+            //  register figures of 28 instantiations, profiles/nlmeans_steps_codeobj.txt; its steps -- NaN test, weight,
+            //  finish -- are shared.  A fix to this loop nest is a fix to three.)
             const int py = cy0 + p_;
             const int64_t y = y0 + wave * TYW + p_;
             if (!(a.n_eff >= 0 && (a.n_eff - 1.0) == 0) &&
-                nlm_own_patch_nan3<F, FZ, V>(lds, pzc - FZ, pstride, vstride, cols, py, cx)) {
+                nlm_own_patch_nan<F, FZ, V>(lds, pzc - FZ, pstride, vstride, cols, py, cx)) {
                 // a NaN in the pixel's own patch: every distance, weight and sum is NaN (nd/_filters.pyx:386-420)
+                // (nlm_store_nan written out: the call here raised sgpr spills or registers of some instantiations,
+                //  profiles/nlmeans_steps_codeobj.txt)
 #pragma unroll
                 for (int v = 0; v < V; ++v)
                     a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = __builtin_nanf("");
@@ -1792,13 +1786,7 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
                                         const float sq = df * df;
                                         dsq = dsq + (double)sq;
                                     }
-                        dsq = dsq / (double)a.dsq_norm;
-                        const double t = dsq - a.two_sigma2;
-                        const double m = (0.0 > t) ? 0.0 : t;
-                        const double w = exp((-m) / a.h2);
-                        t_w = t_w + w;
-                        t_sq = t_sq + (w * w);
-                        if (w > m_w) m_w = w;
+                        const double w = nlm_weight_exact(dsq, (double)a.dsq_norm, a.two_sigma2, a.h2, &t_w, &t_sq, &m_w);
 #pragma unroll
                         for (int v = 0; v < V; ++v)
                             wsum[v] = (float)((double)wsum[v] +
@@ -1810,9 +1798,7 @@ __global__ void __launch_bounds__(256) nlmeans_patch3_kernel(const NlmTiledArgs 
                 const double total = t_w + wself;
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    const float c = lds[pzc * pstride + v * vstride + py * cols + cx];
-                    const float sfin = (float)((double)wsum[v] + (wself * (double)c));
-                    a.out[i2 * a.so2 + (int64_t)v * a.so3 + y * a.so0 + x] = (float)((double)sfin / total);
+                    nlm_finish(a, i2, v, y, x, wsum[v], lds[pzc * pstride + v * vstride + py * cols + cx], wself, total);
                 }
             }
         }
@@ -1846,27 +1832,127 @@ static bool launch_patch3(const NlmTiledArgs &a, int f, int fz, int tyw, int64_t
     return ok;
 }
 
-static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[3], int64_t nvars,
-                         const int64_t si[4], const int64_t so[4], const uint32_t r[3],
-                         const uint32_t f[3], double sigma, double h, double n_eff, int patch_mode,
-                         int neff_policy, int32_t *status_dev, const int64_t G[3],
-                         const int64_t toff[3], const int64_t clo[3], const int64_t chi[3],
-                         hipStream_t stream)
+// bytes of a patch3 tile: np planes of nvars variables, 4 tyw rows plus the halo the kernel lays out, and the two index maps
+static size_t patch3_lds(size_t np, size_t nvars, int tyw, int Fp)
+{
+    const size_t cols = 64 + 2 * (size_t)kPatch3RMax, rows = 4 * (size_t)tyw + 2 * (size_t)(kPatch3RMax + Fp);
+    return np * nvars * rows * cols * sizeof(float) + (rows + cols) * sizeof(int);
+}
+
+// The three regimes of the tiled forms.  Each takes the filled arguments (a copy: the tile counts are the
+// regime's own) and returns 1 = launched, 0 = nothing was launched, the per-pixel kernel takes the call.
+// uniform weights (patch_mode 0 with f > 0): the streaming form, then the ring, then the window kernel
+static int try_uniform(NlmTiledArgs a, bool f64, double sigma, double h, hipStream_t stream)
+{
+    const int64_t ey = a.chi0 - a.clo0, ex = a.chi1 - a.clo1, nsl = a.chi2 - a.clo2;
+    const int rz = a.rz;
+    // weight exp(-max(0 - 2 sigma^2, 0) / h^2) must be exactly 1
+    if (!(sigma == sigma) || !(h == h) || h == 0.0 || !(sigma * sigma < INFINITY)) return 0;
+    if (a.r1 > 16) return 0;
+    a.tiles_x = (int)ceil_div(ex, kWinTX);
+    a.tiles_y = (int)ceil_div(ey, kWinTY);
+    const int64_t nbr = (int64_t)a.tiles_x * a.tiles_y * a.nvars;       // a block per tile and variable
+    if (!f64 && rz == 1 && a.r0 == a.r1 && a.r1 >= 1 && a.r1 <= 5 &&
+        a.si0 >= 0 && (a.N0 * a.si0 + a.N1) * 4 < 0x7fffffffLL && nbr <= 0x7fffffffLL) {
+        KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
+        if (launch_stream3(a, nbr, stream)) return 1;
+    }
+    if (!f64 && a.r0 <= kRollR0Max && a.r1 <= 10) {
+        const size_t lds_r = roll_lds(2 * rz + 1, a.r0, a.r1);
+        if (lds_r <= kBigLds && nbr <= 0x7fffffffLL) {
+            KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
+            if (launch_roll_r1(a, nbr, lds_r, stream)) return 1;
+        }
+    }
+    const int64_t nb = (int64_t)a.tiles_x * a.tiles_y * nsl;
+    const size_t rows = kWinTY + 2 * a.r0, cols = kWinTX + 2 * a.r1;
+    const size_t lds = (size_t)(2 * rz + 1) * rows * cols * (f64 ? sizeof(double) : sizeof(float)) +
+                       (rows + cols) * sizeof(int);
+    // (float32 stays within the default limit; float64 may take up to kBigLds)
+    if (nb > 0x7fffffffLL || lds > (f64 ? kBigLds : 64 * 1024)) return 0;
+    KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
+    hipError_t e = hipSuccess;
+    pick(f64, [&](auto F64) {
+        using T = std::conditional_t<decltype(F64)::value, double, float>;
+        auto launch = [&](auto R) {
+            constexpr auto kernel = &nlmeans_window_kernel<T, decltype(R)::value>;
+            if (lds > 64 * 1024) e = allow_dynamic_lds(kernel, lds);
+            if (e == hipSuccess) hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), lds, stream, a);
+        };
+        if (!pick_le<4, 10>(a.r1, launch)) launch(int_c<16>{});
+    });
+    ND_HIP_CHECK(e);
+    return 1;
+}
+
+// true patch distances with a window or a patch along the third axis (round 6): nlmeans_patch3_kernel.
+// f0, f1, fz: the patch radii the distances use (0 in patch_mode 0, whose patch loops run once).
+static int try_patch_along_time(NlmTiledArgs a, uint32_t f0, uint32_t f1, uint32_t fz, hipStream_t stream)
+{
+    const int64_t ey = a.chi0 - a.clo0, ex = a.chi1 - a.clo1, nsl = a.chi2 - a.clo2;
+    if (a.nvars > 4) return 0;
+    // (3 x 3 patches, or none, in the plane; 5 x 5 and larger: the per-pixel kernel -- every instantiation costs
+    //  build time, and no caller of the reference uses them with a window along time)
+    if (f0 != f1 || f0 > 1 || fz > 1 || a.rz > 2 || a.r0 > kPatch3RMax || a.r1 > kPatch3RMax) return 0;
+    const int Fp = (int)f0;
+    const size_t np = 2 * (size_t)(a.rz + fz) + 1;
+    // 16-row tiles where their planes fit the LDS, 8-row tiles otherwise (seven planes of four variables)
+    int tyw = kPatch3TYW;
+    if (patch3_lds(np, a.nvars, tyw, Fp) > kBigLds) {
+        if (a.nvars < 3) return 0;
+        tyw = 2;
+    }
+    const size_t lds = patch3_lds(np, a.nvars, tyw, Fp);
+    a.tiles_x = (int)ceil_div(ex, 64 - 2 * Fp);
+    a.tiles_y = (int)ceil_div(ey, 4 * tyw);
+    const int64_t nb = (int64_t)a.tiles_x * a.tiles_y * nsl;
+    if (lds > kBigLds || nb > 0x7fffffffLL) return 0;
+    KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
+    return launch_patch3(a, Fp, (int)fz, tyw, nb, lds, stream) ? 1 : 0;
+}
+
+// true patch distances in the plane: the cross-lane form (3 x 3 to 7 x 7 patches), else one column per lane
+static int try_patch_planar(NlmTiledArgs a, uint32_t f0, uint32_t f1, hipStream_t stream)
+{
+    const int64_t ey = a.chi0 - a.clo0, ex = a.chi1 - a.clo1, nsl = a.chi2 - a.clo2;
+    // (round 6: patches of 9 x 9 and 11 x 11 -- f = 4, 5 -- in the one-column-per-lane kernel, whose sliding sums are
+    //  generic in F; before, they took the per-pixel kernel: r = 5, f = 4 on 4 x 1024 x 2048 177 ms)
+    if (f0 != f1 || f0 > 5 || a.nvars > 4) return 0;
+    static const bool no_patch2 = env_int("ND_AMD_NLM_PATCH1", 0) != 0;      // 1: one column per lane for every patch size
+    // (launch_patch2 sizes its own tile and checks its own limits: Patch2Geom<F> and Patch2Rows<V> need F and V as
+    //  constants, which only the launcher has; launch_patch and launch_patch3 are handed lds and the block count)
+    if (!no_patch2 && f0 >= 1 && f0 <= 3 && launch_patch2(a, (int)f0, stream)) return 1;
+    const int tyw = (a.nvars == 1) ? 16 : 8;
+    a.tiles_x = (int)ceil_div(ex, 64);
+    a.tiles_y = (int)ceil_div(ey, 4 * tyw);
+    const size_t cols = 64 + 2 * (a.r1 + f0), rows = 4 * tyw + 2 * (a.r0 + f0);
+    const size_t lds = (size_t)a.nvars * rows * cols * sizeof(float) + (rows + cols) * sizeof(int);
+    if (lds > kBigLds || (int64_t)a.tiles_x * a.tiles_y * nsl > 0x7fffffffLL) return 0;
+    KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
+    return launch_patch(a, (int)f0, nsl, lds, stream) ? 1 : 0;
+}
+
+// Try a tiled form; 1 = launched, 0 = not applicable.  g: the per-pixel kernel's arguments, checked and
+// filled (nlmeans_impl); the scalar parameters are copied from there.
+template <typename T>
+static int nlm_try_tiled(const NlmArgs<T> &g, const uint32_t r[3], const uint32_t f[3], double sigma, double h,
+                         int patch_mode, hipStream_t stream)
 {
     // float64 arrays: the uniform-weight window kernel only (the reference-compatible mode with
     // f > 0); everything else of float64 stays in the per-pixel kernel
-    const bool f64 = dtype != ND_AMD_F32;
-    if (f64 && !((patch_mode == 0) && (f[0] > 0 || f[1] > 0 || f[2] > 0))) return 0;
-    if (nvars < 1) return 0;
+    const bool f64 = sizeof(T) == 8;
+    const bool uniform = (patch_mode == 0) && (f[0] > 0 || f[1] > 0 || f[2] > 0);
+    if (f64 && !uniform) return 0;
+    if (g.nvars < 1) return 0;
     // Canonical axes of the tiled kernels: rows, contiguous columns, and a third axis that is
     // either a plain slice axis or (window kernel only) a window axis visited OUTERMOST.
     //   layout A: user axes (rows, cols, slices) -- e.g. (y, x, time): cols contiguous, r[2] = f[2] = 0
     //   layout B: user axes (z, rows, cols)      -- e.g. (time, y, x): cols contiguous, z = first
     //             filter dimension, so the reference visits it outermost (nd/_filters.pyx:363-370)
     int A0, A1, A2;
-    if (si[1] == 1 && so[1] == 1 && r[2] == 0 && f[2] == 0) {
+    if (g.si[1] == 1 && g.so[1] == 1 && r[2] == 0 && f[2] == 0) {
         A0 = 0; A1 = 1; A2 = 2;
-    } else if (si[2] == 1 && so[2] == 1) {
+    } else if (g.si[2] == 1 && g.so[2] == 1) {
         A0 = 1; A1 = 2; A2 = 0;
     } else {
         return 0;
@@ -1874,135 +1960,36 @@ static int nlm_try_tiled(const void *arr, void *out, int dtype, const int64_t N[
     const uint32_t rz = r[A2], fz = f[A2];
     if (r[A0] == 0 && r[A1] == 0 && rz == 0) return 0;
     for (int d = 0; d < 3; ++d)
-        if (G[d] > 0x3fffffff || N[d] > 0x3fffffff) return 0;
+        if (g.G[d] > 0x3fffffff || g.N[d] > 0x3fffffff) return 0;
     NlmTiledArgs a;
-    a.arr = static_cast<const float *>(arr);
-    a.out = static_cast<float *>(out);
-    a.N0 = N[A0]; a.N1 = N[A1]; a.N2 = N[A2];
-    a.G0 = G[A0]; a.G1 = G[A1]; a.Gz = G[A2];
-    a.off0 = toff[A0]; a.off1 = toff[A1]; a.offz = toff[A2];
-    a.clo0 = clo[A0]; a.chi0 = chi[A0]; a.clo1 = clo[A1]; a.chi1 = chi[A1];
-    a.clo2 = clo[A2]; a.chi2 = chi[A2];
-    a.si0 = si[A0]; a.si2 = si[A2]; a.si3 = si[3];
-    a.so0 = so[A0]; a.so2 = so[A2]; a.so3 = so[3];
+    a.arr = reinterpret_cast<const float *>(g.arr);
+    a.out = reinterpret_cast<float *>(g.out);
+    a.N0 = g.N[A0]; a.N1 = g.N[A1]; a.N2 = g.N[A2];
+    a.G0 = g.G[A0]; a.G1 = g.G[A1]; a.Gz = g.G[A2];
+    a.off0 = g.toff[A0]; a.off1 = g.toff[A1]; a.offz = g.toff[A2];
+    a.clo0 = g.clo[A0]; a.chi0 = g.chi[A0]; a.clo1 = g.clo[A1]; a.chi1 = g.chi[A1];
+    a.clo2 = g.clo[A2]; a.chi2 = g.chi[A2];
+    a.si0 = g.si[A0]; a.si2 = g.si[A2]; a.si3 = g.si[3];
+    a.so0 = g.so[A0]; a.so2 = g.so[A2]; a.so3 = g.so[3];
     a.r0 = (int)r[A0]; a.r1 = (int)r[A1]; a.f0 = (int)f[A0]; a.f1 = (int)f[A1];
     a.rz = (int)rz;
-    a.nvars = (int)nvars;
-    a.dsq_norm = (float)((((uint32_t)nvars * (2u * f[0] + 1u)) * (2u * f[1] + 1u)) * (2u * f[2] + 1u));
-    a.two_sigma2 = 2.0 * (sigma * sigma);
-    a.h2 = h * h;
-    a.n_eff = n_eff;
-    a.neff_policy = neff_policy;
-    a.status = status_dev;
-    const int64_t ey = a.chi0 - a.clo0, ex = a.chi1 - a.clo1, nsl = a.chi2 - a.clo2;
-    if (ey < 1 || ex < 1 || nsl < 1) return 0;
+    a.nvars = g.nvars;
+    a.tiles_x = a.tiles_y = 0;                 // (the regime's)
+    a.dsq_norm = (float)g.dsq_norm;            // (the unsigned product, a double holds it exactly: (float) of it either way)
+    a.two_sigma2 = g.two_sigma2; a.h2 = g.h2; a.n_eff = g.n_eff;
+    a.neff_policy = g.neff_policy; a.status = g.status;
+    if (a.chi0 - a.clo0 < 1 || a.chi1 - a.clo1 < 1 || a.chi2 - a.clo2 < 1) return 0;
 
-    const bool uniform = (patch_mode == 0) && (f[0] > 0 || f[1] > 0 || f[2] > 0);
-    if (uniform) {
-        // weight exp(-max(0 - 2 sigma^2, 0) / h^2) must be exactly 1
-        if (!(sigma == sigma) || !(h == h) || h == 0.0 || !(sigma * sigma < INFINITY)) return 0;
-        if (a.r1 > 16) return 0;
-        a.tiles_x = (int)ceil_div(ex, kWinTX);
-        a.tiles_y = (int)ceil_div(ey, kWinTY);
-        if (!f64 && rz == 1 && a.r0 == a.r1 && a.r1 >= 1 && a.r1 <= 5 &&
-            a.si0 >= 0 && (a.N0 * a.si0 + a.N1) * 4 < 0x7fffffffLL) {
-            const int64_t nbr = (int64_t)a.tiles_x * a.tiles_y * nvars;
-            if (nbr <= 0x7fffffffLL) {
-                KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-                if (launch_stream3(a, nbr, stream)) return 1;
-            }
-        }
-        if (!f64 && a.r0 <= kRollR0Max && a.r1 <= 10) {
-            const size_t nw = ((2 * (size_t)a.r1 + 4) + 3) / 4 * 4;
-            const size_t lds_r = (size_t)(2 * rz + 1) * (kWinTY + 2 * a.r0) * (kWinTX - 4 + nw) * sizeof(float);
-            const int64_t nbr = (int64_t)a.tiles_x * a.tiles_y * nvars;
-            if (lds_r <= kBigLds && nbr <= 0x7fffffffLL) {
-                KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-                if (launch_roll_r1(a, nbr, lds_r, stream)) return 1;
-            }
-        }
-        const int64_t nb = (int64_t)a.tiles_x * a.tiles_y * nsl;
-        const size_t rows = kWinTY + 2 * a.r0, cols = kWinTX + 2 * a.r1;
-        const size_t lds = (size_t)(2 * rz + 1) * rows * cols * (f64 ? sizeof(double) : sizeof(float)) +
-                           (rows + cols) * sizeof(int);
-        if (nb > 0x7fffffffLL) return 0;
-        // (float32 stays within the default limit; float64 may take up to kBigLds)
-        if (lds > (f64 ? kBigLds : 64 * 1024)) return 0;
-        KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-        hipError_t e = hipSuccess;
-        pick(f64, [&](auto F64) {
-            using T = std::conditional_t<decltype(F64)::value, double, float>;
-            auto launch = [&](auto R) {
-                constexpr auto kernel = &nlmeans_window_kernel<T, decltype(R)::value>;
-                if (lds > 64 * 1024) e = allow_dynamic_lds(kernel, lds);
-                if (e == hipSuccess) hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(256), lds, stream, a);
-            };
-            if (!pick_le<4, 10>(a.r1, launch)) launch(int_c<16>{});
-        });
-        ND_HIP_CHECK(e);
-        return 1;
-    }
+    if (uniform) return try_uniform(a, f64, sigma, h, stream);
     // true patch distances (patch_mode 1, or f = 0 in either mode: the loops run once)
-    if (rz != 0 || fz != 0) {
-        // a window along the third axis (round 6): nlmeans_patch3_kernel -- the visiting order is the
-        // reference's only where that axis is the outermost filter dimension (layout B)
-        const uint32_t F0z = (patch_mode == 1) ? f[A0] : 0u, F1z = (patch_mode == 1) ? f[A1] : 0u;
-        const uint32_t FZz = (patch_mode == 1) ? fz : 0u;
-        if (A2 != 0 || f64 || nvars > 4) return 0;
-        if (patch_mode == 0 && (f[A0] != 0 || f[A1] != 0 || fz != 0)) return 0;
-        // (3 x 3 patches, or none, in the plane; 5 x 5 and larger: the per-pixel kernel -- every instantiation costs
-        //  build time, and no caller of the reference uses them with a window along time)
-        if (F0z != F1z || F0z > 1 || FZz > 1 || rz > 2 || a.r0 > kPatch3RMax || a.r1 > kPatch3RMax) return 0;
-        const int Fp = (int)F0z;
-        const size_t cols3 = 64 + 2 * (size_t)kPatch3RMax;
-        const size_t np3 = 2 * (size_t)(rz + FZz) + 1;
-        // 16-row tiles where their planes fit the LDS, 8-row tiles otherwise (seven planes of four variables)
-        int tyw = kPatch3TYW;
-        size_t rows3 = 4 * (size_t)tyw + 2 * (size_t)(kPatch3RMax + Fp);
-        size_t lds3 = np3 * (size_t)nvars * rows3 * cols3 * sizeof(float) + (rows3 + cols3) * sizeof(int);
-        if (lds3 > kBigLds) {
-            if (nvars < 3) return 0;
-            tyw = 2;
-            rows3 = 4 * (size_t)tyw + 2 * (size_t)(kPatch3RMax + Fp);
-            lds3 = np3 * (size_t)nvars * rows3 * cols3 * sizeof(float) + (rows3 + cols3) * sizeof(int);
-        }
-        a.tiles_x = (int)ceil_div(ex, 64 - 2 * Fp);
-        a.tiles_y = (int)ceil_div(ey, 4 * tyw);
-        const int64_t nb3 = (int64_t)a.tiles_x * a.tiles_y * nsl;
-        if (lds3 > kBigLds || nb3 > 0x7fffffffLL) return 0;
-        KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-        return launch_patch3(a, Fp, (int)FZz, tyw, nb3, lds3, stream) ? 1 : 0;
-    }
+    if (patch_mode == 0 && (f[A0] != 0 || f[A1] != 0 || fz != 0)) return 0;
     const uint32_t F0 = (patch_mode == 1) ? f[A0] : 0u, F1 = (patch_mode == 1) ? f[A1] : 0u;
-    if (patch_mode == 0 && (f[A0] != 0 || f[A1] != 0)) return 0;
-    // (round 6: patches of 9 x 9 and 11 x 11 -- f = 4, 5 -- in the one-column-per-lane kernel, whose sliding sums are
-    //  generic in F; before, they took the per-pixel kernel: r = 5, f = 4 on 4 x 1024 x 2048 177 ms)
-    if (F0 != F1 || F0 > 5 || nvars > 4) return 0;
-    static const bool no_patch2 = env_int("ND_AMD_NLM_PATCH1", 0) != 0;      // 1: one column per lane for every patch size
-    if (!no_patch2 && F0 >= 1 && F0 <= 3) {
-        // cross-lane form: two columns per lane
-        const int hl = (F0 == 3) ? 2 : 1, tx2 = 2 * (64 - 2 * hl), tyw2 = (nvars == 1) ? Patch2Rows<1>::TYW : Patch2Rows<2>::TYW;
-        int m = a.r1 + 2 * hl + (a.r1 & 1);
-        if (m <= kPatch2Margin) m = kPatch2Margin;     // the constant-pitch instantiation (launch_patch2)
-        const size_t cols2 = (size_t)tx2 + 2 * (size_t)m, rows2 = 4 * (size_t)tyw2 + 2 * (size_t)(a.r0 + F0);
-        const size_t lds2 = (size_t)nvars * rows2 * cols2 * sizeof(float) + (rows2 + cols2) * sizeof(int);
-        a.tiles_x = (int)ceil_div(ex + 1, tx2);        // + 1: the tiles start on an even global column
-        a.tiles_y = (int)ceil_div(ey, 4 * tyw2);
-        if (lds2 <= kBigLds && (int64_t)a.tiles_x * a.tiles_y * nsl <= 0x7fffffffLL) {
-            KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-            if (launch_patch2(a, (int)F0, nsl, lds2, stream)) return 1;
-        }
+    if (rz != 0 || fz != 0) {
+        // the visiting order is the reference's only where that axis is the outermost filter dimension (layout B)
+        if (A2 != 0) return 0;
+        return try_patch_along_time(a, F0, F1, (patch_mode == 1) ? fz : 0u, stream);
     }
-    const int tyw = (nvars == 1) ? 16 : 8;
-    a.tiles_x = (int)ceil_div(ex, 64);
-    a.tiles_y = (int)ceil_div(ey, 4 * tyw);
-    const size_t cols = 64 + 2 * (a.r1 + F0);
-    const size_t rows = 4 * tyw + 2 * (a.r0 + F0);
-    const size_t lds = (size_t)nvars * rows * cols * sizeof(float) + (rows + cols) * sizeof(int);
-    if (lds > kBigLds) return 0;
-    if ((int64_t)a.tiles_x * a.tiles_y * nsl > 0x7fffffffLL) return 0;
-    KernelTimer timer(ND_AMD_KERNEL_NLMEANS_TILED, stream);
-    return launch_patch(a, (int)F0, nsl, lds, stream) ? 1 : 0;
+    return try_patch_planar(a, F0, F1, stream);
 }
 
 template <typename T>
@@ -2071,9 +2058,7 @@ static int nlmeans_impl(const void *arr, void *out, const int64_t N[3], int64_t 
     if (status_dev) ND_HIP_CHECK(hipMemsetAsync(status_dev, 0, sizeof(int32_t), stream));
     if (a.total == 0) return ND_AMD_OK;
 
-    if (nlm_try_tiled(arr, out, sizeof(T) == 4 ? ND_AMD_F32 : ND_AMD_F64, N, nvars, si, so, r, f,
-                      sigma, h, n_eff, patch_mode, neff_policy, status_dev, G, toff, clo, chi,
-                      stream)) {
+    if (nlm_try_tiled(a, r, f, sigma, h, patch_mode, stream)) {
         ND_HIP_CHECK(hipGetLastError());
         return ND_AMD_OK;
     }
