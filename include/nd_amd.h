@@ -106,6 +106,7 @@ extern "C" {
 #define ND_AMD_KERNEL_SPECKLE         29  /* nd_amd_speckle_lee and nd_amd_speckle_multitemporal, the whole call */
 #define ND_AMD_KERNEL_REGIONS         30  /* nd_amd_label_regions, nd_amd_region_sizes, nd_amd_sieve_regions, the whole call */
 #define ND_AMD_KERNEL_ZONAL           31  /* nd_amd_zonal_keys, nd_amd_zonal_stats, nd_amd_zonal_paint, the whole call */
+#define ND_AMD_KERNEL_TEMPORAL        32  /* nd_amd_temporal_stats, the whole call */
 
 /* layouts of nd_amd_warp_translate */
 #define ND_AMD_LAYOUT_PLANAR       0   /* (time, row, col), col fastest */
@@ -1311,6 +1312,87 @@ int nd_amd_zonal_stats(const void *values, int dtype, int64_t nplanes, int64_t n
 int nd_amd_zonal_paint(const int32_t *keys, const double *table, int64_t nplanes, int64_t ny, int64_t nx,
                        int64_t n, const void *src, const int64_t *src_strides,   /* NULL: fill               */
                        void *dst, const int64_t *dst_strides, int dtype, double fill, void *hip_stream);
+
+/* ----------------------------------------------------------------------
+ * Statistics along time: per-pixel reductions over the dates of a stack --
+ * count, sum, mean, second moment, variance, standard deviation, coefficient
+ * of variation, minimum and maximum with their dates, the median and any
+ * percentiles.  The reference has no counterpart; the moments are this
+ * project's definition, the order statistics numpy 2.2.6's
+ * (np.nanmedian, np.nanpercentile; np.median, np.percentile with skipna = 0),
+ * and tests/temporal_ref.py restates all of it bit for bit.
+ *
+ *   Per pixel, x[0 .. k - 1] is the series in date order, of type T
+ *   (ND_AMD_F32, ND_AMD_F64).  "double" below is float64, bracketed as
+ *   written, nothing fused (-ffp-contract=off).  With skipna != 0 the valid
+ *   dates are those with x[t] not NaN; with skipna == 0 every date is valid
+ *   and NaN enters the arithmetic as it is.
+ *       n = the number of valid dates (count); nan_count = the NaN dates
+ *           (in both modes)
+ *       sum = 0.0;  for valid t ascending:  sum = sum + double(x[t])
+ *       mean = sum / double(n)                        (0 / 0 = NaN for n = 0)
+ *       m2 = 0.0;   for valid t ascending:  d = double(x[t]) - mean;
+ *                                           m2 = m2 + d * d
+ *       var = m2 / double(n - ddof) if n - ddof > 0 else NaN
+ *       std = sqrt(var), correctly rounded;  cv = std / mean
+ *       min, max     the smallest / largest valid value; NaN for n = 0, and
+ *                    with skipna == 0 NaN if any date is NaN
+ *       argmin, argmax   the first date whose value == min / max; -1 for
+ *                    n = 0; with skipna == 0 the first NaN date if there is one
+ *       order statistics   the valid values sorted ascending, A_0 <= ... <=
+ *                    A_{n-1}; NaN for n = 0, and with skipna == 0 NaN if any
+ *                    date is NaN
+ *         percentile p   exactly the arithmetic of nd_amd_rgb_limits in T:
+ *                    q = T(p) / T(100), vi = T(n - 1) * q, lo = floor(vi),
+ *                    hi = min(lo + 1, n - 1) (both n - 1 where vi >= T(n - 1)),
+ *                    g = vi - lo, d = A_hi - A_lo; A_lo + d * g, or
+ *                    A_hi - d * (1 - g) where g >= 0.5; every operation
+ *                    rounded to T
+ *         median     A_{(n-1)/2} for odd n, (A_{n/2-1} + A_{n/2}) / T(2) in T
+ *                    for even n (np.nanmedian's arithmetic, not percentile 50's)
+ *   Infinities are ordinary values and nothing is special-cased.  The sign of
+ *   a zero result of min, max, the median or a percentile is not pinned, and
+ *   neither are the payload and sign of a NaN result.
+ *
+ * x holds element (t, y, x) at x[t * strides[0] + y * strides[1] + x *
+ * strides[2]]: 3 host values in elements for (series, y, x), none negative;
+ * (time, y, x) and (y, x, time) stacks, crops and steps are read where they
+ * lie, and a (time, x) variable is ny = 1.  percentiles: a host array of
+ * npercentiles values in [0, 100].  Outputs, device memory, each (ny, nx)
+ * contiguous and each NULL to skip it: count, nan_count, argmin, argmax int32;
+ * sum, mean, m2, var, std, cv float64; min, max, median of type T;
+ * percentile_out (npercentiles, ny, nx) of type T.
+ *
+ * Forms (nd_amd/csrc/temporal.hip), chosen by k, the type, the strides and
+ * whether an order statistic is asked for, all giving the same bits: series of at most
+ * ND_AMD_TEMPORAL_REG_MAX_* dates are held in registers; order statistics of
+ * at most ND_AMD_TEMPORAL_LDS_MAX_* dates are sorted in LDS; the moments alone
+ * are served for every k by two walks over memory (through the LDS tile where
+ * a series of stride 1 fits it).  No workspace, nothing is synchronised,
+ * every launch goes to hip_stream.
+ * ND_AMD_EINVAL before any HIP call for a bad dtype, negative sizes or
+ * strides, k < 1, ddof < 0, a percentile outside [0, 100] (NaN included) and
+ * a null data pointer; ND_AMD_EUNSUPPORTED for planes of 2^31 pixels or more,
+ * for order statistics of more than ND_AMD_TEMPORAL_LDS_MAX_* dates and for
+ * more than 2^26 - 1 blocks of 64 pixels (only a strided view of that many
+ * short rows gets there); ND_AMD_OK with nothing done for an empty plane or
+ * when no output is asked for.
+ * ---------------------------------------------------------------------- */
+#define ND_AMD_TEMPORAL_REG_MAX_F32 64     /* the longest series of the register form                         */
+#define ND_AMD_TEMPORAL_REG_MAX_F64 64
+#define ND_AMD_TEMPORAL_LDS_MAX_F32 256    /* the longest series whose order statistics are served: a tile of */
+#define ND_AMD_TEMPORAL_LDS_MAX_F64 128    /* 64 pixels x k in 64 KiB of LDS                                  */
+
+int nd_amd_temporal_stats(const void *x, int dtype, int64_t k, int64_t ny, int64_t nx,
+                          const int64_t *strides,                      /* 3 host values: series, y, x       */
+                          int skipna, int ddof,
+                          const double *percentiles, int npercentiles, /* host                              */
+                          int32_t *count, int32_t *nan_count,          /* (ny, nx) each, NULL to skip       */
+                          double *sum, double *mean, void *min, void *max,
+                          int32_t *argmin, int32_t *argmax,
+                          double *m2, double *var, double *std, double *cv,
+                          void *median, void *percentile_out,          /* (npercentiles, ny, nx)            */
+                          void *hip_stream);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,7 @@ KERNEL_NAMES = {1: 'omnibus_c2_global', 2: 'omnibus_c2_search', 3: 'correlate',
                 17: 'classify_forest', 18: 'classify_kmeans', 19: 'classify_gather', 20: 'class_mean',
                 21: 'classify_knn', 22: 'classify_linear', 23: 'kmeans_step', 24: 'feature_moments',
                 25: 'gather_rows', 26: 'change_segments', 27: 'rasterize', 28: 'resample', 29: 'speckle', 30: 'regions',
-                31: 'zonal'}
+                31: 'zonal', 32: 'temporal'}
 LAYOUT_PLANAR, LAYOUT_PIXEL_MAJOR = 0, 1
 STRUCT_DIAG, STRUCT_C2, STRUCT_C3 = 0, 1, 2
 
@@ -53,7 +53,8 @@ SYMBOLS = ('nd_amd_abi_version', 'nd_amd_last_error',
            'nd_amd_resample', 'nd_amd_resample_nearest', 'nd_amd_resample_check_table',
            'nd_amd_speckle_lee', 'nd_amd_speckle_multitemporal_workspace_bytes', 'nd_amd_speckle_multitemporal',
            'nd_amd_regions_workspace_bytes', 'nd_amd_label_regions', 'nd_amd_region_sizes', 'nd_amd_sieve_regions',
-           'nd_amd_zonal_keys', 'nd_amd_zonal_workspace_bytes', 'nd_amd_zonal_stats', 'nd_amd_zonal_paint')
+           'nd_amd_zonal_keys', 'nd_amd_zonal_workspace_bytes', 'nd_amd_zonal_stats', 'nd_amd_zonal_paint',
+           'nd_amd_temporal_stats')
 CLASSIFY_BLOCK_ROWS, CLASSIFY_MAX_FEATURES = 1024, 1024
 CLASSIFY_KNN_MAX_K, CLASSIFY_KNN_MAX_FEATURES, CLASSIFY_KNN_TILE = 32, 128, 8
 KMEANS_FIT_MAX_ACC = 4096
@@ -63,6 +64,11 @@ SPECKLE_METHODS = {'lee': 0, 'kuan': 1}
 # include/nd_amd.h: ND_AMD_SPECKLE_MAX_W, _MAX_VARIABLES, _HOT_MAX_PLANES, _TILE_Y, _TILE_X, _HOT_TILE_Y
 SPECKLE_MAX_W, SPECKLE_MAX_VARIABLES, SPECKLE_HOT_MAX_PLANES = 31, 4, 32
 SPECKLE_TILE_Y, SPECKLE_TILE_X, SPECKLE_HOT_TILE_Y = 32, 64, 8
+# include/nd_amd.h: ND_AMD_TEMPORAL_REG_MAX_*, _LDS_MAX_*; the forms that nd_amd_temporal_stats_in_form names, an
+# entry of temporal.hip for the tests that is in no header (kernels.temporal_stats binds it where `_form` is used)
+TEMPORAL_REG_MAX = {F32: 64, F64: 64}
+TEMPORAL_LDS_MAX = {F32: 256, F64: 128}
+TEMPORAL_FORMS = {'register': 1, 'lds': 2, 'stream': 3}
 LINKS = {'none': 0, 'softmax': 1, 'ovr': 2}
 LINEAR_OUTPUTS = {'predict': 0, 'decision_function': 1, 'predict_proba': 2}
 
@@ -239,6 +245,8 @@ def lib():
     L.nd_amd_zonal_stats.argtypes = [vp, i32, i64, i64, i64, pi64, vp, vp, i64] + [vp] * 6 + [vp, C.c_size_t, vp]
     L.nd_amd_zonal_paint.restype = i32
     L.nd_amd_zonal_paint.argtypes = [vp, vp, i64, i64, i64, i64, vp, pi64, vp, pi64, i32, dbl, vp]
+    L.nd_amd_temporal_stats.restype = i32
+    L.nd_amd_temporal_stats.argtypes = [vp, i32, i64, i64, i64, pi64, i32, i32, C.POINTER(dbl), i32] + [vp] * 14 + [vp]
     v = L.nd_amd_abi_version()
     if v != 1:
         raise ImportError('nd_amd: libnd_amd.so has ABI version %d, expected 1' % v)

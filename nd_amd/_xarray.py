@@ -3,7 +3,8 @@ nd_amd/_xarray.py -- optional xarray accessors mirroring nd/_xarray.py:135-161 f
 this package provides: `ds.nd_amd.change_omnibus(...)`, `ds.nd_amd.nlmeans(...)`,
 `ds.nd_amd.boxcar(...)`, `ds.nd_amd.convolve(...)`, `ds.nd_amd.gaussian(...)`, `ds.nd_amd.to_rgb(...)`,
 `ds.nd_amd.resample(...)`, `ds.nd_amd.reproject(...)`, `ds.nd_amd.lee(...)`, `ds.nd_amd.multitemporal(...)`,
-`ds.nd_amd.sieve(...)`, `ds.nd_amd.label_regions(...)`, `ds.nd_amd.zonal_stats(...)`, `ds.nd_amd.zonal_paint(...)`.
+`ds.nd_amd.sieve(...)`, `ds.nd_amd.label_regions(...)`, `ds.nd_amd.zonal_stats(...)`, `ds.nd_amd.zonal_paint(...)`,
+`ds.nd_amd.temporal_stats(...)`, `ds.nd_amd.composite(...)`.
 
 Registered only when xarray is importable (it is not installed in the build or GPU images); the
 accessor name differs from the reference's (`nd`, `filter`) so both can be loaded side by side.
@@ -29,6 +30,8 @@ _METHODS = {
     'label_regions': ('regions', 'label_regions'),
     'zonal_stats': ('zonal', 'zonal_stats'),
     'zonal_paint': ('zonal', 'zonal_paint'),
+    'temporal_stats': ('temporal', 'temporal_stats'),
+    'composite': ('temporal', 'composite'),
 }
 
 
@@ -59,8 +62,9 @@ def register():
     """Attach the `nd_amd` accessor to xarray Datasets and DataArrays; False without xarray."""
     if xr is None:
         return False
-    from . import change, filters, regions, warp, zonal
-    modules = {'change': change, 'filters': filters, 'regions': regions, 'warp': warp, 'zonal': zonal}
+    from . import change, filters, regions, temporal, warp, zonal
+    modules = {'change': change, 'filters': filters, 'regions': regions, 'warp': warp, 'zonal': zonal,
+               'temporal': temporal}
     namespace = {'__init__': lambda accessor, obj: setattr(accessor, '_obj', obj)}
     for name, (module, function) in _METHODS.items():
         namespace[name] = _forward(getattr(modules[module], function))

@@ -65,10 +65,14 @@ PER_FILE = {'nlmeans.hip': ['-fno-slp-vectorize'],
 # fully unrolled loop over the planes; a spill would put the values it exists to keep on chip into memory
 # regions.hip: the union-find keeps its parents in LDS and in the parent plane; its kernels have no private array
 # zonal.hip: plane p's running sums live in lane p and the eight loads in flight are indexed by an unrolled loop
+# temporal.hip: the register form keeps a pixel's series in up to 64 registers, sorts it by a network with constant
+# indices and reads a rank by a select chain; an instantiation that spills is taken off the list in temporal.hip
+# (ND_AMD_TEMPORAL_REG_MAX_*), not tolerated
 NO_SCRATCH = {'omnibus_ml.hip': 'omnibus_c2_ml_kernel', 'rgb.hip': 'rgb_', 'classify.hip': 'class',
               'kmeans_fit.hip': '_kernel', 'omnibus_diag.hip': 'omnibus_diag_',
               'change_segments.hip': 'change_segments_kernel', 'rasterize.hip': 'rasterize_', 'resample.hip': 'resample_',
-              'speckle.hip': 'speckle_', 'regions.hip': 'regions_', 'zonal.hip': 'zonal_'}
+              'speckle.hip': 'speckle_', 'regions.hip': 'regions_', 'zonal.hip': 'zonal_',
+              'temporal.hip': 'temporal_'}
 # bytes per lane by the kernel's template arguments <K, KMAX, STATS, CHAIN>, keyed (STATS, CHAIN)
 SCRATCH_BUDGET = {(False, False): 0, (False, True): 96, (True, False): 256, (True, True): 384}
 

@@ -2365,6 +2365,106 @@ def zonal_paint(table, index, like=None, out=None, keep=False, fill=None, dims=N
     return out
 
 
+# ---------------------------------------------------------------------------
+# statistics along time (include/nd_amd.h "Statistics along time"; tests/temporal_ref.py restates it bit for bit)
+# ---------------------------------------------------------------------------
+TEMPORAL_STATS = ('count', 'nan_count', 'sum', 'mean', 'min', 'max', 'argmin', 'argmax', 'm2', 'var', 'std', 'cv',
+                  'median')
+# the order of nd_amd_temporal_stats' outputs
+_TEMPORAL_OUT = ('count', 'nan_count', 'sum', 'mean', 'min', 'max', 'argmin', 'argmax', 'm2', 'var', 'std', 'cv',
+                 'median')
+_TEMPORAL_INT = ('count', 'nan_count', 'argmin', 'argmax')
+_TEMPORAL_T = ('min', 'max', 'median')
+# the longest series the register form holds, and the longest whose order statistics are served (the LDS form)
+TEMPORAL_REG_MAX = {torch.float32: _lib.TEMPORAL_REG_MAX[_lib.F32], torch.float64: _lib.TEMPORAL_REG_MAX[_lib.F64]}
+TEMPORAL_LDS_MAX = {torch.float32: _lib.TEMPORAL_LDS_MAX[_lib.F32], torch.float64: _lib.TEMPORAL_LDS_MAX[_lib.F64]}
+
+
+def temporal_percentiles(q):
+    """`q` (None, a number or a sequence of numbers) as a tuple of floats in [0, 100]; ValueError otherwise"""
+    if q is None:
+        return ()
+    values = [q] if np.ndim(q) == 0 else list(q)
+    out = []
+    for p in values:
+        if isinstance(p, (bool, str)) or not np.isreal(p) or not 0 <= float(p) <= 100:
+            raise ValueError('q must be numbers in [0, 100], got %r' % (p,))
+        out.append(float(p))
+    names = [temporal_percentile_name(p) for p in out]
+    if len(set(names)) != len(names):
+        raise ValueError('q holds percentiles that share a name (%s): each is named with %%g'
+                         % ', '.join(sorted(n for n in set(names) if names.count(n) > 1)))
+    return tuple(out)
+
+
+def _temporal_in_form(form):
+    """nd_amd_temporal_stats_in_form (temporal.hip; in no header) with `form` bound: the tests' way to one kernel form"""
+    fn = _lib.lib().nd_amd_temporal_stats_in_form
+    if fn.argtypes is None:
+        fn.restype = C.c_int
+        fn.argtypes = list(_lib.lib().nd_amd_temporal_stats.argtypes[:-1]) + [C.c_int, C.c_void_p]
+    return lambda *args: fn(*(args[:-1] + (_lib.TEMPORAL_FORMS[form], args[-1])))
+
+
+def temporal_percentile_name(p):
+    """the key of percentile p in temporal_stats' result: 'p2', 'p97.5'"""
+    return 'p%g' % p
+
+
+def temporal_stats(x, stats=('mean', 'std'), q=(), skipna=True, ddof=0, axis=0, _form='auto'):
+    """Per-pixel statistics along axis `axis` of a 3-D ROCm tensor with any non-negative strides: the other two axes,
+    in their order, are (y, x), so a (time, y, x) stack has axis=0 and a (y, x, time) stack axis=2; both are read where
+    they lie.  float32 and float64 are computed as they are, every other real type as float64.  stats: names among
+    TEMPORAL_STATS; q: percentiles in [0, 100].  -> a dict of (ny, nx) tensors: the statistics by name, percentile p as
+    temporal_percentile_name(p); min, max, median and percentiles of the type computed in, count, nan_count, argmin
+    and argmax int32, the rest float64.  Order statistics of series longer than TEMPORAL_LDS_MAX raise
+    NotImplementedError; the moments are served for every length.  `_form` names one kernel form for the tests."""
+    stats = (stats,) if isinstance(stats, str) else tuple(stats)
+    for s in stats:
+        if s not in TEMPORAL_STATS:
+            raise ValueError('stats must be among %s, got %r' % (TEMPORAL_STATS, s))
+    q = temporal_percentiles(q)
+    if isinstance(ddof, bool) or int(ddof) != ddof or ddof < 0:
+        raise ValueError('ddof must be a non-negative integer, got %r' % (ddof,))
+    if not isinstance(x, torch.Tensor):
+        raise TypeError('x must be a torch.Tensor, got %r' % type(x))
+    if x.is_complex():
+        raise TypeError('x is complex: statistics along time are defined on real data')
+    if x.dim() != 3:
+        raise ValueError('x must have three axes (the series and y, x), got %d' % x.dim())
+    if not x.is_cuda:
+        raise ValueError('x must live on a ROCm device (got %s); nd_amd has no CPU path' % x.device)
+    if x.dtype not in _DT:
+        x = x.to(torch.float64)
+    axis = axis % 3
+    view = x.movedim(axis, 0)
+    k, ny, nx = view.shape
+    if k < 1:
+        raise ValueError('the series has no date')
+    if (('median' in stats or q) and k > TEMPORAL_LDS_MAX[x.dtype]
+            and not (_form == 'register' and k <= TEMPORAL_REG_MAX[x.dtype])):
+        raise NotImplementedError('order statistics of %s series are served up to %d dates (TEMPORAL_LDS_MAX), got %d'
+                                  % (x.dtype, TEMPORAL_LDS_MAX[x.dtype], k))
+    dev = x.device
+    with torch.cuda.device(dev):
+        out = {s: torch.empty((ny, nx), dtype=torch.int32 if s in _TEMPORAL_INT else
+                              (x.dtype if s in _TEMPORAL_T else torch.float64), device=dev)
+               for s in _TEMPORAL_OUT if s in stats}
+        pct = torch.empty((len(q), ny, nx), dtype=x.dtype, device=dev) if q else None
+        if ny * nx:
+            entry = _lib.lib().nd_amd_temporal_stats if _form == 'auto' else _temporal_in_form(_form)
+            _lib.check(entry(
+                _ptr(view), _DT[x.dtype], k, ny, nx, _lib.i64_array(view.stride()), int(bool(skipna)), int(ddof),
+                (C.c_double * len(q))(*q) if q else None, len(q),
+                *([_ptr(out[s]) if s in out else None for s in _TEMPORAL_OUT] + [_ptr(pct) if q else None]),
+                _stream_ptr(dev)))
+            _record([x, pct] + list(out.values()), dev)
+    res = {s: out[s] for s in stats}
+    for j, p in enumerate(q):
+        res[temporal_percentile_name(p)] = pct[j]
+    return res
+
+
 def _lib_device(device=None):
     if device is not None:
         return torch.device(device)
